@@ -11,9 +11,15 @@ to rank 0 (RCCL), enqueued on the stream the render runs on.
 started by a launcher; under a launcher (RANK / WORLD_SIZE in the environment) it is one of the ranks.
 
 Prints ONE JSON line on rank 0.  `value` = rays of all ranks / max-over-ranks wall time of the K timed
-steps (inputs resident in HBM; barrier + synchronize on both sides).
+steps (inputs resident in HBM; barrier + synchronize on both sides); `ms_per_step` = that wall time / K.
 
-After the timed steps, and outside `value`, the N = 1 run starts ONE child process (`--side-child`; a child, never an exec; the
+A plain run does only that: set-up, W warm-up steps, the K timed steps, `--dump-outputs DIR` (the last timed step's image,
+`DIR/image.npy`, float32 row sums of all samples, (H, W, 3) -- a seeded sample of rows, listed in `DIR/image_rows.npy`, when the frame
+exceeds 48 MiB -- and its ray count, `DIR/rays.npy`, float64) and the line.  Everything else it can measure or check runs with `--full`:
+the measured copy bandwidth (`roofline.measured_copy_bw`), the oracle's check of the gathered image of an N > 1 run (`parity`), the
+CPU baseline and its parity leg at N = 1 (`cpu_baseline`, `parity`), and the side measurements below.
+
+With `--full`, after the timed steps, and outside `value`, the N = 1 run starts ONE child process (`--side-child`; a child, never an exec; the
 headline numbers are already on disk in gpurun_out/bench_headline.json by then, and a fault, hang or time-out of the child costs only
 its own fields) that measures on this one GPU:
   `secondary`         the other BASELINE configurations: config 3 at its full size, and ONE rank's share of configs 4 and 5 (its stripes
@@ -398,6 +404,27 @@ def run_side_child(args, timeout_s: float = 420.0):
     return {"side_error": f"the side-measurement child ended with code {r.returncode} and no result"}
 
 
+DUMP_IMAGE_LIMIT = 48 << 20      # bytes of image.npy; a larger frame is dumped as a seeded sample of its rows
+
+
+def dump_outputs(out_dir: str, image, rays: int):
+    """`--dump-outputs DIR`: what a caller of the timed path receives from its last step -- the (H, W, 3) float32 row sums of the gathered
+    frame and the step's ray count -- so that two builds can be compared output for output (same arguments, same inputs)."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes > DUMP_IMAGE_LIMIT:
+        n = max(1, DUMP_IMAGE_LIMIT // (image.nbytes // image.shape[0]))
+        rows = np.sort(np.random.default_rng(0).choice(image.shape[0], size=n, replace=False))
+        image = image[rows]
+        np.save(d / "image_rows.npy", rows.astype(np.float64))
+    else:
+        (d / "image_rows.npy").unlink(missing_ok=True)
+    np.save(d / "image.npy", image)
+    np.save(d / "rays.npy", np.array([rays], dtype=np.float64))
+
+
 def free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -523,6 +550,11 @@ def main():
     ap.add_argument("--spp", type=int, default=1024)
     ap.add_argument("--spp-per-launch", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=12345)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: copy bandwidth, CPU baseline + parity, the oracle check of an N > 1 "
+                         "run, and the side measurements at N = 1 (configs 3 / 4 / 5, projected scaling, cold start)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR: image.npy (float32 row sums, (H, W, 3)) and rays.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the child process that follows the timed steps at N = 1 (configs 3 / 4 / 5, projected scaling, cold start)")
     ap.add_argument("--side-child", action="store_true", help=argparse.SUPPRESS)
@@ -629,13 +661,15 @@ def main():
     fence()
     t0 = time.perf_counter()
     total_rays_local, kernel_ms, n_launch = 0, 0.0, 0
+    last_rays_local = 0
     img = None
     step_walls = []                                                    # this rank's own step: clear -> launches -> gather enqueued -> its stream drained
     for _ in range(args.steps):
         ts = time.perf_counter()
         img = step(timed=True)
         # ray counter and kernel times are read after the step's work is enqueued; download syncs the stream
-        total_rays_local += tracer.ray_count()
+        last_rays_local = tracer.ray_count()
+        total_rays_local += last_rays_local
         step_walls.append((time.perf_counter() - ts) * 1e3)
         nl, ms = tracer.kernel_time()
         kernel_ms += ms; n_launch += nl
@@ -644,7 +678,7 @@ def main():
 
     red_dev = "cpu" if args.rehearse_on_one_gpu else f"cuda:{local_rank}"
     t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
-    r = torch.tensor([total_rays_local], dtype=torch.int64, device=red_dev)
+    r = torch.tensor([total_rays_local, last_rays_local], dtype=torch.int64, device=red_dev)
     k = torch.tensor([kernel_ms / max(n_launch, 1)], dtype=torch.float64, device=red_dev)
     gms = [a_.elapsed_time(b_) for a_, b_ in gather_events]            # (the fence above has synchronised them)
     g = torch.tensor([sum(gms) / len(gms) if gms else 0.0], dtype=torch.float64, device=red_dev)
@@ -653,7 +687,7 @@ def main():
         dist.all_reduce(r, op=dist.ReduceOp.SUM)
         dist.all_reduce(k, op=dist.ReduceOp.MAX)
         dist.all_reduce(g, op=dist.ReduceOp.MAX)
-    dt_max, rays, kern_ms, gather_ms = float(t.item()), int(r.item()), float(k.item()), float(g.item())
+    dt_max, rays, last_rays, kern_ms, gather_ms = float(t.item()), int(r[0].item()), int(r[1].item()), float(k.item()), float(g.item())
     per_rank = None
     if collective:
         own_gather = (sum(gms) / len(gms)) if gms else ((sum(gather_host_ms) / len(gather_host_ms)) if gather_host_ms else 0.0)
@@ -664,6 +698,8 @@ def main():
     if rank == 0 and os.environ.get("AMBER_BENCH_SAVE_IMAGE") and img is not None:
         torch.cuda.synchronize()
         np.save(os.environ["AMBER_BENCH_SAVE_IMAGE"], img.detach().cpu().numpy())
+    if rank == 0 and args.dump_outputs and img is not None:
+        dump_outputs(args.dump_outputs, img.detach().cpu().numpy().reshape(H, W, 3), last_rays)
     if rank == 0:
         rays_per_launch_local = total_rays_local / max(n_launch, 1)
         achieved = rays_per_launch_local * BYTES_PER_RAY / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
@@ -700,7 +736,7 @@ def main():
             # rays: over the timed steps; kernel_ms: mean per launch; step_wall_ms: the rank's own step until its stream has drained (the gather included:
             # on rank 0 that waits for every rank's rows); gather_ms: the collective + re-ordering on the render stream (host time in the gloo rehearsal)
             out["per_rank"] = per_rank
-        if world > 1 and not args.no_parity and img is not None:
+        if world > 1 and args.full and not args.no_parity and img is not None:
             # the checker's leg of an N > 1 run: 16 rows of the GATHERED image (row sums of all samples) against the oracle, on rank 0, outside the timed region
             try:
                 sys.path.insert(0, str(ROOT / "tests"))
@@ -731,7 +767,7 @@ def main():
                 out["roofline"]["valu"] = None
                 out["roofline"]["valu_withheld"] = (f"profiles/{summ[0]} measured {prof_ms:.3f} ms per launch, this run {kern_ms:.3f} ms (or another workload / rank count): "
                                                     "more than 5 % apart, the profile is stale for this kernel -- re-run tools/profile.sh")
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 bw = measured_copy_bandwidth(torch, f"cuda:{local_rank}")
                 out["roofline"]["measured_copy_bw"] = round(bw, 1)
@@ -739,7 +775,7 @@ def main():
             except Exception as e:                                     # never lose the bench line over the side measurement
                 out["roofline"]["measured_copy_bw"] = None
                 out["roofline"]["measured_copy_bw_error"] = str(e)[:120]
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             # The headline is measured: make it durable before anything else can go wrong, then run the side measurements
             # in a child process -- a GPU fault or a hang there costs only `secondary` / `projected_scaling` / `cold_start`.
             try:
@@ -760,7 +796,7 @@ def main():
             for k, v in side.items():
                 if k.endswith("_error"):
                     out[k] = v
-        if not args.no_cpu_baseline and world == 1:                    # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only
             out["cpu_baseline"], out["parity"] = cpu_baseline(amber_amd, W, args.spp, args.seed)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

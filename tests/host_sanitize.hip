@@ -76,8 +76,9 @@ static void CheckReferenceBvh(const std::vector<AmberFlatObject>& flat, const ch
   std::printf("ok   reference bvh %-22s objects %zu inner %u leaves %u (largest %u) depth %u\n", what, flat.size(), t.n_inner, t.n_leaves, t.largest_leaf, t.depth);
 }
 
-int main() {
+int main(int argc, char** argv) {
   using namespace amber;
+  const std::string out = argc > 1 ? argv[1] : ".";                              // where the writers and the import cases put their files
   // 1. Cornell box: flatten + filter program
   {
     const auto scene = etude::CornelBox(0.050f, 0.050f, 6);
@@ -211,14 +212,14 @@ int main() {
   {
     postprocess::HDRImage img(33, 17);
     for (unsigned y = 0; y < 17; y++) for (unsigned x = 0; x < 33; x++) img[prelude::Pixel(x, y)] = postprocess::HDR(0.001f * x, 0.002f * y, 0.5f);
-    cli::ExportPNG(postprocess::Gamma()(postprocess::Filmic()(img)), "/tmp/amber_sanitize.png");
-    cli::ExportEXR(img, "/tmp/amber_sanitize.exr");
+    cli::ExportPNG(postprocess::Gamma()(postprocess::Filmic()(img)), out + "/amber_sanitize.png");
+    cli::ExportEXR(img, out + "/amber_sanitize.exr");
     std::printf("ok   png/exr writers\n");
   }
   // 5. scene import: well-formed, malformed and random inputs must parse or throw, never read out of bounds
   {
-    const std::string dir = "/tmp/amber_sanitize_import";
-    (void)std::system(("mkdir -p " + dir).c_str());
+    const std::string dir = out + "/amber_sanitize_import";
+    (void)std::system(("mkdir -p '" + dir + "'").c_str());
     auto write = [&](const std::string& name, const std::string& text) { std::ofstream f(dir + "/" + name, std::ios::binary); f << text; };
     const std::string cam = "#camera 0 0 4 0 0 -1 0 1 0\n";
     const char* cases[] = {

@@ -39,7 +39,7 @@ def _reference_image(amber, width, spp, seed=12345):
 
 def test_plain_gpus_flag_starts_its_own_ranks(amber, tmp_path):
     """`python bench.py --gpus 3 --rehearse-on-one-gpu` with no launcher around it: one JSON line, n_gpus 3, exact image."""
-    line, img = _bench(tmp_path, "--gpus", "3", "--rehearse-on-one-gpu", "--width", "256", "--spp", "64")
+    line, img = _bench(tmp_path, "--gpus", "3", "--rehearse-on-one-gpu", "--width", "256", "--spp", "64", "--full")   # --full: the oracle's check below
     assert line["n_gpus"] == 3 and line["ranks"] == 3 and line["config"]["parallelism"] == "stripes3x8rows"
     ref, rays = _reference_image(amber, 256, 64)
     assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))
@@ -78,3 +78,18 @@ def test_more_ranks_than_stripes(amber, tmp_path):
     line, img = _bench(tmp_path, "--gpus", "3", "--rehearse-on-one-gpu", "--width", "16", "--spp", "16")
     ref, _ = _reference_image(amber, 16, 16)
     assert line["n_gpus"] == 3 and np.array_equal(img.view(np.uint32), ref.view(np.uint32))
+
+
+def test_dump_outputs_are_the_last_steps_image(amber, tmp_path):
+    """`--dump-outputs DIR`: the image and ray count of the last timed step, the same bits as a plain single-handle render."""
+    e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "0", "--width", "64", "--spp", "16",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=e, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    img, rays = np.load(tmp_path / "out" / "image.npy"), np.load(tmp_path / "out" / "rays.npy")
+    assert img.dtype == np.float32 and rays.dtype == np.float64 and not (tmp_path / "out" / "image_rows.npy").exists()
+    ref, ref_rays = _reference_image(amber, 64, 16)
+    assert np.array_equal(img.view(np.uint32), ref.reshape(img.shape).view(np.uint32))
+    assert rays.tolist() == [ref_rays] and line["config"]["rays_per_step"] == ref_rays
