@@ -2,6 +2,13 @@
 // Part of the one translation unit pt_host.hip (kernels are launched from there); see its header comment.
 
 namespace {
+// The known-answer kernels' engines: those of the render kernels but REFERENCE_BVH, which the kat_* entry points refuse first
+constexpr const char* kKatNoRefBvh = "the known-answer kernels have no instantiation for AMBER_ENGINE_REFERENCE_BVH (its traversal stack belongs to the render kernels' grid): compare amber_hip_pt_signatures instead";
+template <typename F>
+void WithKatEngine(const amber_hip_pt* h, F&& f) {
+  WithHitEngine(h->hit_engine, [&](auto engine) -> int { if constexpr (decltype(engine)::value != ENGINE_REF_BVH) f(engine); return AMBER_OK; });
+}
+
 // Engine WAVEFRONT host loop: batches of <= max_chunks accumulation chunks; per batch generate, then bounce launches
 // until the live-ray count read back from the device is zero, then the ordered reduction into the framebuffer.
 int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
@@ -21,13 +28,7 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
     const size_t q_len = shard_capacity * AMBER_WF_SHARDS;
     const size_t n_counts = static_cast<size_t>(kMaxBounces + 2) * AMBER_WF_SHARDS;
     const size_t bytes = (26 * q_len + 3 * n_paths) * 4 + n_counts * sizeof(unsigned int);
-    if (bytes > h->wf_bytes) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      if (h->d_wf) { HIP_TRY(hipFree(h->d_wf)); h->d_wf = nullptr; h->wf_bytes = 0; }
-      hipError_t e = hipMalloc(&h->d_wf, bytes);
-      if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string("hipMalloc(wavefront queues): ") + hipGetErrorString(e));
-      h->wf_bytes = bytes;
-    }
+    { const int rc = Grow(h, h->d_wf, bytes / sizeof(float), "wavefront queues"); if (rc != AMBER_OK) return rc; }
     float* base = h->d_wf;
     WfQueue q[2];
     for (int k = 0; k < 2; k++) {
@@ -42,10 +43,10 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
     a.row_begin = h->row_begin; a.stripe_rows = h->stripe_rows; a.stripe_period = h->stripe_period; a.n_pixels = n_pixels;
     a.first_sample = first_sample + done; a.n_samples = n; a.n_paths = static_cast<uint32_t>(n_paths); a.bounce = 0; a.shard_capacity = static_cast<uint32_t>(shard_capacity);
     const uint32_t n_blocks = 2048u;                          // 8192 waves = 32 per shard
-    std::pair<hipEvent_t, hipEvent_t>* evp = nullptr;
+    std::pair<Event, Event>* evp = nullptr;
     { const int rc = AcquireEventPair(h, &evp); if (rc != AMBER_OK) return rc; }
     auto& ev = *evp;
-    HIP_TRY(hipEventRecord(ev.first, h->stream));
+    HIP_TRY(hipEventRecord(ev.first.v, h->stream));
     a.out = q[0]; a.in = q[1];
     hipLaunchKernelGGL(wf_generate_kernel, dim3(n_blocks), dim3(256), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
@@ -54,9 +55,11 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
       const uint32_t burst = bounce < 16 ? 8 : 16;            // launches enqueued before the live count is read back
       for (uint32_t k = 0; k < burst && bounce < kMaxBounces; k++, bounce++) {
         a.bounce = bounce; a.in = q[bounce & 1]; a.out = q[(bounce + 1) & 1];
-        if (h->hit_engine == AMBER_ENGINE_TWO_PHASE) hipLaunchKernelGGL(wf_bounce_kernel<ENGINE_TWO_PHASE>, dim3(n_blocks), dim3(256), 0, h->stream, a);
-        else if (h->hit_engine == AMBER_ENGINE_BVH) hipLaunchKernelGGL(wf_bounce_kernel<ENGINE_BVH>, dim3(n_blocks), dim3(256), 0, h->stream, a);
-        else hipLaunchKernelGGL(wf_bounce_kernel<ENGINE_LIST>, dim3(n_blocks), dim3(256), 0, h->stream, a);
+        WithHitEngine(h->hit_engine, [&](auto engine) -> int {          // instantiated for TWO_PHASE and BVH (the engines WAVEFRONT resolves to), else LIST
+          constexpr int kEngine = decltype(engine)::value == ENGINE_TWO_PHASE || decltype(engine)::value == ENGINE_BVH ? decltype(engine)::value : ENGINE_LIST;
+          hipLaunchKernelGGL(wf_bounce_kernel<kEngine>, dim3(n_blocks), dim3(256), 0, h->stream, a);
+          return AMBER_OK;
+        });
         HIP_TRY(hipGetLastError());
       }
       unsigned int shard_live[AMBER_WF_SHARDS];
@@ -67,7 +70,7 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
       if (live == 0) break;
       if (bounce >= kMaxBounces) return Fail(AMBER_EHIP, "wavefront engine: path longer than 4096 bounces");
     }
-    HIP_TRY(hipEventRecord(ev.second, h->stream));
+    HIP_TRY(hipEventRecord(ev.second.v, h->stream));
     const uint32_t n_elems = n_pixels * 3u;
     hipLaunchKernelGGL(wf_reduce_kernel, dim3((n_elems + 255u) / 256u), dim3(256), 0, h->stream, h->d_fb, meas, n_pixels, n_chunks);
     HIP_TRY(hipGetLastError());
@@ -83,7 +86,7 @@ extern "C" {
 // ---- KAT entry points -----------------------------------------------------------------------------
 int amber_hip_kat_cast(amber_hip_pt* h, uint32_t n, const float* origins, const float* dirs,
                        int32_t* out_object, float* out_t, float* out_pos, float* out_normal) {
-  if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, "the known-answer kernels have no instantiation for AMBER_ENGINE_REFERENCE_BVH (its traversal stack belongs to the render kernels' grid): compare amber_hip_pt_signatures instead");
+  if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);
   if (!h || !origins || !dirs || !out_object || !out_t || !out_pos || !out_normal) return Fail(AMBER_EINVAL, "null argument");
   if (n == 0) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
@@ -91,10 +94,7 @@ int amber_hip_kat_cast(amber_hip_pt* h, uint32_t n, const float* origins, const 
   HIP_TRY(d_o.alloc(3 * n)); HIP_TRY(d_d.alloc(3 * n)); HIP_TRY(d_t.alloc(n)); HIP_TRY(d_p.alloc(3 * n)); HIP_TRY(d_n.alloc(3 * n)); HIP_TRY(d_i.alloc(n));
   HIP_TRY(hipMemcpy(d_o.p, origins, 3ull * n * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_d.p, dirs, 3ull * n * 4, hipMemcpyHostToDevice));
-  if (h->hit_engine == AMBER_ENGINE_TWO_PHASE) hipLaunchKernelGGL(kat_cast_kernel<ENGINE_TWO_PHASE>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_o.p, d_d.p, d_i.p, d_t.p, d_p.p, d_n.p);
-  else if (h->hit_engine == kHitTwoPhaseN) hipLaunchKernelGGL(kat_cast_kernel<ENGINE_TWO_PHASE_N>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_o.p, d_d.p, d_i.p, d_t.p, d_p.p, d_n.p);
-  else if (h->hit_engine == AMBER_ENGINE_BVH) hipLaunchKernelGGL(kat_cast_kernel<ENGINE_BVH>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_o.p, d_d.p, d_i.p, d_t.p, d_p.p, d_n.p);
-  else hipLaunchKernelGGL(kat_cast_kernel<ENGINE_LIST>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_o.p, d_d.p, d_i.p, d_t.p, d_p.p, d_n.p);
+  WithKatEngine(h, [&](auto engine) { hipLaunchKernelGGL(kat_cast_kernel<decltype(engine)::value>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_o.p, d_d.p, d_i.p, d_t.p, d_p.p, d_n.p); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out_object, d_i.p, 4ull * n, hipMemcpyDeviceToHost));
@@ -145,7 +145,7 @@ int amber_hip_kat_eye(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const 
 
 int amber_hip_kat_trace(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const uint32_t* sample,
                         uint32_t max_bounces, uint32_t* out_records, uint32_t* out_casts) {
-  if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, "the known-answer kernels have no instantiation for AMBER_ENGINE_REFERENCE_BVH (its traversal stack belongs to the render kernels' grid): compare amber_hip_pt_signatures instead");
+  if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);
   if (!h || !pixel || !sample || !out_records || !out_casts || max_bounces == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (n == 0) return AMBER_OK;
   const uint32_t npx = h->scene.sensor.w * h->scene.sensor.h;
@@ -157,10 +157,7 @@ int amber_hip_kat_trace(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, cons
   HIP_TRY(hipMemcpy(d_p.p, pixel, 4ull * n, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_s.p, sample, 4ull * n, hipMemcpyHostToDevice));
   HIP_TRY(hipMemsetAsync(d_r.p, 0, nrec * 4, h->stream));
-  if (h->hit_engine == AMBER_ENGINE_TWO_PHASE) hipLaunchKernelGGL(kat_trace_kernel<ENGINE_TWO_PHASE>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, d_p.p, d_s.p, max_bounces, d_r.p, d_c.p);
-  else if (h->hit_engine == kHitTwoPhaseN) hipLaunchKernelGGL(kat_trace_kernel<ENGINE_TWO_PHASE_N>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, d_p.p, d_s.p, max_bounces, d_r.p, d_c.p);
-  else if (h->hit_engine == AMBER_ENGINE_BVH) hipLaunchKernelGGL(kat_trace_kernel<ENGINE_BVH>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, d_p.p, d_s.p, max_bounces, d_r.p, d_c.p);
-  else hipLaunchKernelGGL(kat_trace_kernel<ENGINE_LIST>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, d_p.p, d_s.p, max_bounces, d_r.p, d_c.p);
+  WithKatEngine(h, [&](auto engine) { hipLaunchKernelGGL(kat_trace_kernel<decltype(engine)::value>, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, d_p.p, d_s.p, max_bounces, d_r.p, d_c.p); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out_records, d_r.p, nrec * 4, hipMemcpyDeviceToHost));
@@ -169,7 +166,7 @@ int amber_hip_kat_trace(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, cons
 }
 
 int amber_hip_kat_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint64_t* out) {
-  if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, "the known-answer kernels have no instantiation for AMBER_ENGINE_REFERENCE_BVH (its traversal stack belongs to the render kernels' grid): compare amber_hip_pt_signatures instead");
+  if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);
   if (!h || !out || n_samples == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
   const uint64_t n = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w * n_samples;
@@ -179,10 +176,7 @@ int amber_hip_kat_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   DevBuf<unsigned long long> d_out;
   HIP_TRY(d_out.alloc(n));
   const dim3 grid(static_cast<uint32_t>((n + 255) / 256));
-  if (h->hit_engine == AMBER_ENGINE_TWO_PHASE) hipLaunchKernelGGL(kat_signature_kernel<ENGINE_TWO_PHASE>, grid, dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, first_sample, n_samples, h->row_begin, h->stripe_rows, h->stripe_period, d_out.p);
-  else if (h->hit_engine == kHitTwoPhaseN) hipLaunchKernelGGL(kat_signature_kernel<ENGINE_TWO_PHASE_N>, grid, dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, first_sample, n_samples, h->row_begin, h->stripe_rows, h->stripe_period, d_out.p);
-  else if (h->hit_engine == AMBER_ENGINE_BVH) hipLaunchKernelGGL(kat_signature_kernel<ENGINE_BVH>, grid, dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, first_sample, n_samples, h->row_begin, h->stripe_rows, h->stripe_period, d_out.p);
-  else hipLaunchKernelGGL(kat_signature_kernel<ENGINE_LIST>, grid, dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, first_sample, n_samples, h->row_begin, h->stripe_rows, h->stripe_period, d_out.p);
+  WithKatEngine(h, [&](auto engine) { hipLaunchKernelGGL(kat_signature_kernel<decltype(engine)::value>, grid, dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, first_sample, n_samples, h->row_begin, h->stripe_rows, h->stripe_period, d_out.p); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -213,9 +207,9 @@ int amber_hip_kat_traversal_rate(amber_hip_pt* h, uint32_t n, const float* origi
   const uint32_t n_blocks = static_cast<uint32_t>(h->n_cus) * (waves >= 4 && waves <= 8 ? waves : 5u);
   HIP_TRY(d_stack.alloc(static_cast<size_t>(n_blocks) * 256u * AMBER_BVH_STACK));
   HIP_TRY(hipMemcpy(d_rays.p, packed.data(), packed.size() * sizeof(float4), hipMemcpyHostToDevice));
-  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evs;   // released on every exit path
-  HIP_TRY(hipEventCreate(&evs.a)); HIP_TRY(hipEventCreate(&evs.b));
-  const hipEvent_t e0 = evs.a, e1 = evs.b;
+  Event ev0, ev1;                                                        // released on every exit path
+  HIP_TRY(hipEventCreate(&ev0.v)); HIP_TRY(hipEventCreate(&ev1.v));
+  const hipEvent_t e0 = ev0.v, e1 = ev1.v;
   double best = 1e300;
   const uint32_t nv = static_cast<uint32_t>(n_virtual);
   for (uint32_t rep = 0; rep < 2u; rep++) {                              // a warm-up launch and the measured one
@@ -237,7 +231,7 @@ int amber_hip_kat_traversal_rate(amber_hip_pt* h, uint32_t n, const float* origi
   HIP_TRY(hipMemcpy(res.data(), d_out.p, n * sizeof(float2), hipMemcpyDeviceToHost));
   if (out_rounds) HIP_TRY(hipMemcpy(out_rounds, d_rounds.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   std::vector<uint32_t> prims(h->scene.n_objects);
-  HIP_TRY(hipMemcpy(prims.data(), h->d_bvh_prims, prims.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(prims.data(), h->scene.bvh_prims, prims.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   for (uint32_t i = 0; i < n; i++) {
     int32_t slot; std::memcpy(&slot, &res[i].y, 4);
     out_object[i] = slot < 0 ? -1 : static_cast<int32_t>(prims[slot]);
@@ -281,12 +275,7 @@ int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_s
   HIP_TRY(hipSetDevice(h->device));
   { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if (n > h->sig_paths) {
-    if (h->d_sig) { HIP_TRY(hipFree(h->d_sig)); h->d_sig = nullptr; h->sig_paths = 0; }
-    hipError_t e = hipMalloc(&h->d_sig, n * sizeof(unsigned long long));
-    if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string("hipMalloc(signatures): ") + hipGetErrorString(e));
-    h->sig_paths = n;
-  }
+  { const int rc = Grow(h, h->d_sig, n, "signatures"); if (rc != AMBER_OK) return rc; }
   HIP_TRY(hipMemsetAsync(h->d_sig, 0, n * sizeof(unsigned long long), h->stream));
   if (bvh_items) {
     const int rc = RenderPassBvhItems(h, first_sample, n_samples, n_pixels, h->d_sig); if (rc != AMBER_OK) return rc;

@@ -1,6 +1,7 @@
 // host_sanitize.hip -- host-only driver built with AddressSanitizer + UBSan (tests/test_host_sanitizers.py):
-// exercises the host code that prepares device data -- object model, Flatten, filter program, BVH build, output
-// writers -- on degenerate and large inputs.  No GPU call is made (GPU sanitizers are not available on this pool).
+// exercises the host code that prepares device data -- object model, Flatten, the product's own scene preparation
+// (scene_prep.h: engine choice, device records, filter programs and their groups, BVH builds, light slots, lens
+// constants), output writers -- on degenerate and large inputs.  No GPU call is made (GPU sanitizers are not available on this pool).
 #include <cstdio>
 #include <random>
 #include <vector>
@@ -11,25 +12,98 @@
 #include "../amber_amd/csrc/amber/postprocess.h"
 #include "../amber_amd/csrc/amber/rendering.h"
 #include "../amber_amd/csrc/amber/scene.h"
-#include "../amber_amd/csrc/hip/bvh_build.h"
-#include "../amber_amd/csrc/hip/filter_build.h"
-#include "../amber_amd/csrc/hip/ref_bvh_build.h"
+#include "../amber_amd/csrc/hip/scene_prep.h"
 
 using amber_dev::DevObject;
+using amber_prep::PreparedScene;
 
-static std::vector<DevObject> ToDev(const amber::scene::FlatScene& fs) {
-  std::vector<DevObject> objs(fs.objects.size());
-  for (size_t i = 0; i < objs.size(); i++) {
-    const AmberFlatObject& f = fs.objects[i];
-    DevObject& o = objs[i];
-    std::memset(&o, 0, sizeof o);
-    o.kind = f.kind; o.material = f.material;
-    for (int c = 0; c < 3; c++) o.a[c] = f.p[c];
-    if (f.kind == AMBER_PRIM_TRIANGLE) for (int c = 0; c < 3; c++) { o.e1[c] = f.p[3 + c] - f.p[c]; o.e2[c] = f.p[6 + c] - f.p[c]; o.n[c] = f.p[9 + c]; }
-    else if (f.kind == AMBER_PRIM_SPHERE) o.radius = f.p[3];
-    else { for (int c = 0; c < 3; c++) o.e1[c] = f.p[3 + c]; o.radius = f.p[6]; o.height = f.p[7]; }
+static void Require(bool ok, const char* what, const char* check) {
+  if (!ok) { std::printf("FAIL %s: %s\n", what, check); std::exit(1); }
+}
+
+// what amber_hip_pt_create prepares for this scene and engine (default switches), before it touches the device
+static PreparedScene Prepare(const AmberFlatScene& s, uint32_t engine) {
+  const AmberSensor sensor{64, 48, 0.036f, 0.024f};
+  AmberPtParams params{};
+  params.engine = engine;
+  return amber_prep::PrepareScene(&s, &sensor, &params, amber_prep::EnvSwitches(), 12, 52);   // the kernels' AMBER_PATH_BVH_STACK, AMBER_BVH_SHADE_BATCH
+}
+
+// The prepared scene is consistent: the engine resolved as expected, every object once in the filter programs' LDS image (scene index
+// in kind >> 8) and in engine BVH's leaf order, group ranges inside the merged records, every blade's and light's slot naming that
+// object, finite lens constants.
+static void CheckPrepared(const AmberFlatScene& s, const PreparedScene& p, uint32_t hit_engine, const char* what) {
+  const uint32_t n = s.n_objects;
+  Require(p.error.empty() && p.hit_engine == hit_engine, what, "engine resolution");
+  Require(p.objects.size() == n && p.materials.size() == s.n_materials && p.blades.size() == s.lens.n_blades && p.lights.size() == s.n_lights, what, "record counts");
+  Require(p.scene.n_objects == n && p.scene.n_lights == s.n_lights && p.scene.n_lds_objects == p.prog_objects.size(), what, "scene scalars");
+  const std::vector<DevObject>& prog = p.prog_objects;
+  if (p.two_phase) {
+    std::vector<int> seen(n, 0);
+    auto see = [&](const DevObject& o) { Require((o.kind >> 8) < n, what, "LDS image: scene index"); seen[o.kind >> 8]++; };
+    if (p.groups.empty()) for (const DevObject& o : prog) see(o);
+    for (size_t g = 0; g < p.groups.size(); g++) {
+      const amber_dev::DevFilterGroup& gr = p.groups[g];
+      Require(gr.n_objects <= 32 && gr.plane_first + gr.n_planes <= p.planes.size() && gr.tri_first <= p.tri_filters.size() &&
+              gr.sphere_first + gr.n_sphere_filters <= p.sphere_filters.size(), what, "group ranges");
+      for (uint32_t k = 0; k < gr.n_objects; k++) see(prog[32 * g + k]);
+    }
+    for (int c : seen) Require(c == 1, what, "LDS image: every object once");
+    Require(p.groups.empty() == (hit_engine != amber_prep::kHitTwoPhaseN) && p.scene.n_groups == std::max<size_t>(1, p.groups.size()), what, "groups");
   }
-  return objs;
+  for (uint32_t i = 0; i < s.lens.n_blades; i++)
+    Require(p.blades[i].slot < 0 || (size_t(p.blades[i].slot) < prog.size() && (prog[p.blades[i].slot].kind >> 8) == s.lens.first_blade_object + i), what, "blade slot");
+  for (uint32_t i = 0; i < s.n_lights; i++)
+    Require(p.lights[i].slot < 0 || (size_t(p.lights[i].slot) < prog.size() && (prog[p.lights[i].slot].kind >> 8) == s.lights[i].object), what, "light slot");
+  if (hit_engine == AMBER_ENGINE_BVH || hit_engine == AMBER_ENGINE_REFERENCE_BVH) {
+    Require(p.bvh_prims.size() == n && p.bvh_objects.size() == n && p.bvh_spheres.size() == n && (p.bvh_tris.empty() || p.bvh_tris.size() == 3 * n), what, "leaf-order arrays");
+    std::vector<int> seen(n, 0);
+    for (uint32_t k = 0; k < n; k++) {
+      Require(p.bvh_prims[k] < n && std::memcmp(&p.bvh_objects[k], &p.objects[p.bvh_prims[k]], sizeof(DevObject)) == 0, what, "leaf-order records");
+      seen[p.bvh_prims[k]]++;
+    }
+    for (int c : seen) Require(c == 1, what, "leaf order: every object once");
+  }
+  if (hit_engine == AMBER_ENGINE_REFERENCE_BVH) Require(p.ref_leaves.size() == p.ref_nodes.size() + 1, what, "reference tree");
+  const amber_dev::DevLens& L = p.lens;
+  bool finite = std::isfinite(L.size_over_area) && std::isfinite(L.inv_scene_area) && std::isfinite(L.sd2) && L.edge_tol > 0 && L.edge_tol <= 1;
+  for (const auto& corner : p.aperture_rect) for (float v : corner) finite = finite && std::isfinite(v);
+  Require(finite, what, "lens constants");
+  std::printf("ok   prepare %-34s objects %6u: hit engine %u, %zu group(s), %zu planes, %zu lights%s\n", what, n, p.hit_engine, std::max<size_t>(1, p.groups.size()),
+              p.planes.size(), p.lights.size(), hit_engine == AMBER_ENGINE_BVH ? (p.bvh_paths ? ", path kernel" : ", item kernel") : "");
+}
+
+// A flat scene that owns its arrays: one of the driver's scenes grown to n_objects by small spheres and triangles, with extra_lights more
+// lights on the last triangles (in the grouped engine: the last groups)
+struct GrownScene {
+  std::vector<AmberFlatObject> objects;
+  std::vector<AmberFlatLight> lights;
+  AmberFlatScene flat{};
+};
+static GrownScene Grow(const AmberFlatScene& base, uint32_t n_objects, uint32_t extra_lights, unsigned seed) {
+  GrownScene g;
+  g.objects.assign(base.objects, base.objects + base.n_objects);
+  if (base.n_lights) g.lights.assign(base.lights, base.lights + base.n_lights);
+  std::mt19937 rng(seed); std::uniform_real_distribution<float> u(-1.f, 1.f);
+  while (g.objects.size() < n_objects) {
+    AmberFlatObject o{};
+    o.material = static_cast<uint32_t>(g.objects.size() % base.n_materials);
+    o.kind = g.objects.size() % 3 == 0 ? AMBER_PRIM_SPHERE : AMBER_PRIM_TRIANGLE;
+    for (int c = 0; c < 3; c++) o.p[c] = u(rng);
+    if (o.kind == AMBER_PRIM_SPHERE) o.p[3] = 0.02f;
+    else for (int c = 0; c < 3; c++) { o.p[3 + c] = o.p[c] + 0.05f * u(rng); o.p[6 + c] = o.p[c] + 0.05f * u(rng); o.p[9 + c] = c == 2; }   // (the normal is only copied)
+    g.objects.push_back(o);
+  }
+  for (uint32_t k = 0, i = n_objects; k < extra_lights && i-- > base.n_objects;) {
+    if (g.objects[i].kind != AMBER_PRIM_TRIANGLE) continue;
+    AmberFlatLight l{};
+    l.object = i; l.cum_power = (g.lights.empty() ? 0.f : g.lights.back().cum_power) + 1.f; l.pdf_area = 1.f; l.irradiance[0] = l.irradiance[1] = l.irradiance[2] = 1.f;
+    g.lights.push_back(l); k++;
+  }
+  g.flat = base;
+  g.flat.objects = g.objects.data(); g.flat.n_objects = static_cast<uint32_t>(g.objects.size());
+  g.flat.lights = g.lights.empty() ? nullptr : g.lights.data(); g.flat.n_lights = static_cast<uint32_t>(g.lights.size());
+  return g;
 }
 
 static void CheckBvh(const std::vector<DevObject>& objs, const char* what) {
@@ -79,11 +153,17 @@ static void CheckReferenceBvh(const std::vector<AmberFlatObject>& flat, const ch
 int main(int argc, char** argv) {
   using namespace amber;
   const std::string out = argc > 1 ? argv[1] : ".";                              // where the writers and the import cases put their files
-  // 1. Cornell box: flatten + filter program
+  (void)amber_prep::ReadEnv();
+  // 1. Cornell box: flatten + the product's preparation for every engine, filter program
+  const auto cornell = etude::CornelBox(0.050f, 0.050f, 6).Flatten();
   {
-    const auto scene = etude::CornelBox(0.050f, 0.050f, 6);
-    const auto fs = scene.Flatten();
-    const auto objs = ToDev(fs);
+    const auto& fs = cornell;
+    const PreparedScene prep = Prepare(fs.flat, AMBER_ENGINE_AUTO);
+    CheckPrepared(fs.flat, prep, AMBER_ENGINE_TWO_PHASE, "cornell (auto)");
+    CheckPrepared(fs.flat, Prepare(fs.flat, AMBER_ENGINE_LIST), AMBER_ENGINE_LIST, "cornell (list)");
+    CheckPrepared(fs.flat, Prepare(fs.flat, AMBER_ENGINE_BVH), AMBER_ENGINE_BVH, "cornell (bvh)");
+    CheckPrepared(fs.flat, Prepare(fs.flat, AMBER_ENGINE_REFERENCE_BVH), AMBER_ENGINE_REFERENCE_BVH, "cornell (reference bvh)");
+    const std::vector<DevObject>& objs = prep.objects;
     amber_filter::FilterProgram fp;
     { const float zero_center[3] = {0, 0, 0}; amber_filter::BuildFilterProgram(objs, zero_center, fp); }
     uint32_t pairs = 0, singles = 0;
@@ -109,6 +189,18 @@ int main(int argc, char** argv) {
     std::printf("ok   filter program: 9 planes (4 slabs first), 22 triangles in 11 pair records, 3 spheres\n");
     CheckBvh(objs, "cornell");
     CheckReferenceBvh(fs.objects, "cornell");
+    // AUTO's three ranges (<= 32 objects above, 33-80, 81-128), TWO_PHASE asked for up to 128 objects, lights in the last groups
+    for (uint32_t n : {33u, 64u, 80u}) {
+      const GrownScene g = Grow(fs.flat, n, 3, n);
+      CheckPrepared(g.flat, Prepare(g.flat, AMBER_ENGINE_AUTO), amber_prep::kHitTwoPhaseN, ("cornell + small objects, auto, " + std::to_string(n)).c_str());
+    }
+    for (uint32_t n : {81u, 128u}) {
+      const GrownScene g = Grow(fs.flat, n, 3, n);
+      CheckPrepared(g.flat, Prepare(g.flat, AMBER_ENGINE_AUTO), AMBER_ENGINE_BVH, ("cornell + small objects, auto, " + std::to_string(n)).c_str());
+      CheckPrepared(g.flat, Prepare(g.flat, AMBER_ENGINE_TWO_PHASE), amber_prep::kHitTwoPhaseN, ("cornell + small objects, two_phase, " + std::to_string(n)).c_str());
+    }
+    const GrownScene g = Grow(fs.flat, 1000, 8, 1000);
+    CheckPrepared(g.flat, Prepare(g.flat, AMBER_ENGINE_REFERENCE_BVH), AMBER_ENGINE_REFERENCE_BVH, "cornell + small objects, ref bvh, 1000");
   }
   // 2. degenerate inputs: pinhole (zero-area triangle), one object, coincident centres, extreme coordinates
   {
@@ -122,7 +214,11 @@ int main(int argc, char** argv) {
     objects.emplace_back(prims.back().get(), mats.back().get());
     const auto sc = scene::RGBScene::Create<raytracer::List<float, scene::RGBObject>>(std::move(prims), std::move(mats), std::move(objects), std::move(lens));
     const auto fs = sc.Flatten();
-    const auto objs = ToDev(fs);
+    const PreparedScene prep = Prepare(fs.flat, AMBER_ENGINE_AUTO);
+    CheckPrepared(fs.flat, prep, AMBER_ENGINE_TWO_PHASE, "pinhole+disk+cylinder (auto)");
+    CheckPrepared(fs.flat, Prepare(fs.flat, AMBER_ENGINE_BVH), AMBER_ENGINE_BVH, "pinhole+disk+cylinder (bvh)");
+    CheckPrepared(fs.flat, Prepare(fs.flat, AMBER_ENGINE_REFERENCE_BVH), AMBER_ENGINE_REFERENCE_BVH, "pinhole+disk+cylinder (ref bvh)");
+    const std::vector<DevObject>& objs = prep.objects;
     amber_filter::FilterProgram fp;
     { const float zero_center[3] = {0, 0, 0}; amber_filter::BuildFilterProgram(objs, zero_center, fp); }
     if (fp.always_mask != 0x7u || !fp.planes.empty()) { std::printf("FAIL degenerate filter program always=%x\n", fp.always_mask); return 1; }
@@ -139,12 +235,15 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < far.size(); i++) { far[i].a[0] = (i % 2 ? 1e30f : -1e30f); far[i].a[1] = static_cast<float>(i); far[i].radius = 1e-30f; }
     CheckBvh(far, "extreme coordinates");
   }
-  // 3. large random cloud
+  // 3. large random cloud: 200k spheres in the Cornell box's lens and lights, through the product's preparation (engine BVH)
   {
     std::mt19937 rng(3); std::uniform_real_distribution<float> u(-1.f, 1.f);
-    std::vector<DevObject> objs(200000);
-    for (auto& o : objs) { std::memset(&o, 0, sizeof o); o.kind = 1; o.a[0] = u(rng); o.a[1] = u(rng); o.a[2] = u(rng); o.radius = 0.004f; }
-    CheckBvh(objs, "200k random spheres");
+    GrownScene cloud = Grow(cornell.flat, 0, 0, 0);
+    for (int i = 0; i < 200000; i++) { AmberFlatObject o{}; o.kind = AMBER_PRIM_SPHERE; o.p[0] = u(rng); o.p[1] = u(rng); o.p[2] = u(rng); o.p[3] = 0.004f; cloud.objects.push_back(o); }
+    cloud.flat.objects = cloud.objects.data(); cloud.flat.n_objects = static_cast<uint32_t>(cloud.objects.size());
+    const PreparedScene prep = Prepare(cloud.flat, AMBER_ENGINE_AUTO);
+    CheckPrepared(cloud.flat, prep, AMBER_ENGINE_BVH, "cornell + 200k random spheres (auto)");
+    CheckBvh(prep.objects, "200k random spheres");
     // the reference's tree of degenerate inputs: one object, a thousand coincident spheres (no plane separates them: one leaf), coordinates at the
     // edge of binary32 (surface areas overflow to inf, costs to NaN: a leaf), NaN centres (refused: std::sort on them is undefined), and 200k random spheres
     auto flat_sphere = [](float x, float y, float z, float r) { AmberFlatObject o{}; o.kind = AMBER_PRIM_SPHERE; o.p[0] = x; o.p[1] = y; o.p[2] = z; o.p[3] = r; return o; };

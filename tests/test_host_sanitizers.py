@@ -1,5 +1,6 @@
 """AddressSanitizer + UBSan over the HOST code that prepares device data (GPU sanitizers are not available on
-this pool): object model, Flatten, filter program, BVH build on degenerate and large inputs, PNG/EXR writers."""
+this pool): object model, Flatten, the engine's own scene preparation (scene_prep.h: filter programs, BVH builds,
+light slots, lens constants) on degenerate and large inputs, PNG/EXR writers."""
 import shutil
 import subprocess
 from pathlib import Path
