@@ -16,6 +16,14 @@ from .api import (  # noqa: F401
     ENGINE_WAVEFRONT,
     PT_FLAG_BVH_ITEMS,
     PT_FLAG_BVH_POOL,
+    PT_FLAG_DEVICE_BUILD,
+    BUILD_NONE,
+    BUILD_HOST,
+    BUILD_DEVICE,
+    BUILD_HOST_FALLBACK,
+    BUILD_REASON_DEPTH,
+    BUILD_REASON_WIDE,
+    BUILD_REASON_BOUNDS,
     AmberError,
     FlatMaterial,
     FlatObject,

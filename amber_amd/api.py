@@ -65,6 +65,17 @@ class PtParams(C.Structure):
                 ("stripe_period", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class BuildInfo(C.Structure):
+    """AmberBuildInfo: engine BVH's tree as create built it (amber_hip_pt_build_info)."""
+    _fields_ = [("where", C.c_uint32), ("fallback_reason", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("depth", C.c_uint32),
+                ("pad", C.c_uint32), ("tree_ms", C.c_double), ("create_ms", C.c_double)]
+
+
+class BvhDumpInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_prims", C.c_uint32), ("root", C.c_int32), ("depth", C.c_uint32),
+                ("gmin", C.c_float * 3), ("step", C.c_float * 3), ("reach", C.c_float * 3)]
+
+
 class HostStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("passes", C.c_uint64), ("launches", C.c_uint32), ("pad", C.c_uint32), ("kernel_ms", C.c_double)]
 
@@ -74,11 +85,14 @@ MAT_LAMBERTIAN, MAT_PHONG, MAT_SPECULAR, MAT_REFRACTION, MAT_DIFFUSE_LIGHT, MAT_
 ENGINE_AUTO, ENGINE_LIST, ENGINE_TWO_PHASE, ENGINE_BVH, ENGINE_WAVEFRONT = 0, 1, 2, 3, 4
 ENGINE_REFERENCE_BVH = 6     # the reference's own tree and traversal order: every ray gets the hit the reference's BVH gives it (include/amber_hip.h)
 PT_FLAG_NULL_STREAM, PT_FLAG_BVH_POOL, PT_FLAG_BVH_ITEMS = 1, 2, 4
+PT_FLAG_DEVICE_BUILD = 8     # engine BVH: create builds the tree on the device (include/amber_hip.h)
+BUILD_NONE, BUILD_HOST, BUILD_DEVICE, BUILD_HOST_FALLBACK = 0, 1, 2, 3
+BUILD_REASON_NONE, BUILD_REASON_DEPTH, BUILD_REASON_WIDE, BUILD_REASON_BOUNDS = 0, 1, 2, 3
 
 # every symbol include/amber_hip.h and include/amber_host.h declare: what libamber_hip.so (the product) exports
 ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
-    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_destroy",
+    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_destroy",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -86,7 +100,7 @@ ABI_SYMBOLS = [
 # what include/amber_hip_lab.h declares: libamber_hip_lab.so (the same sources with -DAMBER_LAB) exports these as well
 LAB_SYMBOLS = [
     "amber_hip_kat_cast", "amber_hip_kat_sample", "amber_hip_kat_eye", "amber_hip_kat_trace", "amber_hip_kat_math", "amber_hip_kat_signatures", "amber_hip_pt_signatures",
-    "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks",
+    "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -133,6 +147,8 @@ def load_library() -> C.CDLL:
     lib.amber_hip_pt_kernel_time.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_double)]
     lib.amber_hip_pt_destroy.argtypes = [vp]
     lib.amber_hip_pt_destroy.restype = None
+    if hasattr(lib, "amber_hip_pt_build_info"):    # absent only in older builds loaded by tools/ab_lib.py
+        lib.amber_hip_pt_build_info.argtypes = [vp, C.POINTER(BuildInfo)]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -147,6 +163,7 @@ def load_library() -> C.CDLL:
         lib.amber_hip_kat_pixel_masks.argtypes = [vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         lib.amber_hip_kat_traversal_rate.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, vp, C.POINTER(C.c_double), vp]
         lib.amber_hip_pt_signatures.argtypes = [vp, u32, u32, vp]
+        lib.amber_hip_kat_bvh_dump.argtypes = [vp, vp, u32, vp, u32, C.POINTER(BvhDumpInfo)]
     lib.amber_host_cornell_box.restype = vp
     lib.amber_host_cornell_box.argtypes = [C.c_float, C.c_float, u32]
     lib.amber_host_scene_import.restype = vp
@@ -276,7 +293,8 @@ class PathTracer:
     def __init__(self, scene: HostScene, sensor: Sensor, seed: int = 12345, max_depth: int = 0, device: int = 0,
                  rows=None, stream: int | None = None, engine: int = ENGINE_AUTO, stripe=None, flags: int = 0):
         """rows = (y0, y1) contiguous band; stripe = (S, period) keeps only rows with (y - y0) % period < S;
-        flags = AMBER_PT_FLAG_* bits (PT_FLAG_BVH_POOL: engine BVH with the per-wave ray pool scheduler)."""
+        flags = AMBER_PT_FLAG_* bits (PT_FLAG_BVH_POOL: engine BVH with the per-wave ray pool scheduler; PT_FLAG_DEVICE_BUILD: engine BVH's tree
+        built on the device at create)."""
         self.sensor = sensor
         rb, re = rows if rows is not None else (0, sensor.height)
         s_rows, s_period = stripe if stripe else (0, 0)
@@ -331,6 +349,12 @@ class PathTracer:
         n, ms = C.c_uint32(), C.c_double()
         _check(load_library().amber_hip_pt_kernel_time(self._h, C.byref(n), C.byref(ms)))
         return n.value, ms.value
+
+    def build_info(self) -> dict:
+        """Engine BVH's tree as create built it: where (BUILD_*), fallback_reason (BUILD_REASON_*), n_nodes, n_leaves, depth, tree_ms, create_ms."""
+        b = BuildInfo()
+        _check(load_library().amber_hip_pt_build_info(self._h, C.byref(b)))
+        return {k: getattr(b, k) for k, _ in BuildInfo._fields_ if k != "pad"}
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),
@@ -416,6 +440,17 @@ class PathTracer:
         always = C.c_uint32()
         _check(load_library().amber_hip_kat_pixel_masks(self._h, None, slots.ctypes.data, C.byref(always), None))
         return slots, always.value
+
+    def bvh_dump(self) -> dict:
+        """Engine BVH's tree as the device holds it (lab build): nodes (n, 8) uint32 -- six plane words (min | max << 16: left x y z, right x y z),
+        then the left and right child references (as int32: >= 0 a node, < 0 leaf -(ref + 1) = first * 16 + all_triangles * 8 + all_spheres * 4 + count);
+        prims: leaf slot -> object index; root, depth, gmin, step, reach: plane = gmin + binary16 value * step."""
+        info = BvhDumpInfo()
+        _check(load_library().amber_hip_kat_bvh_dump(self._h, None, 0, None, 0, C.byref(info)))
+        nodes, prims = np.zeros((info.n_nodes, 8), np.uint32), np.zeros(info.n_prims, np.uint32)
+        _check(load_library().amber_hip_kat_bvh_dump(self._h, nodes.ctypes.data, info.n_nodes, prims.ctypes.data, info.n_prims, C.byref(info)))
+        return dict(nodes=nodes, prims=prims, root=int(info.root), depth=int(info.depth), gmin=np.array(info.gmin[:], np.float32),
+                    step=np.array(info.step[:], np.float32), reach=np.array(info.reach[:], np.float32))
 
     def render_signatures(self, first_sample: int, n_samples: int) -> np.ndarray:
         """kat_signatures' layout and meaning, produced by the PRODUCT render kernel (its signature instantiation)."""

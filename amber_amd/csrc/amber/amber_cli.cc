@@ -4,7 +4,7 @@
 // cli::ParseCommandLineOption (option.cc:40-100) as far as they concern the path tracer:
 //   --algorithm pt|lt   --spp N (0 = until --time / SIGINT)   --width --height   --time SECONDS
 //   --output BASENAME (writes BASENAME.png tone-mapped and BASENAME.exr raw)   --threads (accepted, ignored)
-// plus --seed, --device, --max-depth, --engine of this implementation, and --devices N / --device-list a,b,c: N GPUs inside
+// plus --seed, --device, --max-depth, --engine, --device-build of this implementation, and --devices N / --device-list a,b,c: N GPUs inside
 // the one Render() call (rendering.h HipPathTracingOptions.devices), where the reference uses --threads.  The scene is etude::CornelBox(0.050,
 // 0.050, 6) as in application.cc:68-73, or --scene FILE through cli::ImportScene (import.h: OBJ + MTL subset, the
 // reference reads it through assimp) built with the BVH acceleration (application.cc:74-87).
@@ -44,6 +44,7 @@ struct Option {
   int device = 0;
   std::vector<int> devices;          // --devices N = ordinals 0..N-1, --device-list a,b,c = exactly those (repeats allowed)
   std::uint32_t max_depth = 0, engine = 0, samples_per_launch = 0;   // 0 = batches adapt to time (rendering.h)
+  bool device_build = false;         // --device-build: engine BVH's tree built on the device at create (rendering.h)
   bool help = false;
 };
 
@@ -79,6 +80,7 @@ bool Parse(int argc, char** argv, Option& o) {
     }
     else if (a == "--max-depth") o.max_depth = static_cast<std::uint32_t>(std::strtoul(value("--max-depth"), nullptr, 10));
     else if (a == "--engine") o.engine = static_cast<std::uint32_t>(std::strtoul(value("--engine"), nullptr, 10));
+    else if (a == "--device-build") o.device_build = true;
     else if (a == "--samples-per-launch") o.samples_per_launch = static_cast<std::uint32_t>(std::strtoul(value("--samples-per-launch"), nullptr, 10));
     else { std::cerr << "unknown option " << a << std::endl; return false; }
   }
@@ -93,7 +95,8 @@ int main(int argc, char** argv) {
   if (!Parse(argc, argv, option) || option.help) {
     std::cerr << "amber: a global illumination renderer (MI355X path tracer)\n"
                  "  --algorithm pt  --spp N  --width W  --height H  --time S  --output NAME  [--threads N]  [--scene FILE.obj]\n"
-                 "  [--seed N] [--device N | --devices N | --device-list a,b,..] [--max-depth N] [--engine 0..4|6] [--samples-per-launch N]" << std::endl;
+                 "  [--seed N] [--device N | --devices N | --device-list a,b,..] [--max-depth N] [--engine 0..4|6] [--samples-per-launch N]\n"
+                 "  [--device-build]  (scenes past 80 objects: build the BVH on the GPU -- shorter start, slower render, same image)" << std::endl;
     return option.help ? 0 : -1;
   }
   if (option.spp == 0 && option.time == 0) std::cerr << "note: --spp 0 without --time renders until SIGINT" << std::endl;
@@ -101,6 +104,7 @@ int main(int argc, char** argv) {
   rendering::HipPathTracingOptions hip;
   hip.seed = option.seed; hip.device = option.device; hip.max_depth = option.max_depth; hip.engine = option.engine;
   hip.samples_per_launch = option.samples_per_launch;
+  hip.device_build = option.device_build;
   hip.devices = option.devices;                                        // one engine handle per device inside Render()
   std::unique_ptr<rendering::Algorithm<rendering::RGB>> algorithm;
   try {

@@ -404,7 +404,7 @@ const Image<RGB> HipPathTracing::Render(const Scene<RGB>& scene, const Sensor& s
       workers.emplace_back([&, r] {
         try {                                                            // an exception must not leave a std::thread (std::terminate)
           AmberPtParams p{};
-          p.seed = options_.seed; p.max_depth = options_.max_depth; p.device = devices[r]; p.engine = options_.engine; p.reserved = options_.flags;
+          p.seed = options_.seed; p.max_depth = options_.max_depth; p.device = devices[r]; p.engine = options_.engine; p.reserved = options_.flags | (options_.device_build ? AMBER_PT_FLAG_DEVICE_BUILD : 0u);
           p.row_begin = rb; p.row_end = re;
           if (n_dev > 1) {
             p.row_begin = std::min(rb + r * kStripe, re); p.row_end = re;
@@ -507,7 +507,7 @@ const Image<RGB> HipLightTracing::Render(const Scene<RGB>& scene, const Sensor& 
   std::vector<Handle> handles(n_dev);
   for (uint32_t r = 0; r < n_dev; r++) {
     AmberPtParams p{};
-    p.seed = options_.seed; p.max_depth = options_.max_depth; p.device = devices[r]; p.engine = options_.engine; p.reserved = options_.flags;
+    p.seed = options_.seed; p.max_depth = options_.max_depth; p.device = devices[r]; p.engine = options_.engine; p.reserved = options_.flags | (options_.device_build ? AMBER_PT_FLAG_DEVICE_BUILD : 0u);
     Check(amber_hip_pt_create(&fs.flat, &s, &p, &handles[r].h), "amber_hip_pt_create");
   }
   auto sum = sensor.CreateImage<RGB>();

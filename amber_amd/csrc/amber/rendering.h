@@ -77,6 +77,8 @@ struct HipPathTracingOptions {
   std::uint32_t samples_per_launch = 0;    // Context::Iterate() calls claimed per kernel launch; 0 = adapt to time: start at one
                                            // accumulation chunk, double while a batch takes < 100 ms (expiry latency stays bounded)
   std::uint32_t flags = 0;          // AMBER_PT_FLAG_* bits passed to every handle
+  bool device_build = false;        // AMBER_PT_FLAG_DEVICE_BUILD: engine BVH's tree (scenes past 80 objects) is built on the device at create -- a much
+                                    // shorter start, a tree that renders somewhat slower, the same image (when it pays)
   std::uint32_t row_begin = 0, row_end = 0;   // framebuffer band; 0,0 = whole image
   std::uint32_t engine = 0;         // AMBER_ENGINE_*
 };

@@ -25,6 +25,10 @@
 
 #include "pt_device.h"
 
+// The formulae a tree must be conservative by -- object bounds, padding, the binary16 grid and its outward rounding -- exist once and are
+// callable from the host builder below and from the device builder (bvh_device_build.inc).
+#define AMBER_HD __host__ __device__
+
 namespace amber_bvh {
 
 using amber_dev::DevBvhNode;
@@ -45,9 +49,9 @@ constexpr int kBins = AMBER_BVH_BINS;
 
 struct Box {
   float mn[3], mx[3];
-  void reset() { for (int c = 0; c < 3; c++) { mn[c] = 3.0e38f; mx[c] = -3.0e38f; } }
-  void grow(const Box& b) { for (int c = 0; c < 3; c++) { mn[c] = std::min(mn[c], b.mn[c]); mx[c] = std::max(mx[c], b.mx[c]); } }
-  void grow(const float p[3]) { for (int c = 0; c < 3; c++) { mn[c] = std::min(mn[c], p[c]); mx[c] = std::max(mx[c], p[c]); } }
+  AMBER_HD void reset() { for (int c = 0; c < 3; c++) { mn[c] = 3.0e38f; mx[c] = -3.0e38f; } }
+  AMBER_HD void grow(const Box& b) { for (int c = 0; c < 3; c++) { mn[c] = std::min(mn[c], b.mn[c]); mx[c] = std::max(mx[c], b.mx[c]); } }
+  AMBER_HD void grow(const float p[3]) { for (int c = 0; c < 3; c++) { mn[c] = std::min(mn[c], p[c]); mx[c] = std::max(mx[c], p[c]); } }
   double area() const {
     const double x = double(mx[0]) - mn[0], y = double(mx[1]) - mn[1], z = double(mx[2]) - mn[2];
     return (x < 0 || y < 0 || z < 0) ? 0.0 : 2.0 * (x * y + y * z + z * x);
@@ -68,7 +72,7 @@ struct Box {
 // What no static box can cover is a ray within a fraction of a degree of a triangle's plane and nearly parallel to
 // one of its edges, where the same error grows without bound: engine LIST keeps such numerical-noise hits, engine
 // BVH (like the reference's own BVH, which culls with unpadded boxes) may not -- see DESIGN.md section 5.
-inline Box ObjectBox(const DevObject& o, double sphere_slack2 = 0.0, double tri_reach = 0.0) {
+AMBER_HD inline Box ObjectBox(const DevObject& o, double sphere_slack2 = 0.0, double tri_reach = 0.0) {
   Box b; b.reset();
   const uint32_t kind = o.kind & 0xffu;
   if (kind == 0) {            // triangle: v0, v0+E1, v0+E2
@@ -106,7 +110,7 @@ inline Box ObjectBox(const DevObject& o, double sphere_slack2 = 0.0, double tri_
 
 // Padding: an accepted reference hit lies within a few binary32 roundings of the primitive (relative to the
 // coordinates involved); 2^-16 of the scene extent plus 2^-16 of the coordinate magnitude is ~250x that.
-inline void PadBox(Box& b, float scene_extent) {
+AMBER_HD inline void PadBox(Box& b, float scene_extent) {
   for (int c = 0; c < 3; c++) {
     const float m = std::max(std::fabs(b.mn[c]), std::fabs(b.mx[c]));
     const float pad = 1.52587890625e-05f * (scene_extent + m) + 1e-30f;
@@ -295,19 +299,19 @@ struct QuantizedBvh {
 #ifndef AMBER_BVH_F16
 #define AMBER_BVH_F16 1
 #endif
-inline double F16Value(uint16_t h) {                          // exact
+AMBER_HD inline double F16Value(uint16_t h) {                          // exact
   const int e = (h >> 10) & 31, m = h & 1023;
   const double v = e == 0 ? std::ldexp(double(m), -24) : std::ldexp(double(1024 + m), e - 25);
   return (h & 0x8000u) ? -v : v;
 }
-inline uint16_t F16Step(uint16_t h, bool up) {                // the next NORMAL (or zero) binary16 value above / below h; h is normal or zero, finite
+AMBER_HD inline uint16_t F16Step(uint16_t h, bool up) {                // the next NORMAL (or zero) binary16 value above / below h; h is normal or zero, finite
   const bool neg = (h & 0x8000u) != 0;
   const uint16_t mag = h & 0x7fffu;
   if (mag == 0) return up ? 0x0400u : 0x8400u;               // 0 -> +-2^-14
   if (neg == up) return mag == 0x0400u ? 0u : static_cast<uint16_t>((neg ? 0x8000u : 0u) | (mag - 1u));   // towards zero
   return mag >= 0x7bffu ? h : static_cast<uint16_t>((neg ? 0x8000u : 0u) | (mag + 1u));                    // away from zero (stops at 65504)
 }
-inline uint16_t F16Nearest(double u) {                        // some normal-or-zero binary16 value near u (the caller walks to the side it needs)
+AMBER_HD inline uint16_t F16Nearest(double u) {                        // some normal-or-zero binary16 value near u (the caller walks to the side it needs)
   if (!(u == u)) return 0u;
   const bool neg = u < 0; double a = std::fabs(u);
   if (a < std::ldexp(1.0, -14)) return 0u;
@@ -321,7 +325,7 @@ inline uint16_t F16Nearest(double u) {                        // some normal-or-
 // A scene with NO extent on the axis (a planar mesh in x = 1234.5) gets half = 2^-20 |mid|, not a denormal-sized step: with a step
 // far below the rounding of mid, PlaneWord's search for a representable value beyond its guard walked all 30 000 binary16
 // values per plane (a millisecond per node) and ended at +-65504, outside the |value| <= 1 + one step that `reach` promises.
-inline void F16AxisGrid(double lo, double hi, float& mid, float& half) {
+AMBER_HD inline void F16AxisGrid(double lo, double hi, float& mid, float& half) {
   mid = static_cast<float>(0.5 * (lo + hi));
   half = static_cast<float>(std::max(hi - double(mid), double(mid) - lo) * 1.000001);
   const float floor_half = std::max(1e-30f, std::fabs(mid) * 9.5367431640625e-07f);        // 2^-20 |mid|: 16 binary32 ulps of the coordinate
@@ -330,16 +334,21 @@ inline void F16AxisGrid(double lo, double hi, float& mid, float& half) {
 }
 // The word of one axis of a box: value(min) | value(max) << 16 with  gmin + value(min) * step <= mn  and  gmin + value(max) * step >= mx,
 // checked in extended precision with a guard of 2^-50 of the operands' magnitude (one representable value further out when in doubt).
-inline uint32_t PlaneWord(float mn, float mx, float gmin, float step) {
+// Real = long double: the host builder's word (the tightest one).  Real = double (PlaneWordOutward): the same search where there is no
+// wider type, i.e. on the device; gmin + value * step then rounds once, by at most 2^-53 of the guard's operands, which the guard (2^-50
+// of them) covers eight times over -- so its words obey the same inequalities in exact arithmetic and differ from the host's by at most
+// ONE binary16 step, either way, and only when a plane lies within the guard of a representable value (tests/cpp/plane_word_outward_check.cpp).
+template <typename Real>
+AMBER_HD inline uint32_t PlaneWordT(float mn, float mx, float gmin, float step) {
 #if AMBER_BVH_F16
-  const long double g = gmin, st = step;
-  const long double guard = (std::fabs((long double)gmin) + std::fabs((long double)step) * 2.0L) * 0x1p-50L;
-  auto plane = [&](uint16_t h) { return g + (long double)F16Value(h) * st; };
+  const Real g = gmin, st = step;
+  const Real guard = ((g < 0 ? -g : g) + (st < 0 ? -st : st) * Real(2)) * Real(8.8817841970012523e-16);   // 2^-50
+  auto plane = [&](uint16_t h) { return g + Real(F16Value(h)) * st; };
   uint16_t a = F16Nearest((double(mn) - double(gmin)) / double(step)), b = F16Nearest((double(mx) - double(gmin)) / double(step));
-  while (plane(a) > (long double)mn - guard) { const uint16_t n = F16Step(a, false); if (n == a) break; a = n; }
-  for (;;) { const uint16_t n = F16Step(a, true); if (n == a || plane(n) > (long double)mn - guard) break; a = n; }        // the tightest such value
-  while (plane(b) < (long double)mx + guard) { const uint16_t n = F16Step(b, true); if (n == b) break; b = n; }
-  for (;;) { const uint16_t n = F16Step(b, false); if (n == b || plane(n) < (long double)mx + guard) break; b = n; }
+  while (plane(a) > Real(mn) - guard) { const uint16_t n = F16Step(a, false); if (n == a) break; a = n; }
+  for (;;) { const uint16_t n = F16Step(a, true); if (n == a || plane(n) > Real(mn) - guard) break; a = n; }        // the tightest such value
+  while (plane(b) < Real(mx) + guard) { const uint16_t n = F16Step(b, true); if (n == b) break; b = n; }
+  for (;;) { const uint16_t n = F16Step(b, false); if (n == b || plane(n) < Real(mx) + guard) break; b = n; }
   return uint32_t(a) | (uint32_t(b) << 16);
 #else
   const double g = gmin, st = step;
@@ -350,6 +359,8 @@ inline uint32_t PlaneWord(float mn, float mx, float gmin, float step) {
   return uint32_t(a) | (uint32_t(b) << 16);
 #endif
 }
+inline uint32_t PlaneWord(float mn, float mx, float gmin, float step) { return PlaneWordT<long double>(mn, mx, gmin, step); }
+AMBER_HD inline uint32_t PlaneWordOutward(float mn, float mx, float gmin, float step) { return PlaneWordT<double>(mn, mx, gmin, step); }
 inline uint32_t EmptyPlaneWord() {                            // min above max: no ray enters
 #if AMBER_BVH_F16
   return 0x3c00u | (0xbc00u << 16);                           // min +1, max -1

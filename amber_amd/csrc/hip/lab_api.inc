@@ -263,6 +263,21 @@ int amber_hip_kat_pixel_masks(amber_hip_pt* h, uint32_t* out_mask, uint32_t* out
   return AMBER_OK;
 }
 
+int amber_hip_kat_bvh_dump(amber_hip_pt* h, uint32_t* nodes, uint32_t node_capacity, uint32_t* prims, uint32_t prim_capacity, AmberBvhDump* info) {
+  if (!h || !info) return Fail(AMBER_EINVAL, "null argument");
+  if (h->hit_engine != AMBER_ENGINE_BVH) return Fail(AMBER_EINVAL, "the handle's engine is not BVH");
+  HIP_TRY(hipSetDevice(h->device));
+  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  static_assert(sizeof(DevBvhNodeQ) == 8 * sizeof(uint32_t), "a dumped node is 8 words");
+  info->n_nodes = h->build.n_nodes; info->n_prims = h->scene.n_objects; info->root = h->scene.bvh_root; info->depth = h->build.depth;
+  for (int c = 0; c < 3; c++) { info->gmin[c] = h->scene.bvh_gmin[c]; info->step[c] = h->scene.bvh_step[c]; info->reach[c] = h->scene.bvh_reach[c]; }
+  const uint32_t n_nodes = std::min(node_capacity, info->n_nodes), n_prims = std::min(prim_capacity, info->n_prims);
+  if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, h->scene.bvh_nodes, static_cast<size_t>(n_nodes) * sizeof(DevBvhNodeQ), hipMemcpyDeviceToHost));
+  if (prims && n_prims) HIP_TRY(hipMemcpy(prims, h->scene.bvh_prims, static_cast<size_t>(n_prims) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}
+
 int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint64_t* out) {
   if (!h || !out || n_samples == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");

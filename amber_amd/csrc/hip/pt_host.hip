@@ -8,6 +8,8 @@
 //   pt_bvh_megakernel.inc  pt_bvh_megakernel: engine BVH on deep trees -- lanes own (pixel, chunk of 8 samples) items, the closest hit is a RESUMABLE
 //                          per-lane traversal of the 2-wide binary16-plane tree advanced in wave rounds until a batch of lanes has finished; per-item
 //                          sums, reduce_partials_kernel.
+//   bvh_device_build.inc   AMBER_PT_FLAG_DEVICE_BUILD: engine BVH's tree built by kernels at create (Morton order, radix-tree hierarchy, the host builder's
+//                          bounds / padding / outward binary16 planes) instead of bvh_build.h's binned-SAH build on the host.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -17,8 +19,11 @@
 // Replaces: PathTracing<RGB>::Thread::operator() / Render
 //           (/root/reference/src/amber/rendering/algorithm_pt.cc:112-160).
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -153,6 +158,8 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   double timed_ms = 0;
 };
 
+#include "bvh_device_build.inc"
+
 namespace {
 
 uint64_t HostSplitMix64(uint64_t z) {
@@ -201,8 +208,11 @@ hipError_t Upload(amber_hip_pt* h, const std::vector<T>& v, size_t extra, P& dst
   return e;
 }
 
-// validate -> prepare (scene_prep.h) -> upload -> enqueue the pixel masks.  Whatever the handle holds is released on every early return.
+// validate -> prepare (scene_prep.h) -> upload (or, with AMBER_PT_FLAG_DEVICE_BUILD, build engine BVH's tree where the objects now are) -> enqueue the
+// pixel masks.  Whatever the handle holds is released on every early return.
 int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtParams* params, amber_hip_pt** out) {
+  const auto t_create = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   int rc = ValidateScene(s, sensor);
   if (rc != AMBER_OK) return rc;
   int n_dev = 0;
@@ -249,7 +259,8 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
     if (e != hipSuccess) return Fail(AMBER_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
     h->stream = h->own_stream.v;
   }
-  static_cast<amber_prep::SceneState&>(*h) = std::move(p);      // (the device arrays stay in p until the upload)
+  static_cast<amber_prep::SceneState&>(*h) = std::move(p);      // (only the SceneState part moves: the device arrays, p.objects and p.bvh_pending stay in p
+                                                                //  until the upload -- the device build and its host fallback below rely on that)
   h->n_materials = s->n_materials;
   { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, params->device) == hipSuccess && v > 0) h->n_cus = v; }
 
@@ -264,14 +275,35 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
   HIP_TRY(Upload(h.get(), p.prog_objects, 1, sc.prog_objects));
   if (!p.groups.empty()) HIP_TRY(Upload(h.get(), p.groups, 0, sc.groups));
   HIP_TRY(Upload(h.get(), p.lights, 1, sc.lights));
-  HIP_TRY(Upload(h.get(), p.bvh_nodes, 1, sc.bvh_nodes));
+  if (p.bvh_pending) {
+    // engine BVH with AMBER_PT_FLAG_DEVICE_BUILD: the tree from the objects where they now are.  A tree the traversal must not walk (too deep) or
+    // that cannot be built (no finite bounds) is replaced by the host's: same arrays, same upload as without the flag.
+    const auto t_tree = std::chrono::steady_clock::now();
+    uint32_t reason = AMBER_BUILD_REASON_NONE, n_nodes = 0, depth = 0;
+    { const int rc_build = DeviceBuildBvh(h.get(), p.objects, &reason, &n_nodes, &depth); if (rc_build != AMBER_OK) return rc_build; }
+    if (reason == AMBER_BUILD_REASON_NONE) {
+      amber_prep::ChooseBvhScheduler(*h, p.objects, params, env, n_nodes, depth, AMBER_PATH_BVH_STACK, AMBER_BVH_SHADE_BATCH);
+      h->build.where = AMBER_BUILD_DEVICE; h->build.n_nodes = n_nodes; h->build.n_leaves = n_nodes + 1u; h->build.depth = depth;
+      p.bvh_pending = false;
+      h->build.tree_ms = ms_since(t_tree);
+    } else {
+      const double spent = ms_since(t_tree);
+      amber_prep::HostBvhFallback(*h, p, reason, params, env, AMBER_PATH_BVH_STACK, AMBER_BVH_SHADE_BATCH);
+      h->build.tree_ms += spent;
+    }
+  }
+  if (h->build.where != AMBER_BUILD_DEVICE) {
+    const auto t_upload = std::chrono::steady_clock::now();
+    HIP_TRY(Upload(h.get(), p.bvh_nodes, 1, sc.bvh_nodes));
 #if AMBER_BVH_WIDE
-  HIP_TRY(Upload(h.get(), p.bvh_nodes4, 1, sc.bvh_nodes4));
+    HIP_TRY(Upload(h.get(), p.bvh_nodes4, 1, sc.bvh_nodes4));
 #endif
-  HIP_TRY(Upload(h.get(), p.bvh_prims, 1, sc.bvh_prims));
-  HIP_TRY(Upload(h.get(), p.bvh_tris, 3, sc.bvh_tris));
-  HIP_TRY(Upload(h.get(), p.bvh_objects, 1, sc.bvh_objects));
-  HIP_TRY(Upload(h.get(), p.bvh_spheres, 1, sc.bvh_spheres));
+    HIP_TRY(Upload(h.get(), p.bvh_prims, 1, sc.bvh_prims));
+    HIP_TRY(Upload(h.get(), p.bvh_tris, 3, sc.bvh_tris));
+    HIP_TRY(Upload(h.get(), p.bvh_objects, 1, sc.bvh_objects));
+    HIP_TRY(Upload(h.get(), p.bvh_spheres, 1, sc.bvh_spheres));
+    if (h->hit_engine == AMBER_ENGINE_BVH) h->build.tree_ms += ms_since(t_upload);
+  }
   HIP_TRY(Upload(h.get(), std::vector<DevLens>{p.lens}, 0, sc.lens));
   const size_t fb_floats = static_cast<size_t>(local_rows) * sensor->width * 3;
   HIP_TRY(h->d_fb.alloc(fb_floats));
@@ -294,6 +326,7 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
     sc.ref_stack = h->d_ref_stack; sc.ref_stack_stride = static_cast<uint32_t>(threads);
   }
   { const int rc_masks = StartPixelMasks(h.get(), nullptr); if (rc_masks != AMBER_OK) return rc_masks; }   // asynchronous, on the render stream: in front of the handle's first launch
+  h->build.create_ms = ms_since(t_create);
   *out = h.release();
   return AMBER_OK;
 }
@@ -835,6 +868,12 @@ int amber_hip_pt_stream(amber_hip_pt* h, void** stream) {
 int amber_hip_pt_local_rows(amber_hip_pt* h, uint32_t* n_rows) {
   if (!h || !n_rows) return Fail(AMBER_EINVAL, "null argument");
   *n_rows = h->local_rows;
+  return AMBER_OK;
+}
+
+int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) {
+  if (!h || !out) return Fail(AMBER_EINVAL, "null argument");
+  *out = h->build;
   return AMBER_OK;
 }
 

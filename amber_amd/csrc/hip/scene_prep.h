@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +38,8 @@ struct EnvSwitches {
   bool pixel_mask = true;                           // AMBER_PIXEL_MASK=0: no per-pixel candidate masks of the primary rays
   uint32_t pixel_mask_block = 0;                    // AMBER_PIXEL_MASK_BLOCK=1/2/4: side of a mask's block of pixels (measurement hook); 0: not set
   double test_density_scale = 0;                    // AMBER_TEST_RECORD_DENSITY_SCALE: a test hook that mis-sizes the record buffer; 0: off
+  uint32_t test_device_build_max_depth = 0;         // AMBER_TEST_DEVICE_BUILD_MAX_DEPTH: a test hook that lowers the depth the device build accepts, so that
+                                                    // create's host fallback runs on an ordinary scene; 0: off (the limit is kMaxDepth)
 };
 
 inline EnvSwitches ReadEnv() {
@@ -54,6 +57,7 @@ inline EnvSwitches ReadEnv() {
   e.pixel_mask = !((ev = std::getenv("AMBER_PIXEL_MASK")) && ev[0] == '0');
   if ((ev = std::getenv("AMBER_PIXEL_MASK_BLOCK")) && (ev[0] == '1' || ev[0] == '2' || ev[0] == '4') && ev[1] == 0) e.pixel_mask_block = static_cast<uint32_t>(ev[0] - '0');
   if ((ev = std::getenv("AMBER_TEST_RECORD_DENSITY_SCALE"))) e.test_density_scale = std::atof(ev);
+  if ((ev = std::getenv("AMBER_TEST_DEVICE_BUILD_MAX_DEPTH")) && std::atoi(ev) > 0) e.test_device_build_max_depth = static_cast<uint32_t>(std::atoi(ev));
   return e;
 }
 
@@ -70,10 +74,61 @@ struct SceneState {
   float aperture_rect[4][3] = {};            // world corners of the blades' bounding rectangle in the lens plane (pixel_mask_kernel)
   std::vector<uint32_t> prog_order;          // two-phase engine: scene index of the object in filter-program slot k (the bit positions of the masks)
   std::vector<DevPlane> host_planes;         // ... and its plane records (pixel_mask_kernel's wave-uniform tests are made on the host)
+  AmberBuildInfo build{};                    // engine BVH's tree: who built it, its size, what the tree stage cost (amber_hip_pt_build_info)
 };
+
+// Engine BVH's scheduler and shading batch, from the depth of its tree -- whoever built it.
+inline void ChooseBvhScheduler(SceneState& st, const std::vector<DevObject>& objs, const AmberPtParams* params, const EnvSwitches& env,
+                               size_t n_nodes, uint32_t depth, uint32_t path_bvh_stack, uint32_t shade_batch) {
+  st.bvh_paths = !st.bvh_pool && !(params->reserved & AMBER_PT_FLAG_BVH_ITEMS) && st.engine != AMBER_ENGINE_WAVEFRONT && depth <= path_bvh_stack;
+  // The shading batch of pt_bvh_megakernel.  While a wave collects finished lanes they idle through the rounds of the others, and a round
+  // over triangle leaves costs about twice a round over sphere leaves (45 against 20 vector instructions per leaf object before any
+  // root / quotient), so idle lanes are dearer in a mesh: tools/shade_batch_sweep.py (profiles/r05_shade_batch_sweep.txt) -- 1M spheres
+  // best at 52 (49.7 ms at 64 spp; 40: 52.3), 1M-triangle terrain at 32 (62.1; 40: 63.8; 52: 68.5), 82k-triangle room at 36-44 (32.8; 52: 33.9).
+  {
+    size_t n_triangles = 0;                                   // (every scene has a few: the aperture blades)
+    for (const DevObject& ob : objs) n_triangles += (ob.kind & 0xffu) == AMBER_PRIM_TRIANGLE ? 1u : 0u;
+    st.bvh_shade_batch = 2u * n_triangles > objs.size() ? 40u : shade_batch;   // a mesh: 40; mostly spheres (disks, cylinders): 52
+  }
+  if (env.bvh_shade_batch) st.bvh_shade_batch = env.bvh_shade_batch;
+  if (env.bvh_paths_off || env.bvh_paths_max_depth < depth) st.bvh_paths = false;
+  if (env.debug_bvh) std::fprintf(stderr, "amber_hip: BVH of %zu objects: %zu nodes, depth %u; scheduler %s, shading batch %u\n", objs.size(), n_nodes, depth,
+                                  st.bvh_pool ? "pt_bvh_pool_kernel" : (st.bvh_paths ? "pt_megakernel<ENGINE_BVH>" : "pt_bvh_megakernel"), st.bvh_shade_batch);
+}
+
+// The host builder (bvh_build.h) and what follows from its tree's depth.
+inline amber_bvh::FlatBvh BuildHostTree(SceneState& st, const std::vector<DevObject>& objs, const AmberPtParams* params, const EnvSwitches& env,
+                                        uint32_t path_bvh_stack, uint32_t shade_batch) {
+  const auto t0 = std::chrono::steady_clock::now();
+  amber_bvh::FlatBvh bvh = amber_bvh::BuildBvh(objs);
+  st.build.tree_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (env.debug_bvh) {
+    const amber_bvh::BvhQuality q = amber_bvh::MeasureBvh(bvh.nodes, bvh.root_ref);
+    std::fprintf(stderr, "amber_hip: BVH %s: SAH inner-node term %.3f, leaf term %.3f (x objects %.3f), leaf volume / scene volume %.3f; %u inner nodes, %u leaves, %u levels\n",
+                 "as built", q.inner_area, q.leaf_area, q.leaf_object_area, q.leaf_volume, q.inner, q.leaves, q.depth);
+  }
+  ChooseBvhScheduler(st, objs, params, env, bvh.nodes.size(), bvh.depth, path_bvh_stack, shade_batch);
+  st.build.where = st.build.fallback_reason ? AMBER_BUILD_HOST_FALLBACK : AMBER_BUILD_HOST;
+  st.build.n_nodes = static_cast<uint32_t>(bvh.nodes.size()); st.build.n_leaves = st.build.n_nodes + 1u; st.build.depth = bvh.depth;
+  return bvh;
+}
+
+// Per-ray box margin of engine BVH (BvhBegin) from the bounds of all widened object boxes: centre and half diagonal of the scene bounds, 1 / smallest sphere radius
+inline void SetBvhRayMargin(DevScene& sc, const float bounds_min[3], const float bounds_max[3], bool has_spheres, float min_sphere_radius) {
+  double d2 = 0;
+  for (int c = 0; c < 3; c++) {
+    sc.bvh_center[c] = 0.5f * (bounds_min[c] + bounds_max[c]);
+    const double e = double(bounds_max[c]) - bounds_min[c];
+    d2 += e * e;
+  }
+  sc.bvh_half_diag = static_cast<float>(0.5 * std::sqrt(d2) * 1.0001);
+  sc.bvh_inv_rmin = !has_spheres ? 0.0f : (min_sphere_radius > 0 ? static_cast<float>(std::min(3.0e38, 1.0001 / min_sphere_radius)) : 3.0e38f);
+}
+
 
 struct PreparedScene : SceneState {
   std::string error;                         // not empty: create refuses the scene (AMBER_EINVAL) with this message
+  bool bvh_pending = false;                  // AMBER_PT_FLAG_DEVICE_BUILD on engine BVH: no tree yet -- create builds it on the device (bvh_device_build.inc) or calls HostBvh
   uint32_t ref_depth = 0;                    // levels of the reference's tree (engine REFERENCE_BVH: its traversal stack)
   // the device arrays
   std::vector<DevObject> objects;
@@ -93,6 +148,62 @@ struct PreparedScene : SceneState {
   std::vector<DevRefNode> ref_nodes;         // engine REFERENCE_BVH: the reference's own tree
   std::vector<DevRefLeaf> ref_leaves;
 };
+
+// st and p are the same object while PrepareScene runs; in create's fallback (HostBvhFallback) the state has been moved into the handle and
+// p still holds the arrays to upload, so the scalars go to st and the vectors to p.
+// Engine BVH's device arrays from a host-built tree: quantised nodes, leaf-order permutation, object records and compact sphere / triangle
+// records in leaf order, the grid and the per-ray margin.  (Engine REFERENCE_BVH: only the object arrays, in the order bvh.prim_index gives.)
+inline void FillBvhArrays(SceneState& st, PreparedScene& p, const std::vector<DevObject>& objs, amber_bvh::FlatBvh& bvh) {
+  const auto t0 = std::chrono::steady_clock::now();
+  amber_bvh::QuantizedBvh qbvh = amber_bvh::QuantizeBvh(bvh.nodes, bvh.root_ref, [&](uint32_t slot) { return objs[bvh.prim_index[slot]].kind & 0xffu; });
+#if AMBER_BVH_WIDE
+  {
+    amber_bvh::QuantizedBvh4 q4 = amber_bvh::CollapseBvh4(bvh.nodes, bvh.root_ref, qbvh, [&](uint32_t slot) { return objs[bvh.prim_index[slot]].kind & 0xffu; });
+    p.bvh_nodes4 = std::move(q4.nodes);
+    qbvh.root_ref = q4.root_ref;
+  }
+#endif
+  p.bvh_nodes = std::move(qbvh.nodes);
+  {
+    std::vector<DevObject>& leaf_order = p.bvh_objects;
+    std::vector<float4>& leaf_spheres = p.bvh_spheres;
+    leaf_order.resize(bvh.prim_index.size());
+    leaf_spheres.resize(bvh.prim_index.size());
+    for (size_t k = 0; k < leaf_order.size(); k++) {
+      const DevObject& ob = objs[bvh.prim_index[k]];
+      leaf_order[k] = ob;
+      leaf_spheres[k] = (ob.kind & 0xffu) == AMBER_PRIM_SPHERE ? make_float4(ob.a[0], ob.a[1], ob.a[2], ob.radius) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    // compact triangle records of the leaves (IntersectTriangleLeaf): three float4 per leaf-order slot, only when the scene has triangles
+    bool any_tri = false;
+    for (const DevObject& ob : leaf_order) any_tri = any_tri || (ob.kind & 0xffu) == AMBER_PRIM_TRIANGLE;
+    std::vector<float4>& leaf_tris = p.bvh_tris;
+    leaf_tris.resize(any_tri ? 3 * leaf_order.size() : 0);
+    for (size_t k = 0; any_tri && k < leaf_order.size(); k++) {
+      const DevObject& ob = leaf_order[k];
+      if ((ob.kind & 0xffu) != AMBER_PRIM_TRIANGLE) { leaf_tris[3 * k] = leaf_tris[3 * k + 1] = leaf_tris[3 * k + 2] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
+      float idx; const uint32_t scene_index = bvh.prim_index[k]; std::memcpy(&idx, &scene_index, 4);
+      leaf_tris[3 * k] = make_float4(ob.a[0], ob.a[1], ob.a[2], ob.e1[0]);
+      leaf_tris[3 * k + 1] = make_float4(ob.e1[1], ob.e1[2], ob.e2[0], ob.e2[1]);
+      leaf_tris[3 * k + 2] = make_float4(ob.e2[2], idx, 0.f, 0.f);
+    }
+  }
+  p.bvh_prims = std::move(bvh.prim_index);
+  DevScene& sc = st.scene;
+  sc.bvh_root = qbvh.root_ref;
+  for (int c = 0; c < 3; c++) { sc.bvh_gmin[c] = qbvh.gmin[c]; sc.bvh_step[c] = qbvh.step[c]; sc.bvh_reach[c] = qbvh.reach[c]; }
+  SetBvhRayMargin(sc, bvh.bounds_min, bvh.bounds_max, bvh.has_spheres, bvh.min_sphere_radius);
+  if (st.hit_engine == AMBER_ENGINE_BVH) st.build.tree_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// A scene prepared with its tree pending (AMBER_PT_FLAG_DEVICE_BUILD) whose tree the device did not build: the host builder after all.
+// st: where the scene's state lives by now (create has moved it into the handle).
+inline void HostBvhFallback(SceneState& st, PreparedScene& p, uint32_t reason, const AmberPtParams* params, const EnvSwitches& env, uint32_t path_bvh_stack, uint32_t shade_batch) {
+  st.build.fallback_reason = reason;
+  amber_bvh::FlatBvh bvh = BuildHostTree(st, p.objects, params, env, path_bvh_stack, shade_batch);
+  FillBvhArrays(st, p, p.objects, bvh);
+  p.bvh_pending = false;
+}
 
 // The scene, sensor and parameters are those amber_hip_pt_create has validated; path_bvh_stack and shade_batch are the kernels'
 // AMBER_PATH_BVH_STACK and AMBER_BVH_SHADE_BATCH.
@@ -158,27 +269,14 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
 #endif
   amber_bvh::FlatBvh bvh;
   if (p.hit_engine == AMBER_ENGINE_BVH) {
-    bvh = amber_bvh::BuildBvh(objs);
-    auto report = [&](const char* what) {
-      const amber_bvh::BvhQuality q = amber_bvh::MeasureBvh(bvh.nodes, bvh.root_ref);
-      std::fprintf(stderr, "amber_hip: BVH %s: SAH inner-node term %.3f, leaf term %.3f (x objects %.3f), leaf volume / scene volume %.3f; %u inner nodes, %u leaves, %u levels\n",
-                   what, q.inner_area, q.leaf_area, q.leaf_object_area, q.leaf_volume, q.inner, q.leaves, q.depth);
-    };
-    if (env.debug_bvh) report("as built");
-    p.bvh_paths = !p.bvh_pool && !(params->reserved & AMBER_PT_FLAG_BVH_ITEMS) && p.engine != AMBER_ENGINE_WAVEFRONT && bvh.depth <= path_bvh_stack;
-    // The shading batch of pt_bvh_megakernel.  While a wave collects finished lanes they idle through the rounds of the others, and a round
-    // over triangle leaves costs about twice a round over sphere leaves (45 against 20 vector instructions per leaf object before any
-    // root / quotient), so idle lanes are dearer in a mesh: tools/shade_batch_sweep.py (profiles/r05_shade_batch_sweep.txt) -- 1M spheres
-    // best at 52 (49.7 ms at 64 spp; 40: 52.3), 1M-triangle terrain at 32 (62.1; 40: 63.8; 52: 68.5), 82k-triangle room at 36-44 (32.8; 52: 33.9).
-    {
-      size_t n_triangles = 0;                                   // (every scene has a few: the aperture blades)
-      for (const DevObject& ob : objs) n_triangles += (ob.kind & 0xffu) == AMBER_PRIM_TRIANGLE ? 1u : 0u;
-      p.bvh_shade_batch = 2u * n_triangles > objs.size() ? 40u : shade_batch;   // a mesh: 40; mostly spheres (disks, cylinders): 52
-    }
-    if (env.bvh_shade_batch) p.bvh_shade_batch = env.bvh_shade_batch;
-    if (env.bvh_paths_off || env.bvh_paths_max_depth < bvh.depth) p.bvh_paths = false;
-    if (env.debug_bvh) std::fprintf(stderr, "amber_hip: BVH of %u objects: %zu nodes, depth %u; scheduler %s, shading batch %u\n", s->n_objects, bvh.nodes.size(), bvh.depth,
-                                    p.bvh_pool ? "pt_bvh_pool_kernel" : (p.bvh_paths ? "pt_megakernel<ENGINE_BVH>" : "pt_bvh_megakernel"), p.bvh_shade_batch);
+    const bool device_build = (params->reserved & AMBER_PT_FLAG_DEVICE_BUILD) != 0u;
+#if AMBER_BVH_WIDE
+    if (device_build) p.build.fallback_reason = AMBER_BUILD_REASON_WIDE;   // the device builder writes 2-wide nodes only
+    bvh = BuildHostTree(p, objs, params, env, path_bvh_stack, shade_batch);
+#else
+    if (device_build) p.bvh_pending = true;
+    else bvh = BuildHostTree(p, objs, params, env, path_bvh_stack, shade_batch);
+#endif
   }
   amber_refbvh::FlatTree ref_tree;
   if (p.hit_engine == AMBER_ENGINE_REFERENCE_BVH) {
@@ -272,59 +370,13 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
     }
   }
 
-  // engine BVH: quantised nodes, leaf-order permutation, object records and compact sphere records in leaf order
-  amber_bvh::QuantizedBvh qbvh = amber_bvh::QuantizeBvh(bvh.nodes, bvh.root_ref, [&](uint32_t slot) { return objs[bvh.prim_index[slot]].kind & 0xffu; });
-#if AMBER_BVH_WIDE
-  {
-    amber_bvh::QuantizedBvh4 q4 = amber_bvh::CollapseBvh4(bvh.nodes, bvh.root_ref, qbvh, [&](uint32_t slot) { return objs[bvh.prim_index[slot]].kind & 0xffu; });
-    p.bvh_nodes4 = std::move(q4.nodes);
-    qbvh.root_ref = q4.root_ref;
-  }
-#endif
-  p.bvh_nodes = std::move(qbvh.nodes);
-  {
-    std::vector<DevObject>& leaf_order = p.bvh_objects;
-    std::vector<float4>& leaf_spheres = p.bvh_spheres;
-    leaf_order.resize(bvh.prim_index.size());
-    leaf_spheres.resize(bvh.prim_index.size());
-    for (size_t k = 0; k < leaf_order.size(); k++) {
-      const DevObject& ob = objs[bvh.prim_index[k]];
-      leaf_order[k] = ob;
-      leaf_spheres[k] = (ob.kind & 0xffu) == AMBER_PRIM_SPHERE ? make_float4(ob.a[0], ob.a[1], ob.a[2], ob.radius) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    // compact triangle records of the leaves (IntersectTriangleLeaf): three float4 per leaf-order slot, only when the scene has triangles
-    bool any_tri = false;
-    for (const DevObject& ob : leaf_order) any_tri = any_tri || (ob.kind & 0xffu) == AMBER_PRIM_TRIANGLE;
-    std::vector<float4>& leaf_tris = p.bvh_tris;
-    leaf_tris.resize(any_tri ? 3 * leaf_order.size() : 0);
-    for (size_t k = 0; any_tri && k < leaf_order.size(); k++) {
-      const DevObject& ob = leaf_order[k];
-      if ((ob.kind & 0xffu) != AMBER_PRIM_TRIANGLE) { leaf_tris[3 * k] = leaf_tris[3 * k + 1] = leaf_tris[3 * k + 2] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
-      float idx; const uint32_t scene_index = bvh.prim_index[k]; std::memcpy(&idx, &scene_index, 4);
-      leaf_tris[3 * k] = make_float4(ob.a[0], ob.a[1], ob.a[2], ob.e1[0]);
-      leaf_tris[3 * k + 1] = make_float4(ob.e1[1], ob.e1[2], ob.e2[0], ob.e2[1]);
-      leaf_tris[3 * k + 2] = make_float4(ob.e2[2], idx, 0.f, 0.f);
-    }
-  }
-  p.bvh_prims = std::move(bvh.prim_index);
+  if (!p.bvh_pending) FillBvhArrays(p, p, objs, bvh);
   p.ref_nodes = std::move(ref_tree.nodes);
   p.ref_leaves = std::move(ref_tree.leaves);
 
   DevScene& sc = p.scene;
   sc.n_planes = static_cast<uint32_t>(fprog.planes.size()); sc.n_simple_planes = fprog.n_simple_planes; sc.n_sphere_filters = static_cast<uint32_t>(fprog.spheres.size());
-  sc.bvh_root = p.hit_engine == AMBER_ENGINE_REFERENCE_BVH ? ref_tree.root : qbvh.root_ref;
-  for (int c = 0; c < 3; c++) { sc.bvh_gmin[c] = qbvh.gmin[c]; sc.bvh_step[c] = qbvh.step[c]; sc.bvh_reach[c] = qbvh.reach[c]; }
-  {
-    // per-ray box margin of engine BVH (BvhBegin): centre and half diagonal of the scene bounds, 1 / smallest sphere radius
-    double d2 = 0;
-    for (int c = 0; c < 3; c++) {
-      sc.bvh_center[c] = 0.5f * (bvh.bounds_min[c] + bvh.bounds_max[c]);
-      const double e = double(bvh.bounds_max[c]) - bvh.bounds_min[c];
-      d2 += e * e;
-    }
-    sc.bvh_half_diag = static_cast<float>(0.5 * std::sqrt(d2) * 1.0001);
-    sc.bvh_inv_rmin = !bvh.has_spheres ? 0.0f : (bvh.min_sphere_radius > 0 ? static_cast<float>(std::min(3.0e38, 1.0001 / bvh.min_sphere_radius)) : 3.0e38f);
-  }
+  if (p.hit_engine == AMBER_ENGINE_REFERENCE_BVH) sc.bvh_root = ref_tree.root;
   for (int c = 0; c < 3; c++) sc.fp_center[c] = fp_center[c];
   sc.fp_reach = fp_reach;
   // origin within fp_reach (max norm) of the centre, objects within half of that: no two such points are farther apart than

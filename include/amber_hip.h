@@ -29,7 +29,9 @@ extern "C" {
 
 #define AMBER_HIP_ABI_VERSION 3   /* 3 (round 5): the known-answer / signature entry points, engine WAVEFRONT and AMBER_PT_FLAG_BVH_POOL moved to the lab library
                                     (amber_hip_lab.h); AMBER_PT_FLAG_BVH_ITEMS added.  2 (round 4): lt ranges, stream; a stream-ordered read of
-                                    amber_hip_pt_device_framebuffer() needs amber_hip_pt_sync() first when a launch may have run out of record slots */
+                                    amber_hip_pt_device_framebuffer() needs amber_hip_pt_sync() first when a launch may have run out of record slots.
+                                    Still 3 with AMBER_PT_FLAG_DEVICE_BUILD and amber_hip_pt_build_info(): a flag bit that older libraries ignore and
+                                    a new function; nothing that existed changed its layout or meaning */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -140,9 +142,15 @@ enum {
   AMBER_PT_FLAG_NULL_STREAM = 1u,
   AMBER_PT_FLAG_BVH_POOL = 2u,    /* LAB BUILD ONLY (the product answers AMBER_EINVAL): engine BVH scheduled with the per-wave ray pool
                                      (pt_bvh_pool_kernel).  Same results bit for bit; measured slower on the 1M-sphere scene. */
-  AMBER_PT_FLAG_BVH_ITEMS = 4u    /* engine BVH: always pt_bvh_megakernel.  By default a tree of depth <= 12 (scenes of a few hundred
+  AMBER_PT_FLAG_BVH_ITEMS = 4u,   /* engine BVH: always pt_bvh_megakernel.  By default a tree of depth <= 12 (scenes of a few hundred
                                      objects) renders with the path-granular kernel and a one-shot per-lane traversal
                                      (pt_megakernel<ENGINE_BVH>): same results bit for bit, faster on shallow trees. */
+  AMBER_PT_FLAG_DEVICE_BUILD = 8u /* engine BVH (AUTO past 80 objects, AMBER_ENGINE_BVH, WAVEFRONT over either): create builds the tree on the
+                                     device -- Morton order, radix-tree hierarchy, the host builder's bounds, padding and outward binary16
+                                     planes -- instead of the host's binned-SAH build: a much shorter create, a tree that renders somewhat slower
+                                     (INTEGRATION.md gives the break-even), the same image bit for bit (the answer never depends on the tree).
+                                     A Morton tree deeper than the traversal's limit is replaced by the host's (amber_hip_pt_build_info says
+                                     so).  Any other engine: accepted, no effect. */
 };
 
 /* All engines are the same persistent work-queue kernel; they differ in how a lane finds its closest hit.
@@ -190,6 +198,26 @@ int  amber_hip_pt_device_framebuffer(amber_hip_pt*, void** dptr, uint64_t* n_flo
 int  amber_hip_pt_stream(amber_hip_pt*, void** stream);
 /* Number of framebuffer rows this handle owns (after striping). */
 int  amber_hip_pt_local_rows(amber_hip_pt*, uint32_t* n_rows);
+/* Engine BVH's tree as create built it.  Works for every handle. */
+enum { AMBER_BUILD_NONE = 0,            /* the handle's engine has no such tree (LIST, TWO_PHASE, REFERENCE_BVH) */
+       AMBER_BUILD_HOST = 1, AMBER_BUILD_DEVICE = 2,
+       AMBER_BUILD_HOST_FALLBACK = 3 }; /* AMBER_PT_FLAG_DEVICE_BUILD was set, the host built the tree: fallback_reason */
+enum { AMBER_BUILD_REASON_NONE = 0,
+       AMBER_BUILD_REASON_DEPTH = 1,    /* the Morton tree is deeper than the traversal's limit (30 levels): clustered or coincident objects */
+       AMBER_BUILD_REASON_WIDE = 2,     /* an AMBER_BVH_WIDE measurement build: the device builder writes 2-wide nodes only */
+       AMBER_BUILD_REASON_BOUNDS = 3 }; /* the scene's bounds are not finite: no Morton order */
+typedef struct {
+  uint32_t where;            /* AMBER_BUILD_* */
+  uint32_t fallback_reason;  /* AMBER_BUILD_REASON_* */
+  uint32_t n_nodes;          /* inner nodes (0: the whole scene is one leaf) */
+  uint32_t n_leaves;
+  uint32_t depth;            /* inner nodes on the longest way from the root to a leaf */
+  uint32_t pad;
+  double   tree_ms;          /* host wall time of the tree stage of create, everything it waits for included: build, quantisation, the leaf-order
+                                arrays and their way into device memory; after a fallback, both attempts */
+  double   create_ms;        /* host wall time of amber_hip_pt_create */
+} AmberBuildInfo;
+int  amber_hip_pt_build_info(amber_hip_pt*, AmberBuildInfo* out);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);

@@ -56,6 +56,11 @@ int amber_hip_kat_traversal_rate(amber_hip_pt*, uint32_t n, const float* origins
  * aperture blades, which a primary ray adds itself).  kernel_ms: duration of the mask kernel (create has run it once; asking for the duration runs it again between two events).
  * Any pointer may be NULL. */
 int amber_hip_kat_pixel_masks(amber_hip_pt*, uint32_t* out_mask, uint32_t* out_slot_of_object, uint32_t* out_always_mask, double* kernel_ms);
+/* Engine BVH's tree as the device holds it, built by the host or by the device (AMBER_PT_FLAG_DEVICE_BUILD): copies up to node_capacity nodes
+ * (8 words each: six plane words min | max << 16 for left x y z, right x y z, then the left and right child references) and up to
+ * prim_capacity entries of the leaf order (leaf slot -> object index); info always receives the sizes and the scalars.  nodes / prims may be NULL. */
+typedef struct { uint32_t n_nodes, n_prims; int32_t root; uint32_t depth; float gmin[3], step[3], reach[3]; } AmberBvhDump;
+int amber_hip_kat_bvh_dump(amber_hip_pt*, uint32_t* nodes, uint32_t node_capacity, uint32_t* prims, uint32_t prim_capacity, AmberBvhDump* info);
 /* the engine's sin/cos/pow on device: mode 0 = sincos(x[i]) -> out[2i], out[2i+1] ; mode 1 = pow(x[2i], x[2i+1]) -> out[i] ;
  * mode 2 / 3 = x[i]^4 / x[i]^5 in binary64 -> out[2i], out[2i+1] = low, high word of the double */
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out);
