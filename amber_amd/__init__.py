@@ -24,6 +24,9 @@ from .api import (  # noqa: F401
     BUILD_REASON_DEPTH,
     BUILD_REASON_WIDE,
     BUILD_REASON_BOUNDS,
+    UPDATE_REFIT,
+    UPDATE_REBUILD,
+    UpdateInfo,
     AmberError,
     FlatMaterial,
     FlatObject,

@@ -71,6 +71,12 @@ class BuildInfo(C.Structure):
                 ("pad", C.c_uint32), ("tree_ms", C.c_double), ("create_ms", C.c_double)]
 
 
+class UpdateInfo(C.Structure):
+    """AmberUpdateInfo: what amber_hip_pt_update_objects did, and the tree now in use."""
+    _fields_ = [("mode_used", C.c_uint32), ("fallback_reason", C.c_uint32), ("n_nodes", C.c_uint32), ("depth", C.c_uint32),
+                ("area_before", C.c_float), ("area_after", C.c_float), ("update_ms", C.c_double)]
+
+
 class BvhDumpInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_prims", C.c_uint32), ("root", C.c_int32), ("depth", C.c_uint32),
                 ("gmin", C.c_float * 3), ("step", C.c_float * 3), ("reach", C.c_float * 3)]
@@ -81,6 +87,7 @@ class HostStats(C.Structure):
 
 
 PRIM_TRIANGLE, PRIM_SPHERE, PRIM_DISK, PRIM_CYLINDER = 0, 1, 2, 3
+_RECORD = np.dtype([("kind", np.uint32), ("material", np.uint32), ("p", np.float32, (12,))])     # AmberFlatObject
 MAT_LAMBERTIAN, MAT_PHONG, MAT_SPECULAR, MAT_REFRACTION, MAT_DIFFUSE_LIGHT, MAT_EYE = 0, 1, 2, 3, 4, 5
 ENGINE_AUTO, ENGINE_LIST, ENGINE_TWO_PHASE, ENGINE_BVH, ENGINE_WAVEFRONT = 0, 1, 2, 3, 4
 ENGINE_REFERENCE_BVH = 6     # the reference's own tree and traversal order: every ray gets the hit the reference's BVH gives it (include/amber_hip.h)
@@ -88,11 +95,12 @@ PT_FLAG_NULL_STREAM, PT_FLAG_BVH_POOL, PT_FLAG_BVH_ITEMS = 1, 2, 4
 PT_FLAG_DEVICE_BUILD = 8     # engine BVH: create builds the tree on the device (include/amber_hip.h)
 BUILD_NONE, BUILD_HOST, BUILD_DEVICE, BUILD_HOST_FALLBACK = 0, 1, 2, 3
 BUILD_REASON_NONE, BUILD_REASON_DEPTH, BUILD_REASON_WIDE, BUILD_REASON_BOUNDS = 0, 1, 2, 3
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1     # amber_hip_pt_update_objects: keep the tree's topology and recompute its boxes / build the Morton tree again
 
 # every symbol include/amber_hip.h and include/amber_host.h declare: what libamber_hip.so (the product) exports
 ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
-    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_destroy",
+    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_destroy",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -149,6 +157,8 @@ def load_library() -> C.CDLL:
     lib.amber_hip_pt_destroy.restype = None
     if hasattr(lib, "amber_hip_pt_build_info"):    # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_pt_build_info.argtypes = [vp, C.POINTER(BuildInfo)]
+    if hasattr(lib, "amber_hip_pt_update_objects"):
+        lib.amber_hip_pt_update_objects.argtypes = [vp, u32, u32, vp, u32, C.POINTER(UpdateInfo)]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -296,6 +306,7 @@ class PathTracer:
         flags = AMBER_PT_FLAG_* bits (PT_FLAG_BVH_POOL: engine BVH with the per-wave ray pool scheduler; PT_FLAG_DEVICE_BUILD: engine BVH's tree
         built on the device at create)."""
         self.sensor = sensor
+        self._scene, self._resident = scene, None     # update_objects: the scene's flattened kinds and materials (an update never changes them)
         rb, re = rows if rows is not None else (0, sensor.height)
         s_rows, s_period = stripe if stripe else (0, 0)
         p = PtParams(seed, max_depth, device, rb, re, stream, engine, s_rows, s_period, flags)
@@ -355,6 +366,57 @@ class PathTracer:
         b = BuildInfo()
         _check(load_library().amber_hip_pt_build_info(self._h, C.byref(b)))
         return {k: getattr(b, k) for k, _ in BuildInfo._fields_ if k != "pad"}
+
+    def update_objects(self, first: int, kinds, material_index, params, mode: int = UPDATE_REFIT) -> dict:
+        """amber_hip_pt_update_objects for callers who hold arrays as HostScene.create_arrays takes them: new geometry for the scene objects
+        [first, first + len(kinds)) -- `first` is a SCENE index, i.e. a position in HostScene.flatten() (create_arrays puts the aperture blades in
+        front of the caller's objects: lens.first_blade_object, lens.n_blades) -- and engine BVH's tree refitted (UPDATE_REFIT) or rebuilt
+        (UPDATE_REBUILD) on the device.  Returns AmberUpdateInfo as a dict.  The framebuffer is not cleared.
+
+        The records are made the way the scene would flatten them: the host object model builds the primitives (triangle normals, unit disk /
+        cylinder axes) and flattens them.  Flattening renumbers materials in order of first appearance, so `material_index` cannot be passed
+        through; an update keeps every object's material anyway, so the resident (flattened) index is kept and `material_index` only has to be
+        consistent with it: objects that had one index still have one index, and different indices stay different.  This builds a temporary
+        host scene of the range; callers who already hold flattened records (HostScene.flatten()) use update_flat."""
+        kinds, material_index = np.ascontiguousarray(kinds, np.uint32), np.ascontiguousarray(material_index, np.uint32)
+        n = len(kinds)
+        if n == 0:
+            return self.update_flat(first, np.zeros(0, _RECORD), mode)
+        if self._resident is None:
+            objs, _, _ = self._scene.flatten()
+            self._resident = np.frombuffer(objs, dtype=_RECORD)[["kind", "material"]].copy()
+        if first < 0 or first + n > len(self._resident):
+            raise AmberError(f"update_objects: objects [{first}, {first + n}) are not all in the scene ({len(self._resident)} objects)")
+        resident = self._resident[first:first + n]
+        if not np.array_equal(resident["kind"], kinds):
+            raise AmberError(f"update_objects: object {first + int(np.argmax(resident['kind'] != kinds))}: the kind differs from the resident record's (an update moves geometry only)")
+        pairs = np.unique(np.stack([material_index, resident["material"]], 1), axis=0)
+        if len(np.unique(pairs[:, 0])) != len(pairs) or len(np.unique(pairs[:, 1])) != len(pairs):
+            raise AmberError("update_objects: material_index is not the resident objects' material assignment (an update moves geometry only)")
+        # geometry through the host object model: a pinhole scene of the range with one material; its aperture object is dropped again
+        tmp = HostScene.create_arrays(kinds, np.zeros(n, np.uint32), params, [(MAT_LAMBERTIAN, (0.5, 0.5, 0.5), 0.0)],
+                                      [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1], 0.05, 1.0, 0.01, 0)
+        objs, _, lens = tmp.flatten()
+        flat = np.frombuffer(objs, dtype=_RECORD)
+        keep = np.ones(len(flat), bool)
+        keep[lens.first_blade_object:lens.first_blade_object + lens.n_blades] = False
+        records = flat[keep].copy()
+        tmp.close()
+        assert len(records) == n and np.array_equal(records["kind"], kinds)
+        records["material"] = resident["material"]
+        return self.update_flat(first, records, mode)
+
+    def update_flat(self, first: int, records, mode: int = UPDATE_REFIT, count=None) -> dict:
+        """update_objects with the records as one array of AmberFlatObject (64 bytes each: HostScene.flatten()'s layout).  records=None passes a
+        null pointer with `count` objects."""
+        info = UpdateInfo()
+        ptr, n = None, count or 0
+        if records is not None:
+            records = np.ascontiguousarray(records)
+            assert records.itemsize == C.sizeof(FlatObject)
+            ptr, n = records.ctypes.data, len(records) if count is None else count
+        _check(load_library().amber_hip_pt_update_objects(self._h, first, n, ptr, mode, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in UpdateInfo._fields_}
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

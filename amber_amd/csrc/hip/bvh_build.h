@@ -361,7 +361,7 @@ AMBER_HD inline uint32_t PlaneWordT(float mn, float mx, float gmin, float step) 
 }
 inline uint32_t PlaneWord(float mn, float mx, float gmin, float step) { return PlaneWordT<long double>(mn, mx, gmin, step); }
 AMBER_HD inline uint32_t PlaneWordOutward(float mn, float mx, float gmin, float step) { return PlaneWordT<double>(mn, mx, gmin, step); }
-inline uint32_t EmptyPlaneWord() {                            // min above max: no ray enters
+AMBER_HD inline uint32_t EmptyPlaneWord() {                            // min above max: no ray enters
 #if AMBER_BVH_F16
   return 0x3c00u | (0xbc00u << 16);                           // min +1, max -1
 #else

@@ -46,6 +46,8 @@ struct Reduced {                 // keys (FloatKey) of running minima / maxima; 
   uint32_t cen_mn[3], cen_mx[3];   // their centres
   uint32_t depth;                  // inner nodes on the longest way from the root to a leaf (db_boxes)
   uint32_t n_live;                 // inner nodes that survive the leaf collapse (db_count)
+  uint32_t rmin;                   // key of the smallest |radius| over the spheres (3.0e38 without one): SetBvhRayMargin
+  uint32_t bad_index;              // amber_hip_pt_update_objects: the first object whose new record may not replace the resident one (kNoParent: none)
 };
 
 __global__ void db_init(Reduced* r) {
@@ -54,7 +56,7 @@ __global__ void db_init(Reduced* r) {
     r->raw_mn[threadIdx.x] = hi; r->raw_mx[threadIdx.x] = lo; r->wid_mn[threadIdx.x] = hi; r->wid_mx[threadIdx.x] = lo;
     r->cen_mn[threadIdx.x] = hi; r->cen_mx[threadIdx.x] = lo;
   }
-  if (threadIdx.x == 0) { r->depth = 0; r->n_live = 0; }
+  if (threadIdx.x == 0) { r->depth = 0; r->n_live = 0; r->rmin = FloatKey(3.0e38f); r->bad_index = kNoParent; }
 }
 
 // min / max over the wave (every lane takes part: the callers keep out-of-range threads alive with neutral values), then one atomic per wave.
@@ -77,8 +79,15 @@ __device__ __forceinline__ void ReduceBounds(const float mn[3], const float mx[3
 __global__ void __launch_bounds__(256) db_bounds_raw(const DevObject* __restrict__ objs, uint32_t n, Reduced* r) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   Box b; b.reset();
-  if (i < n) b = amber_bvh::ObjectBox(objs[i]);
+  float radius = 3.0e38f;                                      // std::min(rmin, |radius|) as the host folds it: a NaN or an infinity never becomes the minimum
+  if (i < n) {
+    b = amber_bvh::ObjectBox(objs[i]);
+    if ((objs[i].kind & 0xffu) == 1u && fabsf(objs[i].radius) < 3.0e38f) radius = fabsf(objs[i].radius);
+  }
   ReduceBounds(b.mn, b.mx, i < n, r->raw_mn, r->raw_mx);
+  uint32_t key = FloatKey(radius);
+  for (int o = 32; o > 0; o >>= 1) { const uint32_t a = static_cast<uint32_t>(__shfl_xor(static_cast<int>(key), o)); key = a < key ? a : key; }
+  if ((threadIdx.x & 63u) == 0u && key != FloatKey(3.0e38f)) atomicMin(&r->rmin, key);
 }
 
 // The scene figures BuildBvh derives from the geometric bounds: 16 eps D^2 (sphere slack) and D (triangle reach)
@@ -264,7 +273,7 @@ __global__ void __launch_bounds__(256) db_gather(const DevObject* __restrict__ o
   if (k >= n) return;
   const uint32_t scene_index = sorted_index[k];
   const DevObject ob = objs[scene_index];
-  prims[k] = scene_index;
+  if (prims) prims[k] = scene_index;                         // (null: a refit gathers through the leaf order it keeps)
   leaf_objects[k] = ob;
   const uint32_t kind = ob.kind & 0xffu;
   leaf_spheres[k] = kind == 1u ? make_float4(ob.a[0], ob.a[1], ob.a[2], ob.radius) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -276,80 +285,22 @@ __global__ void __launch_bounds__(256) db_gather(const DevObject* __restrict__ o
   }
 }
 
-// A buffer of the finished tree: owned by the handle like the arrays create uploads
-template <typename T, typename P>
-hipError_t OwnedArray(amber_hip_pt* h, size_t count, P& dst) {
-  DevBuf<uint8_t> b;
-  const hipError_t e = b.alloc(count * sizeof(T));
-  if (e == hipSuccess) { dst = reinterpret_cast<T*>(b.p); h->scene_arrays.push_back(std::move(b)); }
-  return e;
-}
+// What the build needs to know of the scene besides the device records: figures of the object KINDS (which an update never changes) and the
+// smallest sphere radius when the caller has it (create: from the host records; an update: db_bounds_raw reduces it).
+struct BuildInput {
+  const DevObject* objs; uint32_t n;
+  bool any_tri, has_spheres, rmin_known; float rmin;
+  uint32_t small_kinds[3];         // kinds of the first three objects (a scene that is one leaf)
+  bool prepared;                   // the caller has run db_init on the scratch's Reduced and enqueued what writes objs (and may set bad_index)
+};
+constexpr uint32_t kReasonRejected = 0xffu;   // internal to an update: Reduced.bad_index names a record that was refused
+struct BuildResult { uint32_t reason, n_nodes, depth; Reduced red; };
 
-}  // namespace dbuild
-
-// Builds the tree of the n objects at h->scene.objects (already on the device) into the handle.  *reason != 0 on return: nothing of the handle
-// was changed and the caller builds on the host (AMBER_BUILD_REASON_*).  objs: the same records on the host (kinds and radii only are read).
-int DeviceBuildBvh(amber_hip_pt* h, const std::vector<DevObject>& objs, uint32_t* reason, uint32_t* out_nodes, uint32_t* out_depth) {
-  using namespace dbuild;
-  *reason = AMBER_BUILD_REASON_NONE;
-  const uint32_t n = static_cast<uint32_t>(objs.size()), n_inner = n - 1u;
-  const uint32_t kLeaf = static_cast<uint32_t>(amber_bvh::kLeafSize);
-  const bool tree = n > kLeaf;                               // else the whole scene is one leaf
-  const hipStream_t st = h->stream;
-  const dim3 by_object((n + 255u) / 256u), by_node((n_inner + 255u) / 256u), wg(256);
-  double slack_factor = 16.0;
-  if (const char* env = std::getenv("AMBER_BVH_SPHERE_SLACK")) slack_factor = std::atof(env);   // BuildBvh's test hook
-
-  // scratch of the build, released on return
-  DevBuf<Reduced> d_red; DevBuf<Box> d_boxes; DevBuf<unsigned long long> d_codes, d_codes_sorted; DevBuf<uint32_t> d_index, d_sorted; DevBuf<uint8_t> d_temp;
-  DevBuf<int32_t> d_left, d_right; DevBuf<uint32_t> d_first, d_last, d_parent_node, d_parent_object, d_child_boxes, d_arrivals, d_live, d_rank;
-  HIP_TRY(d_red.alloc(1)); HIP_TRY(d_boxes.alloc(n)); HIP_TRY(d_codes.alloc(n)); HIP_TRY(d_codes_sorted.alloc(n)); HIP_TRY(d_index.alloc(n)); HIP_TRY(d_sorted.alloc(n));
-  size_t temp_bytes = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_codes.p, d_codes_sorted.p, d_index.p, d_sorted.p, n, 0u, 63u, st));
-  size_t scan_bytes = 0;
-  if (tree) {
-    HIP_TRY(d_left.alloc(n_inner)); HIP_TRY(d_right.alloc(n_inner)); HIP_TRY(d_first.alloc(n_inner)); HIP_TRY(d_last.alloc(n_inner));
-    HIP_TRY(d_parent_node.alloc(n_inner)); HIP_TRY(d_parent_object.alloc(n)); HIP_TRY(d_child_boxes.alloc(static_cast<size_t>(n_inner) * 16u));
-    HIP_TRY(d_arrivals.alloc(n_inner)); HIP_TRY(d_live.alloc(n_inner)); HIP_TRY(d_rank.alloc(n_inner));
-    HIP_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, d_live.p, d_rank.p, n_inner, rocprim::plus<uint32_t>(), st));
-  }
-  HIP_TRY(d_temp.alloc(std::max(temp_bytes, scan_bytes)));
-
-  hipLaunchKernelGGL(db_init, dim3(1), dim3(64), 0, st, d_red.p);
-  hipLaunchKernelGGL(db_bounds_raw, by_object, wg, 0, st, h->scene.objects, n, d_red.p);
-  hipLaunchKernelGGL(db_bounds_wide, by_object, wg, 0, st, h->scene.objects, n, d_red.p, slack_factor, d_boxes.p);
-  hipLaunchKernelGGL(db_morton, by_object, wg, 0, st, d_boxes.p, n, d_red.p, d_codes.p, d_index.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(rocprim::radix_sort_pairs(d_temp.p, temp_bytes, d_codes.p, d_codes_sorted.p, d_index.p, d_sorted.p, n, 0u, 63u, st));
-  if (tree) {
-    HIP_TRY(hipMemsetAsync(d_arrivals.p, 0, static_cast<size_t>(n_inner) * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(db_hierarchy, by_node, wg, 0, st, d_codes_sorted.p, n, d_left.p, d_right.p, d_first.p, d_last.p, d_parent_node.p, d_parent_object.p);
-    hipLaunchKernelGGL(db_boxes, by_object, wg, 0, st, d_boxes.p, d_sorted.p, n, d_left.p, d_first.p, d_last.p, d_parent_node.p, d_parent_object.p, d_child_boxes.p, d_arrivals.p, d_red.p);
-    hipLaunchKernelGGL(db_live, by_node, wg, 0, st, d_first.p, d_last.p, n_inner, d_live.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(rocprim::inclusive_scan(d_temp.p, scan_bytes, d_live.p, d_rank.p, n_inner, rocprim::plus<uint32_t>(), st));
-    hipLaunchKernelGGL(db_count, dim3(1), dim3(1), 0, st, d_rank.p, n_inner, d_red.p);
-    HIP_TRY(hipGetLastError());
-  }
-  Reduced red;
-  HIP_TRY(hipMemcpyAsync(&red, d_red.p, sizeof red, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-
-  float bmn[3], bmx[3];
-  for (int c = 0; c < 3; c++) { bmn[c] = KeyFloat(red.wid_mn[c]); bmx[c] = KeyFloat(red.wid_mx[c]); }
-  for (int c = 0; c < 3; c++)
-    if (!(std::fabs(bmn[c]) < 3.0e38f && std::fabs(bmx[c]) < 3.0e38f && bmn[c] <= bmx[c])) { *reason = AMBER_BUILD_REASON_BOUNDS; return AMBER_OK; }
-  const uint32_t depth = tree ? red.depth : 0u, n_nodes = tree ? red.n_live : 0u;
-  const uint32_t max_depth = h->env.test_device_build_max_depth ? std::min(h->env.test_device_build_max_depth, static_cast<uint32_t>(amber_bvh::kMaxDepth))
-                                                                : static_cast<uint32_t>(amber_bvh::kMaxDepth);
-  if (depth > max_depth) { *reason = AMBER_BUILD_REASON_DEPTH; return AMBER_OK; }   // never traversed: the stacks assume the limit
-  if (tree && (n_nodes == 0u || n_nodes > n_inner)) return Fail(AMBER_EHIP, "device BVH build: inconsistent node count " + std::to_string(n_nodes));
-
-  // the grid of the plane words.  Every child box lies inside the bounds of all widened boxes and PadBox is monotone (a box inside another is
-  // padded by no more, from no smaller a minimum), so the padded bounds contain every padded child box: the grid QuantizeBvh derives from the
-  // node boxes themselves is at most that large.
+// The grid of the plane words, as QuantizedBvh's fields.  Every child box lies inside the bounds of all widened boxes and PadBox is monotone (a
+// box inside another is padded by no more, from no smaller a minimum), so the padded bounds contain every padded child box: the grid QuantizeBvh
+// derives from the node boxes themselves is at most that large.
+inline Grid GridOfBounds(const float bmn[3], const float bmx[3], bool tree, DevScene& sc) {
   Grid g{};
-  DevScene& sc = h->scene;
   Box all; for (int c = 0; c < 3; c++) { all.mn[c] = bmn[c]; all.mx[c] = bmx[c]; }
   g.extent = std::max(all.mx[0] - all.mn[0], std::max(all.mx[1] - all.mn[1], all.mx[2] - all.mn[2]));
   if (tree) {
@@ -364,34 +315,104 @@ int DeviceBuildBvh(amber_hip_pt* h, const std::vector<DevObject>& objs, uint32_t
   } else {
     for (int c = 0; c < 3; c++) { sc.bvh_gmin[c] = 0.f; sc.bvh_step[c] = 1.f; sc.bvh_reach[c] = 0.f; }           // QuantizedBvh's defaults: no node reads them
   }
-  bool any_tri = false, has_spheres = false; float rmin = 3.0e38f;
-  for (const DevObject& o : objs) {
-    const uint32_t kind = o.kind & 0xffu;
-    any_tri = any_tri || kind == AMBER_PRIM_TRIANGLE;
-    if (kind == AMBER_PRIM_SPHERE) { has_spheres = true; rmin = std::min(rmin, std::fabs(o.radius)); }
-  }
-  amber_prep::SetBvhRayMargin(sc, bmn, bmx, has_spheres, has_spheres ? rmin : 0.0f);
+  return g;
+}
+inline bool FiniteBounds(const Reduced& red, float bmn[3], float bmx[3]) {
+  for (int c = 0; c < 3; c++) { bmn[c] = KeyFloat(red.wid_mn[c]); bmx[c] = KeyFloat(red.wid_mx[c]); }
+  for (int c = 0; c < 3; c++)
+    if (!(std::fabs(bmn[c]) < 3.0e38f && std::fabs(bmx[c]) < 3.0e38f && bmn[c] <= bmx[c])) return false;
+  return true;
+}
 
-  // the + 1 / + 3: no array is empty on the device, as in create's uploads
-  DevBvhNodeQ* d_nodes = nullptr; uint32_t* d_prims = nullptr; DevObject* d_leaf_objects = nullptr; float4* d_spheres = nullptr; float4* d_tris = nullptr;
-  HIP_TRY(OwnedArray<DevBvhNodeQ>(h, n_nodes + 1u, d_nodes));
-  HIP_TRY(OwnedArray<uint32_t>(h, n + 1u, d_prims));
-  HIP_TRY(OwnedArray<float4>(h, (any_tri ? 3u * static_cast<size_t>(n) : 0u) + 3u, d_tris));
-  HIP_TRY(OwnedArray<DevObject>(h, n + 1u, d_leaf_objects));
-  HIP_TRY(OwnedArray<float4>(h, n + 1u, d_spheres));
-  if (tree) hipLaunchKernelGGL(db_emit, by_node, wg, 0, st, h->scene.objects, d_sorted.p, n_inner, d_left.p, d_right.p, d_first.p, d_last.p, d_rank.p, d_child_boxes.p, g, d_nodes, n_nodes);
-  hipLaunchKernelGGL(db_gather, by_object, wg, 0, st, h->scene.objects, d_sorted.p, n, d_prims, d_leaf_objects, d_spheres, any_tri ? d_tris : nullptr);
+}  // namespace dbuild
+
+// Builds the tree of the in.n objects at in.objs (device memory) into the handle's arrays (h->tree; the node array is replaced when the tree has
+// more nodes than it holds, the others are allocated once) and sets the DevScene fields that describe it.  res->reason != 0 on return: nothing
+// of the handle was changed (create then builds on the host, an update refits or refuses).
+int DeviceBuildBvh(amber_hip_pt* h, const dbuild::BuildInput& in, BvhBuildScratch& s, dbuild::BuildResult* res) {
+  using namespace dbuild;
+  res->reason = AMBER_BUILD_REASON_NONE;
+  const uint32_t n = in.n, n_inner = n - 1u;
+  const uint32_t kLeaf = static_cast<uint32_t>(amber_bvh::kLeafSize);
+  const bool tree = n > kLeaf;                               // else the whole scene is one leaf
+  const hipStream_t st = h->stream;
+  const dim3 by_object((n + 255u) / 256u), by_node((n_inner + 255u) / 256u), wg(256);
+  double slack_factor = 16.0;
+  if (const char* env = std::getenv("AMBER_BVH_SPHERE_SLACK")) slack_factor = std::atof(env);   // BuildBvh's test hook
+
+  HIP_TRY(s.red.need(1)); HIP_TRY(s.boxes.need(n)); HIP_TRY(s.codes.need(n)); HIP_TRY(s.codes_sorted.need(n)); HIP_TRY(s.index.need(n)); HIP_TRY(s.sorted.need(n));
+  size_t temp_bytes = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, s.codes.p, s.codes_sorted.p, s.index.p, s.sorted.p, n, 0u, 63u, st));
+  size_t scan_bytes = 0;
+  if (tree) {
+    HIP_TRY(s.left.need(n_inner)); HIP_TRY(s.right.need(n_inner)); HIP_TRY(s.first.need(n_inner)); HIP_TRY(s.last.need(n_inner));
+    HIP_TRY(s.parent_node.need(n_inner)); HIP_TRY(s.parent_object.need(n)); HIP_TRY(s.child_boxes.need(static_cast<size_t>(n_inner) * 16u));
+    HIP_TRY(s.arrivals.need(n_inner)); HIP_TRY(s.live.need(n_inner)); HIP_TRY(s.rank.need(n_inner));
+    HIP_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, s.live.p, s.rank.p, n_inner, rocprim::plus<uint32_t>(), st));
+  }
+  HIP_TRY(s.temp.need(std::max(temp_bytes, scan_bytes)));
+
+  if (!in.prepared) hipLaunchKernelGGL(db_init, dim3(1), dim3(64), 0, st, s.red.p);
+  hipLaunchKernelGGL(db_bounds_raw, by_object, wg, 0, st, in.objs, n, s.red.p);
+  hipLaunchKernelGGL(db_bounds_wide, by_object, wg, 0, st, in.objs, n, s.red.p, slack_factor, s.boxes.p);
+  hipLaunchKernelGGL(db_morton, by_object, wg, 0, st, s.boxes.p, n, s.red.p, s.codes.p, s.index.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim::radix_sort_pairs(s.temp.p, temp_bytes, s.codes.p, s.codes_sorted.p, s.index.p, s.sorted.p, n, 0u, 63u, st));
+  if (tree) {
+    HIP_TRY(hipMemsetAsync(s.arrivals.p, 0, static_cast<size_t>(n_inner) * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(db_hierarchy, by_node, wg, 0, st, s.codes_sorted.p, n, s.left.p, s.right.p, s.first.p, s.last.p, s.parent_node.p, s.parent_object.p);
+    hipLaunchKernelGGL(db_boxes, by_object, wg, 0, st, s.boxes.p, s.sorted.p, n, s.left.p, s.first.p, s.last.p, s.parent_node.p, s.parent_object.p, s.child_boxes.p, s.arrivals.p, s.red.p);
+    hipLaunchKernelGGL(db_live, by_node, wg, 0, st, s.first.p, s.last.p, n_inner, s.live.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rocprim::inclusive_scan(s.temp.p, scan_bytes, s.live.p, s.rank.p, n_inner, rocprim::plus<uint32_t>(), st));
+    hipLaunchKernelGGL(db_count, dim3(1), dim3(1), 0, st, s.rank.p, n_inner, s.red.p);
+    HIP_TRY(hipGetLastError());
+  }
+  Reduced& red = res->red;
+  HIP_TRY(hipMemcpyAsync(&red, s.red.p, sizeof red, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+
+  if (red.bad_index != kNoParent) { res->reason = kReasonRejected; return AMBER_OK; }
+  float bmn[3], bmx[3];
+  if (!FiniteBounds(red, bmn, bmx)) { res->reason = AMBER_BUILD_REASON_BOUNDS; return AMBER_OK; }
+  const uint32_t depth = tree ? red.depth : 0u, n_nodes = tree ? red.n_live : 0u;
+  const uint32_t max_depth = h->env.test_device_build_max_depth ? std::min(h->env.test_device_build_max_depth, static_cast<uint32_t>(amber_bvh::kMaxDepth))
+                                                                : static_cast<uint32_t>(amber_bvh::kMaxDepth);
+  if (depth > max_depth) { res->reason = AMBER_BUILD_REASON_DEPTH; return AMBER_OK; }   // never traversed: the stacks assume the limit
+  if (tree && (n_nodes == 0u || n_nodes > n_inner)) return Fail(AMBER_EHIP, "device BVH build: inconsistent node count " + std::to_string(n_nodes));
+
+  // the arrays first (the + 1 / + 3: no array is empty on the device, as in create's uploads): a failure here leaves the handle as it was.  The
+  // arrays may be in use by passes enqueued earlier; everything below is ordered behind them on the handle's stream, and the stream has just been waited for.
+  // A node array that is too small is not replaced before everything that can fail has been enqueued: until then the handle's tree stands.
+  BvhTreeBufs& t = h->tree;
+  DevBuf<uint8_t> larger_nodes;
+  const bool grow_nodes = !t.nodes.p || t.nodes.n < (n_nodes + 1u) * sizeof(DevBvhNodeQ);
+  if (grow_nodes) HIP_TRY(larger_nodes.alloc((n_nodes + 1u) * sizeof(DevBvhNodeQ)));
+  HIP_TRY(t.prims.need((n + 1u) * sizeof(uint32_t)));
+  HIP_TRY(t.tris.need(((in.any_tri ? 3u * static_cast<size_t>(n) : 0u) + 3u) * sizeof(float4)));
+  HIP_TRY(t.objects.need((n + 1u) * sizeof(DevObject)));
+  HIP_TRY(t.spheres.need((n + 1u) * sizeof(float4)));
+  DevBvhNodeQ* d_nodes = reinterpret_cast<DevBvhNodeQ*>(grow_nodes ? larger_nodes.p : t.nodes.p); uint32_t* d_prims = reinterpret_cast<uint32_t*>(t.prims.p);
+  DevObject* d_leaf_objects = reinterpret_cast<DevObject*>(t.objects.p); float4* d_spheres = reinterpret_cast<float4*>(t.spheres.p); float4* d_tris = reinterpret_cast<float4*>(t.tris.p);
+
+  DevScene& sc = h->scene;
+  const Grid g = GridOfBounds(bmn, bmx, tree, sc);
+  amber_prep::SetBvhRayMargin(sc, bmn, bmx, in.has_spheres, in.has_spheres ? (in.rmin_known ? in.rmin : KeyFloat(red.rmin)) : 0.0f);
+
+  if (tree) hipLaunchKernelGGL(db_emit, by_node, wg, 0, st, in.objs, s.sorted.p, n_inner, s.left.p, s.right.p, s.first.p, s.last.p, s.rank.p, s.child_boxes.p, g, d_nodes, n_nodes);
+  hipLaunchKernelGGL(db_gather, by_object, wg, 0, st, in.objs, s.sorted.p, n, d_prims, d_leaf_objects, d_spheres, in.any_tri ? d_tris : nullptr);
   HIP_TRY(hipGetLastError());
   if (tree) sc.bvh_root = 0;
   else {                                                     // one leaf over the sorted order: read it back (at most kLeafSize words) for the leaf's kind bits
     uint32_t order[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(order, d_sorted.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(order, s.sorted.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    sc.bvh_root = amber_bvh::QuantizedLeafRef(amber_bvh::Builder::LeafRef(0u, n), [&](uint32_t slot) { return objs[order[slot]].kind & 0xffu; });
+    sc.bvh_root = amber_bvh::QuantizedLeafRef(amber_bvh::Builder::LeafRef(0u, n), [&](uint32_t slot) { return in.small_kinds[order[slot] < 3u ? order[slot] : 0u]; });
   }
-  HIP_TRY(hipStreamSynchronize(st));                          // the scratch buffers go out of scope here
+  if (!in.prepared) HIP_TRY(hipStreamSynchronize(st));        // create's scratch goes out of scope when it returns; an update keeps its scratch and waits once, at its end
+  if (grow_nodes) { t.nodes.swap(larger_nodes); s.retired_nodes.swap(larger_nodes); }   // (what retired_nodes held before is released here: an update has waited for the stream since)
   sc.bvh_nodes = d_nodes; sc.bvh_prims = d_prims; sc.bvh_tris = d_tris; sc.bvh_objects = d_leaf_objects; sc.bvh_spheres = d_spheres;
-  *out_nodes = n_nodes; *out_depth = depth;
+  res->n_nodes = n_nodes; res->depth = depth;
   return AMBER_OK;
 }
 

@@ -10,6 +10,8 @@
 //                          sums, reduce_partials_kernel.
 //   bvh_device_build.inc   AMBER_PT_FLAG_DEVICE_BUILD: engine BVH's tree built by kernels at create (Morton order, radix-tree hierarchy, the host builder's
 //                          bounds / padding / outward binary16 planes) instead of bvh_build.h's binned-SAH build on the host.
+//   bvh_update.inc         amber_hip_pt_update_objects: new object geometry into a live handle -- records converted and checked by a kernel, then the
+//                          tree made valid again on the device: refitted (any tree, topology kept) or rebuilt (the Morton tree, in place).
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -91,6 +93,15 @@ struct DevBuf {
     if (e != hipSuccess) p = nullptr; else n = count;
     return e;
   }
+  void swap(DevBuf& o) noexcept { std::swap(p, o.p); std::swap(n, o.n); }
+  // at least `count` elements, contents not kept; what the buffer held stays untouched when the allocation fails
+  hipError_t need(size_t count) {
+    if (p && n >= count) return hipSuccess;
+    DevBuf bigger;
+    const hipError_t e = bigger.alloc(count);
+    if (e == hipSuccess) swap(bigger);
+    return e;
+  }
   operator T*() const { return p; }
 };
 // An event, a stream or pinned host memory, released with kRelease.
@@ -108,6 +119,24 @@ using Event = Owned<hipEvent_t, hipEventDestroy>;
 #include "scene_prep.h"
 using amber_prep::kHitTwoPhaseN;
 
+namespace {
+namespace dbuild { struct Reduced; }
+// Engine BVH's arrays on the device (DevScene.bvh_* point into them), owned by the handle by name: amber_hip_pt_update_objects rewrites them in
+// place and replaces the node array when a rebuilt tree has more nodes.
+struct BvhTreeBufs { DevBuf<uint8_t> nodes, prims, tris, objects, spheres; };
+// Scratch of the device build (bvh_device_build.inc) and of the refit (bvh_update.inc).  Create's is local and released when create returns; a
+// handle that is updated keeps one, so that an update in the steady state allocates nothing.
+struct BvhBuildScratch {
+  DevBuf<dbuild::Reduced> red; DevBuf<amber_bvh::Box> boxes; DevBuf<unsigned long long> codes, codes_sorted; DevBuf<uint32_t> index, sorted; DevBuf<uint8_t> temp;
+  DevBuf<int32_t> left, right; DevBuf<uint32_t> first, last, parent_node, parent_object, child_boxes, arrivals, live, rank;
+  DevBuf<AmberFlatObject> staged;           // update: the caller's records
+  DevBuf<uint32_t> refit_parent;            // refit: parent * 2 + side of every node of the tree in use; valid while the topology stands
+  bool refit_parent_valid = false;
+  DevBuf<double> area;                      // update: {sum of the child boxes' areas, the root's area} of the tree before and after
+  DevBuf<uint8_t> retired_nodes;            // a node array a rebuild has outgrown: passes enqueued earlier may still read it, released once the stream has been waited for
+};
+}  // namespace
+
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
@@ -116,7 +145,24 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   Owned<hipStream_t, hipStreamDestroy> own_stream;   // the stream create made, if any: declared first, so released after every buffer below
   hipStream_t stream = nullptr;             // the render stream: own_stream, the caller's or the legacy default stream
   amber_prep::EnvSwitches env;              // the environment switches, read once at create
-  std::vector<DevBuf<uint8_t>> scene_arrays;   // the scene's arrays uploaded at create (scene.objects ... scene.lens point into them)
+  std::vector<DevBuf<uint8_t>> scene_arrays;   // the scene's arrays uploaded at create (scene.materials ... scene.lens point into them)
+  DevBuf<uint8_t> objects_buf;              // scene.objects
+  BvhTreeBufs tree;                         // engine BVH's arrays
+  // ---- amber_hip_pt_update_objects (bvh_update.inc)
+  DevBuf<uint8_t> objects_alt;              // the object array the next update fills: an update commits by exchanging it with objects_buf
+  BvhBuildScratch update_scratch;
+  uint32_t create_flags = 0;                // AmberPtParams.reserved
+  size_t n_triangles = 0;                   // kinds never change under an update: what ChooseBvhScheduler and the leaf arrays need of them
+  bool has_spheres = false;
+  uint32_t small_kinds[3] = {0, 0, 0};      // kinds of a scene that is one leaf
+  uint32_t first_blade = 0;
+  std::vector<AmberFlatObject> blade_records;   // the aperture blades as create received them (an update must leave them as they are)
+  std::vector<uint32_t> light_object;       // object of every light, and its parameters as the lights table was computed from them
+  std::vector<float> light_p;
+  bool lights_stale = false;                // an update has changed an object the lights table names: light tracing needs a new handle
+  bool area_known = false;
+  float tree_area = 0;                      // AmberUpdateInfo.area_after of the tree in use
+  double area_host[4] = {0, 0, 0, 0};       // where the two area measurements of an update are copied to
   DevBuf<uint2> d_ref_stack;                // engine REFERENCE_BVH: the traversal stack of the reference's tree, [level][thread of the largest grid]
   DevBuf<float> d_fb;
   DevBuf<unsigned long long> d_rays;
@@ -159,6 +205,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
 };
 
 #include "bvh_device_build.inc"
+#include "bvh_update.inc"
 
 namespace {
 
@@ -200,11 +247,17 @@ int ValidateScene(const AmberFlatScene* s, const AmberSensor* sensor) {
 
 // A device copy of v, `extra` elements longer, owned by the handle; the DevScene pointer dst points to it
 template <typename T, typename P>
-hipError_t Upload(amber_hip_pt* h, const std::vector<T>& v, size_t extra, P& dst) {
-  DevBuf<uint8_t> b;
+hipError_t UploadTo(DevBuf<uint8_t>& b, const std::vector<T>& v, size_t extra, P& dst) {
   hipError_t e = b.alloc((v.size() + extra) * sizeof(T));
   if (e == hipSuccess && !v.empty()) e = hipMemcpy(b, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  if (e == hipSuccess) { dst = reinterpret_cast<T*>(b.p); h->scene_arrays.push_back(std::move(b)); }
+  if (e == hipSuccess) dst = reinterpret_cast<T*>(b.p);
+  return e;
+}
+template <typename T, typename P>
+hipError_t Upload(amber_hip_pt* h, const std::vector<T>& v, size_t extra, P& dst) {
+  DevBuf<uint8_t> b;
+  const hipError_t e = UploadTo(b, v, extra, dst);
+  if (e == hipSuccess) h->scene_arrays.push_back(std::move(b));
   return e;
 }
 
@@ -266,7 +319,19 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
 
   // ---- upload (the + 1 / + 3: no array is empty on the device)
   DevScene& sc = h->scene;
-  HIP_TRY(Upload(h.get(), p.objects, 0, sc.objects));
+  HIP_TRY(UploadTo(h->objects_buf, p.objects, 0, sc.objects));
+  h->create_flags = params->reserved;
+  h->n_triangles = amber_prep::CountTriangles(p.objects);
+  for (size_t i = 0; i < p.objects.size(); i++) {
+    h->has_spheres = h->has_spheres || (p.objects[i].kind & 0xffu) == AMBER_PRIM_SPHERE;
+    if (i < 3) h->small_kinds[i] = p.objects[i].kind & 0xffu;
+  }
+  h->first_blade = s->lens.first_blade_object;
+  h->blade_records.assign(s->objects + s->lens.first_blade_object, s->objects + s->lens.first_blade_object + s->lens.n_blades);
+  for (uint32_t i = 0; i < s->n_lights; i++) {
+    h->light_object.push_back(s->lights[i].object);
+    h->light_p.insert(h->light_p.end(), s->objects[s->lights[i].object].p, s->objects[s->lights[i].object].p + 12);
+  }
   HIP_TRY(Upload(h.get(), p.materials, 0, sc.materials));
   HIP_TRY(Upload(h.get(), p.blades, 0, sc.blades));
   HIP_TRY(Upload(h.get(), p.planes, 1, sc.planes));
@@ -280,7 +345,18 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
     // that cannot be built (no finite bounds) is replaced by the host's: same arrays, same upload as without the flag.
     const auto t_tree = std::chrono::steady_clock::now();
     uint32_t reason = AMBER_BUILD_REASON_NONE, n_nodes = 0, depth = 0;
-    { const int rc_build = DeviceBuildBvh(h.get(), p.objects, &reason, &n_nodes, &depth); if (rc_build != AMBER_OK) return rc_build; }
+    {
+      BvhBuildScratch scratch;                                   // released when this block ends
+      dbuild::BuildInput in{};
+      in.objs = sc.objects; in.n = static_cast<uint32_t>(p.objects.size()); in.any_tri = h->n_triangles != 0; in.has_spheres = h->has_spheres;
+      in.rmin_known = true; in.rmin = 3.0e38f;
+      for (const DevObject& o : p.objects) if ((o.kind & 0xffu) == AMBER_PRIM_SPHERE) in.rmin = std::min(in.rmin, std::fabs(o.radius));
+      for (int k = 0; k < 3; k++) in.small_kinds[k] = h->small_kinds[k];
+      dbuild::BuildResult res{};
+      const int rc_build = DeviceBuildBvh(h.get(), in, scratch, &res);
+      if (rc_build != AMBER_OK) return rc_build;
+      reason = res.reason; n_nodes = res.n_nodes; depth = res.depth;
+    }
     if (reason == AMBER_BUILD_REASON_NONE) {
       amber_prep::ChooseBvhScheduler(*h, p.objects, params, env, n_nodes, depth, AMBER_PATH_BVH_STACK, AMBER_BVH_SHADE_BATCH);
       h->build.where = AMBER_BUILD_DEVICE; h->build.n_nodes = n_nodes; h->build.n_leaves = n_nodes + 1u; h->build.depth = depth;
@@ -294,14 +370,14 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
   }
   if (h->build.where != AMBER_BUILD_DEVICE) {
     const auto t_upload = std::chrono::steady_clock::now();
-    HIP_TRY(Upload(h.get(), p.bvh_nodes, 1, sc.bvh_nodes));
+    HIP_TRY(UploadTo(h->tree.nodes, p.bvh_nodes, 1, sc.bvh_nodes));
 #if AMBER_BVH_WIDE
     HIP_TRY(Upload(h.get(), p.bvh_nodes4, 1, sc.bvh_nodes4));
 #endif
-    HIP_TRY(Upload(h.get(), p.bvh_prims, 1, sc.bvh_prims));
-    HIP_TRY(Upload(h.get(), p.bvh_tris, 3, sc.bvh_tris));
-    HIP_TRY(Upload(h.get(), p.bvh_objects, 1, sc.bvh_objects));
-    HIP_TRY(Upload(h.get(), p.bvh_spheres, 1, sc.bvh_spheres));
+    HIP_TRY(UploadTo(h->tree.prims, p.bvh_prims, 1, sc.bvh_prims));
+    HIP_TRY(UploadTo(h->tree.tris, p.bvh_tris, 3, sc.bvh_tris));
+    HIP_TRY(UploadTo(h->tree.objects, p.bvh_objects, 1, sc.bvh_objects));
+    HIP_TRY(UploadTo(h->tree.spheres, p.bvh_spheres, 1, sc.bvh_spheres));
     if (h->hit_engine == AMBER_ENGINE_BVH) h->build.tree_ms += ms_since(t_upload);
   }
   HIP_TRY(Upload(h.get(), std::vector<DevLens>{p.lens}, 0, sc.lens));
@@ -742,6 +818,7 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   *n_out = 0;
   if (ray_count) *ray_count = 0;
   if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, "light tracing runs on the work-queue kernel (engine auto, list, two_phase or bvh)");
+  if (h->lights_stale) return Fail(AMBER_EINVAL, "lights are stale after amber_hip_pt_update_objects: re-create the handle");
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
   const uint32_t all_paths = h->scene.sensor.w * h->scene.sensor.h;          // image.Size() light paths per pass
   if (path_begin > path_end || path_end > all_paths) return Fail(AMBER_EINVAL, "bad light-path range");
@@ -869,6 +946,15 @@ int amber_hip_pt_local_rows(amber_hip_pt* h, uint32_t* n_rows) {
   if (!h || !n_rows) return Fail(AMBER_EINVAL, "null argument");
   *n_rows = h->local_rows;
   return AMBER_OK;
+}
+
+int amber_hip_pt_update_objects(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode, AmberUpdateInfo* info) {
+  if (!h) return Fail(AMBER_EINVAL, "null handle");
+  try {
+    return UpdateObjects(h, first, count, objects, mode, info);
+  } catch (const std::bad_alloc&) {
+    return Fail(AMBER_ENOMEM, "amber_hip_pt_update_objects: out of host memory");
+  }
 }
 
 int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) {

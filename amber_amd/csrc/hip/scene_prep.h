@@ -78,22 +78,29 @@ struct SceneState {
 };
 
 // Engine BVH's scheduler and shading batch, from the depth of its tree -- whoever built it.
-inline void ChooseBvhScheduler(SceneState& st, const std::vector<DevObject>& objs, const AmberPtParams* params, const EnvSwitches& env,
+// (n_objects, n_triangles, flags: what the choice needs of the scene and of AmberPtParams.reserved -- a handle keeps them, so that a tree rebuilt
+//  by amber_hip_pt_update_objects chooses again without the host's object records)
+inline void ChooseBvhScheduler(SceneState& st, size_t n_objects, size_t n_triangles, uint32_t flags, const EnvSwitches& env,
                                size_t n_nodes, uint32_t depth, uint32_t path_bvh_stack, uint32_t shade_batch) {
-  st.bvh_paths = !st.bvh_pool && !(params->reserved & AMBER_PT_FLAG_BVH_ITEMS) && st.engine != AMBER_ENGINE_WAVEFRONT && depth <= path_bvh_stack;
+  st.bvh_paths = !st.bvh_pool && !(flags & AMBER_PT_FLAG_BVH_ITEMS) && st.engine != AMBER_ENGINE_WAVEFRONT && depth <= path_bvh_stack;
   // The shading batch of pt_bvh_megakernel.  While a wave collects finished lanes they idle through the rounds of the others, and a round
   // over triangle leaves costs about twice a round over sphere leaves (45 against 20 vector instructions per leaf object before any
   // root / quotient), so idle lanes are dearer in a mesh: tools/shade_batch_sweep.py (profiles/r05_shade_batch_sweep.txt) -- 1M spheres
   // best at 52 (49.7 ms at 64 spp; 40: 52.3), 1M-triangle terrain at 32 (62.1; 40: 63.8; 52: 68.5), 82k-triangle room at 36-44 (32.8; 52: 33.9).
-  {
-    size_t n_triangles = 0;                                   // (every scene has a few: the aperture blades)
-    for (const DevObject& ob : objs) n_triangles += (ob.kind & 0xffu) == AMBER_PRIM_TRIANGLE ? 1u : 0u;
-    st.bvh_shade_batch = 2u * n_triangles > objs.size() ? 40u : shade_batch;   // a mesh: 40; mostly spheres (disks, cylinders): 52
-  }
+  st.bvh_shade_batch = 2u * n_triangles > n_objects ? 40u : shade_batch;   // a mesh: 40; mostly spheres (disks, cylinders): 52
   if (env.bvh_shade_batch) st.bvh_shade_batch = env.bvh_shade_batch;
   if (env.bvh_paths_off || env.bvh_paths_max_depth < depth) st.bvh_paths = false;
-  if (env.debug_bvh) std::fprintf(stderr, "amber_hip: BVH of %zu objects: %zu nodes, depth %u; scheduler %s, shading batch %u\n", objs.size(), n_nodes, depth,
+  if (env.debug_bvh) std::fprintf(stderr, "amber_hip: BVH of %zu objects: %zu nodes, depth %u; scheduler %s, shading batch %u\n", n_objects, n_nodes, depth,
                                   st.bvh_pool ? "pt_bvh_pool_kernel" : (st.bvh_paths ? "pt_megakernel<ENGINE_BVH>" : "pt_bvh_megakernel"), st.bvh_shade_batch);
+}
+inline size_t CountTriangles(const std::vector<DevObject>& objs) {   // (every scene has a few: the aperture blades)
+  size_t n_triangles = 0;
+  for (const DevObject& ob : objs) n_triangles += (ob.kind & 0xffu) == AMBER_PRIM_TRIANGLE ? 1u : 0u;
+  return n_triangles;
+}
+inline void ChooseBvhScheduler(SceneState& st, const std::vector<DevObject>& objs, const AmberPtParams* params, const EnvSwitches& env,
+                               size_t n_nodes, uint32_t depth, uint32_t path_bvh_stack, uint32_t shade_batch) {
+  ChooseBvhScheduler(st, objs.size(), CountTriangles(objs), params->reserved, env, n_nodes, depth, path_bvh_stack, shade_batch);
 }
 
 // The host builder (bvh_build.h) and what follows from its tree's depth.

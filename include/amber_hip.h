@@ -31,7 +31,7 @@ extern "C" {
                                     (amber_hip_lab.h); AMBER_PT_FLAG_BVH_ITEMS added.  2 (round 4): lt ranges, stream; a stream-ordered read of
                                     amber_hip_pt_device_framebuffer() needs amber_hip_pt_sync() first when a launch may have run out of record slots.
                                     Still 3 with AMBER_PT_FLAG_DEVICE_BUILD and amber_hip_pt_build_info(): a flag bit that older libraries ignore and
-                                    a new function; nothing that existed changed its layout or meaning */
+                                    a new function; nothing that existed changed its layout or meaning.  Still 3 with amber_hip_pt_update_objects(): a new function */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -198,7 +198,7 @@ int  amber_hip_pt_device_framebuffer(amber_hip_pt*, void** dptr, uint64_t* n_flo
 int  amber_hip_pt_stream(amber_hip_pt*, void** stream);
 /* Number of framebuffer rows this handle owns (after striping). */
 int  amber_hip_pt_local_rows(amber_hip_pt*, uint32_t* n_rows);
-/* Engine BVH's tree as create built it.  Works for every handle. */
+/* Engine BVH's tree as create built it (after amber_hip_pt_update_objects in mode REBUILD: as that call built it).  Works for every handle. */
 enum { AMBER_BUILD_NONE = 0,            /* the handle's engine has no such tree (LIST, TWO_PHASE, REFERENCE_BVH) */
        AMBER_BUILD_HOST = 1, AMBER_BUILD_DEVICE = 2,
        AMBER_BUILD_HOST_FALLBACK = 3 }; /* AMBER_PT_FLAG_DEVICE_BUILD was set, the host built the tree: fallback_reason */
@@ -218,6 +218,40 @@ typedef struct {
   double   create_ms;        /* host wall time of amber_hip_pt_create */
 } AmberBuildInfo;
 int  amber_hip_pt_build_info(amber_hip_pt*, AmberBuildInfo* out);
+/* New geometry for the scene objects [first, first + count) of a live handle (objects[0 .. count), host memory, scene index order), and engine
+ * BVH's tree made valid again on the device.  Afterwards the handle renders what a handle created on the new scene renders, bit for bit (the
+ * answer never depends on the tree).  Still ABI version 3: a new function.
+ *   REFIT    keeps the topology and the leaf order of the tree in use -- whoever built it -- and recomputes every box.  Cheapest; the tree
+ *            degrades as objects move far against their own size (INTEGRATION.md has the measured curve).
+ *   REBUILD  builds the Morton tree again, as AMBER_PT_FLAG_DEVICE_BUILD does at create, into the arrays the handle owns; a host-built tree is
+ *            replaced by it, amber_hip_pt_build_info then reports the new tree.  A Morton tree deeper than the traversal's limit is not used:
+ *            the call refits the tree in use instead and says so (mode_used, fallback_reason).
+ * Geometry only: every new record keeps the kind and the material of the one it replaces, and an aperture blade in the range must equal the
+ * resident record bit for bit (the lens is not part of an update).  Objects with NaN parameters are accepted as create accepts them.
+ * Lights: path tracing does not read the lights table, so emitting objects move like any other; but cum_power and pdf_area were computed by
+ * the caller from the old geometry, so once the record of an object named by an AmberFlatLight has changed, amber_hip_lt_trace / _range
+ * answer AMBER_EINVAL until the handle is re-created.
+ * Engines: only where the closest-hit engine is BVH (AUTO past 80 objects, AMBER_ENGINE_BVH).  LIST, TWO_PHASE (AUTO on small scenes: their
+ * create takes half a millisecond), REFERENCE_BVH (its tree is the reference's, built by the reference's sorts), the lab engine WAVEFRONT and
+ * AMBER_BVH_WIDE measurement builds answer AMBER_EINVAL: re-create the handle.
+ * Cost: always a pass over the WHOLE scene on the device -- the sphere slack and the needle reach of every object's box depend on the scene
+ * diagonal and the plane words on the scene bounds -- only the upload is proportional to count.
+ * Order: stream-ordered after everything enqueued on the handle before it and before everything after; a pass enqueued before renders the
+ * old scene.  The framebuffer and the ray counter are NOT cleared (amber_hip_pt_clear is the caller's decision).  The call waits for the
+ * handle's stream before it returns (twice in all: a small read-back, and the end).  All or nothing: on an AMBER_EINVAL / AMBER_ENOMEM return the
+ * handle renders exactly what it rendered before; after AMBER_EHIP (a HIP runtime call failed half way) the handle is to be destroyed.
+ * count == 0: AMBER_OK, nothing changes. */
+enum { AMBER_UPDATE_REFIT = 0, AMBER_UPDATE_REBUILD = 1 };
+typedef struct {
+  uint32_t mode_used;        /* AMBER_UPDATE_*: what was done */
+  uint32_t fallback_reason;  /* AMBER_BUILD_REASON_DEPTH: a requested REBUILD became a REFIT; 0 otherwise */
+  uint32_t n_nodes, depth;   /* of the tree now in use */
+  float    area_before, area_after; /* of the tree in use before / after the call (equal when count == 0); tree quality: sum over the inner nodes of both child boxes' surface areas / the root's surface area, from the
+                                       planes the traversal reads; informative (summed in arrival order: the last bits vary) */
+  double   update_ms;        /* host wall time of the call, everything it waits for included */
+} AmberUpdateInfo;
+int  amber_hip_pt_update_objects(amber_hip_pt*, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode,
+                                 AmberUpdateInfo* info /* may be NULL */);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);
