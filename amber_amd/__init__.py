@@ -27,6 +27,9 @@ from .api import (  # noqa: F401
     UPDATE_REFIT,
     UPDATE_REBUILD,
     UpdateInfo,
+    RAYS_HOST,
+    Ray,
+    RayHit,
     AmberError,
     FlatMaterial,
     FlatObject,

@@ -77,6 +77,16 @@ class UpdateInfo(C.Structure):
                 ("area_before", C.c_float), ("area_after", C.c_float), ("update_ms", C.c_double)]
 
 
+class Ray(C.Structure):
+    """AmberRay: origin, t_max, dir, pad -- 32 bytes (amber_hip_pt_cast_rays / amber_hip_pt_occluded)."""
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("dir", C.c_float * 3), ("pad", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    """AmberRayHit: t (NaN = miss), object (scene index, -1 = miss), pos, normal -- 32 bytes."""
+    _fields_ = [("t", C.c_float), ("object", C.c_int32), ("pos", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
 class BvhDumpInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_prims", C.c_uint32), ("root", C.c_int32), ("depth", C.c_uint32),
                 ("gmin", C.c_float * 3), ("step", C.c_float * 3), ("reach", C.c_float * 3)]
@@ -95,12 +105,16 @@ PT_FLAG_NULL_STREAM, PT_FLAG_BVH_POOL, PT_FLAG_BVH_ITEMS = 1, 2, 4
 PT_FLAG_DEVICE_BUILD = 8     # engine BVH: create builds the tree on the device (include/amber_hip.h)
 BUILD_NONE, BUILD_HOST, BUILD_DEVICE, BUILD_HOST_FALLBACK = 0, 1, 2, 3
 BUILD_REASON_NONE, BUILD_REASON_DEPTH, BUILD_REASON_WIDE, BUILD_REASON_BOUNDS = 0, 1, 2, 3
+RAYS_HOST = 1                # amber_hip_pt_cast_rays / amber_hip_pt_occluded: rays and output are host pointers
+_RAY = np.dtype([("origin", np.float32, (3,)), ("t_max", np.float32), ("dir", np.float32, (3,)), ("pad", np.uint32)])       # AmberRay
+_RAY_HIT = np.dtype([("t", np.float32), ("object", np.int32), ("pos", np.float32, (3,)), ("normal", np.float32, (3,))])    # AmberRayHit
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1     # amber_hip_pt_update_objects: keep the tree's topology and recompute its boxes / build the Morton tree again
 
 # every symbol include/amber_hip.h and include/amber_host.h declare: what libamber_hip.so (the product) exports
 ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
-    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_destroy",
+    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects",
+    "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_destroy",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -159,6 +173,9 @@ def load_library() -> C.CDLL:
         lib.amber_hip_pt_build_info.argtypes = [vp, C.POINTER(BuildInfo)]
     if hasattr(lib, "amber_hip_pt_update_objects"):
         lib.amber_hip_pt_update_objects.argtypes = [vp, u32, u32, vp, u32, C.POINTER(UpdateInfo)]
+    if hasattr(lib, "amber_hip_pt_cast_rays"):
+        lib.amber_hip_pt_cast_rays.argtypes = [vp, u64, vp, vp, u32]
+        lib.amber_hip_pt_occluded.argtypes = [vp, u64, vp, vp, u32]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -417,6 +434,85 @@ class PathTracer:
             ptr, n = records.ctypes.data, len(records) if count is None else count
         _check(load_library().amber_hip_pt_update_objects(self._h, first, n, ptr, mode, C.byref(info)))
         return {k: getattr(info, k) for k, _ in UpdateInfo._fields_}
+
+    # ---- the caller's own rays ----------------------------------------------------------------
+    @staticmethod
+    def _is_torch(a) -> bool:
+        return type(a).__module__.split(".")[0] == "torch"
+
+    def _pack_rays(self, origins, dirs, t_max):
+        """(packed rays, n, torch module or None).  numpy: an array of AmberRay records.  torch: an (n, 8) float32 tensor on the tensors' device."""
+        if self._is_torch(origins) or self._is_torch(dirs):
+            import torch
+            if not (self._is_torch(origins) and self._is_torch(dirs)) or not origins.is_cuda or origins.device != dirs.device:
+                raise AmberError("cast_rays / occluded: origins and dirs must both be numpy arrays or both be torch tensors on the handle's device")
+            o, d = origins.reshape(-1, 3).to(torch.float32), dirs.reshape(-1, 3).to(torch.float32)
+            if len(o) != len(d):
+                raise AmberError("cast_rays / occluded: origins and dirs differ in length")
+            packed = torch.zeros((len(o), 8), dtype=torch.float32, device=o.device)
+            packed[:, 0:3], packed[:, 4:7] = o, d
+            if t_max is None:
+                packed[:, 3] = float("inf")
+            else:
+                packed[:, 3] = t_max if not self._is_torch(t_max) else t_max.to(device=o.device, dtype=torch.float32).reshape(-1)
+            return packed, len(o), torch
+        o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
+        if len(o) != len(d):
+            raise AmberError("cast_rays / occluded: origins and dirs differ in length")
+        packed = np.zeros(len(o), _RAY)
+        packed["origin"], packed["dir"] = o, d
+        packed["t_max"] = np.inf if t_max is None else np.asarray(t_max, np.float32)
+        return packed, len(o), None
+
+    def cast_rays(self, origins, dirs, t_max=None):
+        """amber_hip_pt_cast_rays: the closest hit of every ray (origins, dirs: (n, 3)) through the handle's engine, reported iff t <= t_max
+        (t_max: None = INFINITY, a scalar, or (n,)).  Directions are used as given (t is in units of |dir|).  Returns (object, t, pos, normal):
+        object (n,) int32 scene index or -1, t (n,) float32 or NaN, pos and normal (n, 3) float32, zero on a miss.
+
+        numpy arrays go through AMBER_RAYS_HOST (staged by the handle; the call returns with the answer) and come back as numpy arrays.
+        torch tensors on the handle's device go zero-copy: they are packed into an (n, 8) float32 tensor whose data_ptr() the engine reads,
+        and torch tensors come back.  ORDERING: the engine works on the handle's stream, not on torch's current stream.  Wrap the handle's stream
+        -- torch.cuda.ExternalStream(pt.stream()) -- and call this under `with torch.cuda.stream(...)` of it, so that the packing, the query and
+        the returned tensors are ordered on one stream; without that this method waits for torch's current stream before the query and for the
+        handle's stream after it.  A query enqueued before update_objects answers for the old scene, one enqueued after it for the new one."""
+        packed, n, torch = self._pack_rays(origins, dirs, t_max)
+        lib = load_library()
+        if torch is None:
+            hits = np.zeros(n, _RAY_HIT)
+            _check(lib.amber_hip_pt_cast_rays(self._h, n, packed.ctypes.data, hits.ctypes.data, RAYS_HOST))
+            return hits["object"].copy(), hits["t"].copy(), hits["pos"].copy(), hits["normal"].copy()
+        out = torch.empty((n, 8), dtype=torch.float32, device=packed.device)
+        same = self._torch_enter(torch, packed.device)
+        _check(lib.amber_hip_pt_cast_rays(self._h, n, packed.data_ptr(), out.data_ptr(), 0))
+        self._torch_leave(same)
+        return out[:, 1].contiguous().view(torch.int32), out[:, 0].contiguous(), out[:, 2:5].contiguous(), out[:, 5:8].contiguous()
+
+    def occluded(self, origins, dirs, t_max=None):
+        """amber_hip_pt_occluded: (n,) bool (numpy) or torch.bool, True iff cast_rays on the same ray would report a hit -- something lies on the
+        ray at some t <= t_max.  Engine BVH answers with an any-hit walk that stops at the first such object.  Arguments, memory and ordering as
+        cast_rays (torch tensors: wrap PathTracer.stream() in torch.cuda.ExternalStream)."""
+        packed, n, torch = self._pack_rays(origins, dirs, t_max)
+        lib = load_library()
+        if torch is None:
+            occ = np.zeros(n, np.uint8)
+            _check(lib.amber_hip_pt_occluded(self._h, n, packed.ctypes.data, occ.ctypes.data, RAYS_HOST))
+            return occ.astype(bool)
+        out = torch.empty(n, dtype=torch.uint8, device=packed.device)
+        same = self._torch_enter(torch, packed.device)
+        _check(lib.amber_hip_pt_occluded(self._h, n, packed.data_ptr(), out.data_ptr(), 0))
+        self._torch_leave(same)
+        return out.to(torch.bool)
+
+    def _torch_enter(self, torch, device) -> bool:
+        """True when torch's current stream IS the handle's stream (everything is ordered already); otherwise torch's stream is waited for."""
+        same = torch.cuda.current_stream(device).cuda_stream == self.stream()
+        if not same:
+            torch.cuda.current_stream(device).synchronize()
+        return same
+
+    def _torch_leave(self, same: bool) -> None:
+        if not same:
+            self.sync()
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

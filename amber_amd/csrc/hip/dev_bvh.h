@@ -443,6 +443,58 @@ __device__ __forceinline__ bool BvhRound(const DevScene& sc, int32_t* lds_stack,
   return BvhRoundOn(sc, stack, o, d, tr, best AMBER_STAMP_ARG);
 }
 
+// ---- bounded walks (ray_query.inc: amber_hip_pt_cast_rays / amber_hip_pt_occluded) -----------------------------------------------------
+// A walk that must report a hit iff t <= t_max starts from the bound instead of filtering afterwards.  best.t = t_max itself would lose a hit
+// at EXACTLY t_max: with no hit recorded (idx = -1) an equal distance goes to the tie rule and no index is lower than -1.  So the bound is the
+// next binary32 number above t_max: every t <= t_max is then strictly closer than it -- accepted as a first hit always is -- and every
+// t > t_max is >= the bound and refused (equal: the tie rule against idx = -1).  After the first accepted hit best.t <= t_max and the walk is
+// the unbounded one, so the answer is the closest hit (t, lower index) among the hits with t <= t_max: the closest hit of the ray if that has
+// t <= t_max, nothing otherwise -- the filter's answer.  Culling against the bound stays conservative (boxes and the triangle pre-test only
+// drop what lies beyond best.t).  t_max >= FLT_MAX (INFINITY) leaves BvhBegin's FLT_MAX; t_max <= 0 or NaN ends the walk at once: every
+// primitive test wants t > kEPS.
+__device__ __forceinline__ void BvhBeginBounded(const DevScene& sc, V3 o, V3 d, float t_max, BvhTrav& tr, HitRec& best) {
+  BvhBegin(sc, o, d, tr, best);
+  if (!(t_max > 0.0f)) tr.cur = AMBER_BVH_DONE;
+  else if (t_max < 3.402823466e+38f) best.t = __uint_as_float(__float_as_uint(t_max) + 1u);
+}
+
+// The boxes of the tree contain every point at which the reference's binary32 primitive tests can accept a ray whose origin is no farther from the
+// object than the scene's diagonal (bvh_build.h: sphere slack 16 eps D^2, needle reach, both with D = the diagonal): true of every ray a path
+// tracer casts -- origins lie on objects or on the lens, which is an object.  A caller's ray may start anywhere.  From an origin outside the
+// scene's bounding sphere the tests' rounding grows with the distance and they accept rays that miss the padded boxes (measured: from 10 diagonals
+// away 1 ray in 30 of a 20 000-sphere scene, from 10^4 diagonals nearly every ray), so the tree is not conservative for it and the List answer needs
+// the scan of every object (ClosestHitLeafList / AnyHitLeafList: the cost of engine LIST for that ray).  NaN origins: not in range, and BvhBegin
+// has ended the walk already.
+__device__ __forceinline__ bool BvhOriginInRange(const DevScene& sc, V3 o) {
+  const float cx = o.x - sc.bvh_center[0], cy = o.y - sc.bvh_center[1], cz = o.z - sc.bvh_center[2];
+  return cx * cx + cy * cy + cz * cz <= sc.bvh_half_diag * sc.bvh_half_diag;
+}
+
+// Engine BVH, ANY hit: is there an object the ray hits at some t <= t_max?  The same slab operands, the same exact leaf tests and the same
+// rounds as the closest-hit walk (BvhRoundOn), begun with BvhBeginBounded -- so the slab interval is clipped to t_max from the first node --
+// and ended for the lane by the first primitive hit a leaf accepts: whatever is accepted under that bound has t <= t_max, and which object it
+// is does not matter.  Equal to "the closest hit has t <= t_max" because the exact tests are the same functions and the boxes are conservative:
+// an object with t <= t_max is reached by this walk iff by that one.  The descent still takes the nearer child first (it costs two selects);
+// nothing depends on it.  Returns false when the lane has its answer: best.slot >= 0 = occluded (unless tr.overflow: AnyHitLeafList then).
+template <class Stack, int kBudget = AMBER_BVH_DESCENT_BUDGET>
+__device__ __forceinline__ bool BvhAnyHit(const DevScene& sc, const Stack& stack, V3 o, V3 d, BvhTrav& tr, HitRec& best) {
+  BvhDescend<Stack, kBudget>(sc, stack, tr, best.t);
+  BvhLeafPhase(sc, o, d, tr, best);
+  if (best.slot >= 0) { tr.cur = AMBER_BVH_DONE; tr.pend = 0; return false; }
+  return tr.cur != AMBER_BVH_DONE || tr.pend != 0;
+}
+// Its fallback after a traversal stack overflow (cannot happen with the builder's depth cap): the leaf-order array, same rule, first hit ends it.
+__device__ __forceinline__ bool AnyHitLeafList(const DevScene& sc, V3 o, V3 d, float t_max) {
+  if (!(t_max > 0.0f)) return false;
+  HitRec best; best.u = 0.f; best.v = 0.f; best.idx = -1; best.slot = -1;
+  best.t = t_max < 3.402823466e+38f ? __uint_as_float(__float_as_uint(t_max) + 1u) : 3.402823466e+38f;
+  for (uint32_t k = 0; k < sc.n_objects && best.slot < 0; ++k) {
+    const DevObject& ob = sc.bvh_objects[k];
+    IntersectObject<true>(ob, ob.kind, static_cast<int>(sc.bvh_prims[k]), static_cast<int>(k), o, d, best);
+  }
+  return best.slot >= 0;
+}
+
 __device__ __forceinline__ void ClosestHitBvh(const DevScene& sc, int32_t* lds_stack, V3 o, V3 d, HitRec& best, const int stack_cap = AMBER_BVH_STACK) {
   BvhTrav tr;
   BvhBegin(sc, o, d, tr, best);

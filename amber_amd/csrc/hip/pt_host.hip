@@ -12,6 +12,8 @@
 //                          bounds / padding / outward binary16 planes) instead of bvh_build.h's binned-SAH build on the host.
 //   bvh_update.inc         amber_hip_pt_update_objects: new object geometry into a live handle -- records converted and checked by a kernel, then the
 //                          tree made valid again on the device: refitted (any tree, topology kept) or rebuilt (the Morton tree, in place).
+//   ray_query.inc          amber_hip_pt_cast_rays / amber_hip_pt_occluded: the caller's rays through the handle's engine -- engine BVH in a persistent refill
+//                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -164,6 +166,13 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   float tree_area = 0;                      // AmberUpdateInfo.area_after of the tree in use
   double area_host[4] = {0, 0, 0, 0};       // where the two area measurements of an update are copied to
   DevBuf<uint2> d_ref_stack;                // engine REFERENCE_BVH: the traversal stack of the reference's tree, [level][thread of the largest grid]
+  uint64_t ref_stack_threads = 0;           // ... and the threads it was allocated for: no launch that walks that tree may have more (CheckRefStack)
+  // ---- amber_hip_pt_cast_rays / amber_hip_pt_occluded (ray_query.inc): allocated by the first query, reused by every later one
+  DevBuf<int32_t> d_query_stack;            // engine BVH: the global levels of the hybrid traversal stack, [level][thread of the largest query grid]
+  uint64_t query_stack_threads = 0;         // ... and the threads it was allocated for
+  DevBuf<unsigned int> d_query_next;        // engine BVH: the work counter
+  DevBuf<float4> d_query_rays;              // AMBER_RAYS_HOST: staging of the rays and of the results, at most kQueryStageRays rays
+  DevBuf<uint8_t> d_query_out;
   DevBuf<float> d_fb;
   DevBuf<unsigned long long> d_rays;
   DevBuf<unsigned int> d_next;
@@ -399,7 +408,7 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
     const uint64_t bytes = threads * (static_cast<uint64_t>(p.ref_depth) + 1u) * sizeof(uint2);
     if (bytes > (64ull << 30)) return Fail(AMBER_ENOMEM, "the reference's BVH of this scene is " + std::to_string(p.ref_depth) + " levels deep: its traversal stacks would take " + std::to_string(bytes >> 30) + " GiB");
     HIP_TRY(h->d_ref_stack.alloc(bytes / sizeof(uint2)));
-    sc.ref_stack = h->d_ref_stack; sc.ref_stack_stride = static_cast<uint32_t>(threads);
+    sc.ref_stack = h->d_ref_stack; sc.ref_stack_stride = static_cast<uint32_t>(threads); h->ref_stack_threads = threads;
   }
   { const int rc_masks = StartPixelMasks(h.get(), nullptr); if (rc_masks != AMBER_OK) return rc_masks; }   // asynchronous, on the render stream: in front of the handle's first launch
   h->build.create_ms = ms_since(t_create);
@@ -488,11 +497,12 @@ int WithHitEngine(uint32_t hit_engine, F&& f) {
   }
 }
 
-// Engine REFERENCE_BVH's stack has one column per thread of the largest grid (create): a launch must not have more threads.
-// Checked before a launch takes anything (an event pair) it would have to give back.
+// Engine REFERENCE_BVH's stack has one column per thread of the largest grid (create; the handle remembers how many): a launch must not have more
+// threads.  Every launch site of a kernel that walks that tree -- the render passes, light tracing, the ray queries, which share the one stack -- asks
+// here first, before it takes anything (an event pair) it would have to give back.
 int CheckRefStack(const amber_hip_pt* h, uint32_t n_blocks) {
-  if (h->hit_engine == AMBER_ENGINE_REFERENCE_BVH && static_cast<uint64_t>(n_blocks) * 256u > h->scene.ref_stack_stride)
-    return Fail(AMBER_EINVAL, "engine REFERENCE_BVH: a grid of " + std::to_string(n_blocks) + " workgroups outgrows the traversal stack (" + std::to_string(h->scene.ref_stack_stride) + " threads)");
+  if (h->hit_engine == AMBER_ENGINE_REFERENCE_BVH && static_cast<uint64_t>(n_blocks) * 256u > h->ref_stack_threads)
+    return Fail(AMBER_EINVAL, "engine REFERENCE_BVH: a grid of " + std::to_string(n_blocks) + " workgroups outgrows the traversal stack (" + std::to_string(h->ref_stack_threads) + " threads)");
   return AMBER_OK;
 }
 
@@ -742,6 +752,8 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 }
 }  // namespace
 
+#include "ray_query.inc"
+
 extern "C" {
 
 static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t n_pixels, unsigned long long* sig);   // internal: not part of the ABI
@@ -955,6 +967,14 @@ int amber_hip_pt_update_objects(amber_hip_pt* h, uint32_t first, uint32_t count,
   } catch (const std::bad_alloc&) {
     return Fail(AMBER_ENOMEM, "amber_hip_pt_update_objects: out of host memory");
   }
+}
+
+int amber_hip_pt_cast_rays(amber_hip_pt* h, uint64_t n, const AmberRay* rays, AmberRayHit* hits, uint32_t flags) {
+  return RayQuery(h, n, rays, hits, flags, false, "amber_hip_pt_cast_rays");
+}
+
+int amber_hip_pt_occluded(amber_hip_pt* h, uint64_t n, const AmberRay* rays, uint8_t* occluded, uint32_t flags) {
+  return RayQuery(h, n, rays, occluded, flags, true, "amber_hip_pt_occluded");
 }
 
 int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) {

@@ -1,0 +1,207 @@
+// ray_query.inc -- amber_hip_pt_cast_rays / amber_hip_pt_occluded: the caller's own rays through the handle's closest-hit engine (Scene::Cast and
+// the visibility test built on it), in both builds.  Part of the one translation unit pt_host.hip; the device functions are the render kernels'.
+//
+//   bvh_query_kernel<kAnyHit>        engine BVH.  The shape of bvh_trace_rate_kernel (bvh_stream.inc, the lab's traversal-only measurement):
+//                                    persistent waves claim blocks of 256 rays from one counter, idle lanes are refilled by ballot + mbcnt rank once
+//                                    AMBER_QUERY_REFILL of a wave's lanes are idle, the walk is BvhRoundOn / BvhAnyHit on the hybrid LDS + global stack.
+//                                    Beyond the measurement: a ray is two float4 loads with t_max in origin.w, t_max is the walk's initial bound
+//                                    (BvhBeginBounded), the scene index is looked up once for the winner, ResolveHit gives position and normal, and a
+//                                    result is one 32-byte record (closest hit) or one byte (any hit).  A ray whose origin lies outside the scene's
+//                                    bounding sphere is answered by the leaf-list scan (BvhOriginInRange, dev_bvh.h: the tree's boxes are conservative
+//                                    for origins within the scene only), through the path a traversal stack overflow takes.
+//   ray_query_kernel<kEngine, kAnyHit>  LIST, TWO_PHASE, TWO_PHASE_N, REFERENCE_BVH: one thread per ray through ClosestHit<kEngine>, as the known-answer
+//                                    kernel does it -- object loops wave-uniform, the two-phase image staged once per workgroup, no premask -- in a grid
+//                                    no larger than the render kernels' (REFERENCE_BVH's traversal stack has one column per thread of THAT grid), each
+//                                    thread taking every gridDim.x * 256-th ray.  Occlusion is the closest hit compared with t_max.
+// Waves per SIMD and refill threshold: the traversal-only kernel measured 4, 5, 6 and 8 waves per SIMD equal within noise and is driven with 5 waves,
+// 24 LDS stack levels and a threshold of 16 (EXPERIMENTS.md, engine BVH, round 3); these kernels take that point.  No tuning surface.
+#ifndef AMBER_QUERY_WAVES
+#define AMBER_QUERY_WAVES 5
+#endif
+#define AMBER_QUERY_LDS_LEVELS 24
+#define AMBER_QUERY_REFILL 16u
+
+namespace {
+
+__device__ __forceinline__ void StoreRayHit(float4* __restrict__ hits, size_t i, float t, int32_t object, V3 pos, V3 nrm) {   // AmberRayHit: 32 bytes, two 16-byte stores
+  hits[2u * i] = make_float4(t, __int_as_float(object), pos.x, pos.y);
+  hits[2u * i + 1u] = make_float4(pos.z, nrm.x, nrm.y, nrm.z);
+}
+__device__ __forceinline__ void StoreRayMiss(float4* __restrict__ hits, size_t i) {
+  StoreRayHit(hits, i, __builtin_nanf(""), -1, v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f));
+}
+
+template <bool kAnyHit>
+__global__ void __launch_bounds__(256, AMBER_QUERY_WAVES) bvh_query_kernel(const DevScene sc, uint32_t n, const float4* __restrict__ rays, float4* __restrict__ hits,
+                                                                           uint8_t* __restrict__ occluded, unsigned int* next, int32_t* gstack, uint32_t gstack_stride) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  __shared__ int32_t lds_stack[AMBER_QUERY_LDS_LEVELS * 256];
+  const BvhStackHybrid stack{(LdsInts)(lds_stack + wave * (AMBER_QUERY_LDS_LEVELS * 64)), (GlobalInts)(gstack + (blockIdx.x * 256u + wave * 64u)), gstack_stride,
+                             AMBER_QUERY_LDS_LEVELS, AMBER_BVH_STACK};
+  uint32_t blk_next = 0, blk_end = 0;
+  bool exhausted = false, has = false;
+  uint32_t ray_id = 0;
+  V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
+  float t_max = 0.f;
+  BvhTrav tr; tr.A = v3(0.f, 0.f, 0.f); tr.b_in = v3(0.f, 0.f, 0.f); tr.b_out = v3(0.f, 0.f, 0.f); tr.neg_slack = 0.f; tr.rot[0] = tr.rot[1] = tr.rot[2] = 0u;
+  tr.cur = AMBER_BVH_DONE; tr.pend = 0; tr.sp = 0; tr.overflow = false;
+  HitRec hit; hit.t = 0.f; hit.u = 0.f; hit.v = 0.f; hit.idx = -1; hit.slot = -1;
+  for (;;) {
+    const unsigned long long m_has = __ballot(has);
+    const uint32_t n_idle = 64u - static_cast<uint32_t>(__popcll(m_has));
+    if (n_idle >= AMBER_QUERY_REFILL || m_has == 0ull) {                  // wave-uniform: serve the idle lanes
+      bool want = !has, got = false;
+      unsigned long long mw = __ballot(want);
+      while (mw != 0ull) {
+        const uint32_t avail = blk_end - blk_next;
+        if (avail == 0u) {
+          if (exhausted) break;
+          uint32_t base = 0;
+          if (lane == 0u) base = atomicAdd(next, 256u);                     // (n <= 2^31 and every wave adds once more at most: no wrap)
+          base = __builtin_amdgcn_readfirstlane(base);
+          if (base >= n) { exhausted = true; break; }
+          blk_next = base; blk_end = n - base < 256u ? n : base + 256u;
+          continue;
+        }
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mw >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mw), 0u));
+        if (want && rank < avail) { ray_id = blk_next + rank; want = false; got = true; }
+        const uint32_t wanted = static_cast<uint32_t>(__popcll(mw));
+        blk_next += wanted < avail ? wanted : avail;
+        mw = __ballot(want);
+      }
+      if (got) {
+        const float4 ro = rays[2u * static_cast<size_t>(ray_id)], rd = rays[2u * static_cast<size_t>(ray_id) + 1u];   // AmberRay: origin, t_max | dir, pad
+        o = v3(ro.x, ro.y, ro.z); d = v3(rd.x, rd.y, rd.z); t_max = ro.w;
+        BvhBeginBounded(sc, o, d, t_max, tr, hit);
+        if (tr.cur != AMBER_BVH_DONE && !BvhOriginInRange(sc, o)) { tr.cur = AMBER_BVH_DONE; tr.overflow = true; }   // the tree does not cover this origin: the scan below
+        has = true;
+      }
+      if (__ballot(has) == 0ull) break;
+    }
+    if (has) {
+      if constexpr (kAnyHit) {
+        if (!BvhAnyHit(sc, stack, o, d, tr, hit)) {
+          occluded[ray_id] = (tr.overflow ? AnyHitLeafList(sc, o, d, t_max) : hit.slot >= 0) ? 1 : 0;
+          has = false;
+        }
+      } else {
+        if (!BvhRoundOn(sc, stack, o, d, tr, hit)) {
+          if (tr.overflow) ClosestHitLeafList(sc, o, d, hit);               // (unbounded: the comparison below is the filter)
+          if (hit.slot >= 0 && hit.t <= t_max) {
+            BvhResolveIndex(sc, hit);
+            V3 pos, nrm; uint32_t mat;
+            ResolveHit(sc.bvh_objects, hit, o, d, pos, nrm, mat);
+            StoreRayHit(hits, ray_id, hit.t, hit.idx, pos, nrm);
+          } else {
+            StoreRayMiss(hits, ray_id);
+          }
+          has = false;
+        }
+      }
+    }
+  }
+}
+
+template <int kEngine, bool kAnyHit>
+__global__ void __launch_bounds__(256) ray_query_kernel(const DevScene sc, uint64_t n, const float4* __restrict__ rays, float4* __restrict__ hits, uint8_t* __restrict__ occluded) {
+  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
+  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
+  __shared__ int32_t lds_stack[1];
+  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * 256u; base < n; base += static_cast<uint64_t>(gridDim.x) * 256u) {   // uniform over the workgroup
+    const uint64_t i = base + threadIdx.x;
+    const uint64_t k = i < n ? i : n - 1;      // keep the object loop wave-uniform for every lane
+    const float4 ro = rays[2u * k], rd = rays[2u * k + 1u];
+    const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rd.x, rd.y, rd.z);
+    const float t_max = ro.w;
+    HitRec h;
+#ifdef AMBER_STAMPS
+    StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
+#endif
+    ClosestHit<kEngine>(sc, lds_objects, lds_stack, o, d, -1, h AMBER_STAMP_ARG);
+    if (i >= n) continue;
+    // every exact test forms dot products over all components of o and d: a NaN component makes every distance NaN, which no hit accepts
+    const bool nan_ray = !(o.x == o.x && o.y == o.y && o.z == o.z && d.x == d.x && d.y == d.y && d.z == d.z);
+    const bool found = h.idx >= 0 && !nan_ray && h.t <= t_max;
+    if constexpr (kAnyHit) {
+      occluded[i] = found ? 1 : 0;
+    } else if (found) {
+      V3 pos, nrm; uint32_t mat;
+      ResolveHit<kEngine == ENGINE_TWO_PHASE_N ? 0x7fu : 0xffu>(kTwoPhase ? lds_objects : (kEngine == ENGINE_REF_BVH ? sc.bvh_objects : sc.objects), h, o, d, pos, nrm, mat);
+      StoreRayHit(hits, i, h.t, h.idx, pos, nrm);
+    } else {
+      StoreRayMiss(hits, i);
+    }
+  }
+}
+
+static_assert(sizeof(AmberRay) == 32 && sizeof(AmberRayHit) == 32, "a ray and a hit are two float4 each");
+constexpr uint64_t kQueryMaxRays = 1ull << 31;
+constexpr uint64_t kQueryStageRays = 1ull << 20;          // AMBER_RAYS_HOST: rays per trip through the staging buffers (32 MiB + 32 MiB)
+
+// One launch over n rays in device memory.  Engine BVH's scratch (the global levels of the hybrid stack for the largest grid, the work counter)
+// is allocated by the first query and kept.
+int LaunchRayQuery(amber_hip_pt* h, uint64_t n, const float4* d_rays, void* d_out, bool any_hit) {
+  float4* hits = any_hit ? nullptr : static_cast<float4*>(d_out);
+  uint8_t* occluded = any_hit ? static_cast<uint8_t*>(d_out) : nullptr;
+  const uint64_t by_work = (n + 255u) / 256u;
+  if (h->hit_engine == AMBER_ENGINE_BVH) {
+    const uint32_t max_blocks = static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_QUERY_WAVES);
+    if (!h->d_query_stack) {
+      const hipError_t e = h->d_query_stack.alloc(static_cast<size_t>(max_blocks) * 256u * (AMBER_BVH_STACK - AMBER_QUERY_LDS_LEVELS));
+      if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string("hipMalloc(query traversal stacks): ") + hipGetErrorString(e));
+      h->query_stack_threads = static_cast<uint64_t>(max_blocks) * 256u;
+    }
+    if (!h->d_query_next) HIP_TRY(h->d_query_next.alloc(1));
+    const uint32_t n_blocks = by_work < max_blocks ? static_cast<uint32_t>(by_work) : max_blocks;
+    if (static_cast<uint64_t>(n_blocks) * 256u > h->query_stack_threads)
+      return Fail(AMBER_EINVAL, "ray query: a grid of " + std::to_string(n_blocks) + " workgroups outgrows the traversal stack (" + std::to_string(h->query_stack_threads) + " threads)");
+    HIP_TRY(hipMemsetAsync(h->d_query_next, 0, sizeof(unsigned int), h->stream));
+    const uint32_t stride = static_cast<uint32_t>(h->query_stack_threads);
+    if (any_hit) hipLaunchKernelGGL(bvh_query_kernel<true>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->d_query_next.p, h->d_query_stack.p, stride);
+    else hipLaunchKernelGGL(bvh_query_kernel<false>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->d_query_next.p, h->d_query_stack.p, stride);
+  } else {
+    const uint32_t max_blocks = PersistentBlocks(h);
+    const uint32_t n_blocks = by_work < max_blocks ? static_cast<uint32_t>(by_work) : max_blocks;
+    { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
+    WithHitEngine(h->hit_engine, [&](auto engine) -> int {
+      constexpr int kEngine = decltype(engine)::value;
+      if constexpr (kEngine != ENGINE_BVH) {
+        if (any_hit) hipLaunchKernelGGL((ray_query_kernel<kEngine, true>), dim3(n_blocks), dim3(256), 0, h->stream, h->scene, n, d_rays, hits, occluded);
+        else hipLaunchKernelGGL((ray_query_kernel<kEngine, false>), dim3(n_blocks), dim3(256), 0, h->stream, h->scene, n, d_rays, hits, occluded);
+      }
+      return AMBER_OK;
+    });
+  }
+  HIP_TRY(hipGetLastError());
+  return AMBER_OK;
+}
+
+int RayQuery(amber_hip_pt* h, uint64_t n, const AmberRay* rays, void* out, uint32_t flags, bool any_hit, const char* name) {
+  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
+  if (flags & ~static_cast<uint32_t>(AMBER_RAYS_HOST)) return Fail(AMBER_EINVAL, std::string(name) + ": unknown flag bits");
+  if (n > kQueryMaxRays) return Fail(AMBER_EINVAL, std::string(name) + ": more than 2^31 rays in one call");
+  if (n == 0) return AMBER_OK;
+  if (!rays || !out) return Fail(AMBER_EINVAL, std::string(name) + ": null rays or output pointer");
+#if AMBER_BVH_WIDE
+  return Fail(AMBER_EINVAL, std::string(name) + ": not part of an AMBER_BVH_WIDE measurement build");
+#endif
+  HIP_TRY(hipSetDevice(h->device));
+  if (!(flags & AMBER_RAYS_HOST)) return LaunchRayQuery(h, n, reinterpret_cast<const float4*>(rays), out, any_hit);
+  // host pointers: through the handle's staging buffers, kQueryStageRays at a time, and back before the call returns
+  const size_t out_size = any_hit ? 1u : sizeof(AmberRayHit);
+  const uint64_t chunk = n < kQueryStageRays ? n : kQueryStageRays;
+  { const int rc = Grow(h, h->d_query_rays, chunk * 2u, "ray staging"); if (rc != AMBER_OK) return rc; }
+  { const int rc = Grow(h, h->d_query_out, chunk * out_size, "ray staging"); if (rc != AMBER_OK) return rc; }
+  for (uint64_t done = 0; done < n; done += chunk) {
+    const uint64_t m = n - done < chunk ? n - done : chunk;
+    HIP_TRY(hipMemcpyAsync(h->d_query_rays, rays + done, m * sizeof(AmberRay), hipMemcpyHostToDevice, h->stream));
+    { const int rc = LaunchRayQuery(h, m, h->d_query_rays, h->d_query_out, any_hit); if (rc != AMBER_OK) return rc; }
+    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(out) + done * out_size, h->d_query_out, m * out_size, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  return AMBER_OK;
+}
+
+}  // namespace

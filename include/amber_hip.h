@@ -31,7 +31,8 @@ extern "C" {
                                     (amber_hip_lab.h); AMBER_PT_FLAG_BVH_ITEMS added.  2 (round 4): lt ranges, stream; a stream-ordered read of
                                     amber_hip_pt_device_framebuffer() needs amber_hip_pt_sync() first when a launch may have run out of record slots.
                                     Still 3 with AMBER_PT_FLAG_DEVICE_BUILD and amber_hip_pt_build_info(): a flag bit that older libraries ignore and
-                                    a new function; nothing that existed changed its layout or meaning.  Still 3 with amber_hip_pt_update_objects(): a new function */
+                                    a new function; nothing that existed changed its layout or meaning.  Still 3 with amber_hip_pt_update_objects(): a new function.
+                                    Still 3 with amber_hip_pt_cast_rays() / amber_hip_pt_occluded(): two new functions and their two structs */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -252,6 +253,30 @@ typedef struct {
 } AmberUpdateInfo;
 int  amber_hip_pt_update_objects(amber_hip_pt*, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode,
                                  AmberUpdateInfo* info /* may be NULL */);
+/* The caller's own rays through the handle's closest-hit engine: Scene::Cast (cast_rays) and the visibility test built on it (occluded).  Still
+ * ABI version 3: two new functions.
+ *   cast_rays  hits[i] = what the handle's engine returns for Scene::Cast(rays[i]): LIST, TWO_PHASE (both forms) and BVH the closest finite hit, ties
+ *              to the lower scene index (acceleration_list.h:51-68); REFERENCE_BVH the hit the reference's own tree finds.  The reference's kEPS
+ *              threshold is inside the primitive tests; there is no t_min.  dir is used as given, never normalised: t is in units of |dir|, exactly
+ *              as in the render kernels.  pos and normal are the reference's Intersect() output (a triangle's pos from its barycentrics, not
+ *              o + t d).  t_max filters the answer: the hit is reported iff t <= t_max; otherwise, and on a miss, object = -1, t = NaN, pos and normal
+ *              0.  A NaN t_max is therefore always a miss: pass INFINITY for "unbounded".  A ray with a NaN component hits nothing.  object is a
+ *              scene index (the position in AmberFlatScene.objects), never a leaf slot.
+ *   occluded   occluded[i] = 1 iff cast_rays on the same ray would report a hit, else 0.  Defined through the closest hit; computed by an any-hit walk
+ *              where the engine has one (BVH: the walk ends at the first primitive hit with t <= t_max), by the closest hit elsewhere.
+ * Memory: by default rays and the output are DEVICE pointers on the handle's device, and the call is asynchronous and stream-ordered on the
+ * handle's stream like amber_hip_pt_render_pass: a query enqueued before amber_hip_pt_update_objects sees the old scene, one enqueued after it the
+ * new one; read the output after amber_hip_pt_sync, or from work enqueued on amber_hip_pt_stream.  With AMBER_RAYS_HOST both are HOST pointers: the
+ * call stages through buffers the handle owns (a million rays at a time) and returns after the copy back.
+ * Neither function touches the framebuffer, the ray counter or amber_hip_pt_kernel_time.  Scratch (engine BVH's traversal stacks and work counter,
+ * the staging buffers) is allocated by the first query, sized by the launch and not by n, reused by every later query and released by destroy.
+ * n == 0: AMBER_OK.  AMBER_EINVAL: n > 2^31, a NULL pointer with n > 0, unknown flag bits, an AMBER_BVH_WIDE measurement build.  A handle of the lab
+ * engine WAVEFRONT answers as engine AUTO does (its closest hit is AUTO's). */
+typedef struct { float origin[3]; float t_max; float dir[3]; uint32_t pad; } AmberRay;      /* 32 bytes: two float4 loads */
+typedef struct { float t; int32_t object; float pos[3]; float normal[3]; } AmberRayHit;     /* 32 bytes */
+enum { AMBER_RAYS_HOST = 1u };   /* rays / out are host pointers: the call stages them and waits */
+int  amber_hip_pt_cast_rays(amber_hip_pt*, uint64_t n, const AmberRay* rays, AmberRayHit* hits, uint32_t flags);
+int  amber_hip_pt_occluded(amber_hip_pt*, uint64_t n, const AmberRay* rays, uint8_t* occluded, uint32_t flags);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);
