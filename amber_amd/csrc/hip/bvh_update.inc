@@ -106,25 +106,28 @@ __global__ void __launch_bounds__(256) bu_emit(DevBvhNodeQ* __restrict__ nodes, 
 
 // Tree quality as AmberUpdateInfo reports it, from the planes the traversal reads: out[0] += surface areas of both child boxes of every
 // node, out[1] = surface area of the root (the union of its two).  The sum's rounding depends on the arrival order: informative only.
-__device__ __forceinline__ double PlaneBoxArea(const float lo[3], const float hi[3]) {
-  const double x = double(hi[0]) - lo[0], y = double(hi[1]) - lo[1], z = double(hi[2]) - lo[2];
+// The planes are decoded in binary64 (gmin + value * step rounds once, by 2^-53): narrowed to binary32 they lose up to half an ulp of the
+// COORDINATE each, which for a thin box far from the origin (a planar mesh at z = 1234.5: boxes 0.04 thick) is 1e-3 of its side and moved
+// the figure by 1e-4 (tests/test_tree_tightness.py).
+__device__ __forceinline__ double PlaneBoxArea(const double lo[3], const double hi[3]) {
+  const double x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
   return (x < 0 || y < 0 || z < 0) ? 0.0 : 2.0 * (x * y + y * z + z * x);
 }
 __global__ void __launch_bounds__(256) bu_area(const DevBvhNodeQ* __restrict__ nodes, uint32_t n_nodes, uint32_t root, dbuild::Grid g, double* out) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   double sum = 0.0;
   if (i < n_nodes) {
-    float lo[2][3], hi[2][3];
+    double lo[2][3], hi[2][3];
     for (int side = 0; side < 2; side++)
       for (int c = 0; c < 3; c++) {
         const uint32_t w = nodes[i].w[3 * side + c];
-        lo[side][c] = static_cast<float>(double(g.gmin[c]) + amber_bvh::F16Value(static_cast<uint16_t>(w & 0xffffu)) * double(g.step[c]));
-        hi[side][c] = static_cast<float>(double(g.gmin[c]) + amber_bvh::F16Value(static_cast<uint16_t>(w >> 16)) * double(g.step[c]));
+        lo[side][c] = double(g.gmin[c]) + amber_bvh::F16Value(static_cast<uint16_t>(w & 0xffffu)) * double(g.step[c]);
+        hi[side][c] = double(g.gmin[c]) + amber_bvh::F16Value(static_cast<uint16_t>(w >> 16)) * double(g.step[c]);
       }
     sum = PlaneBoxArea(lo[0], hi[0]) + PlaneBoxArea(lo[1], hi[1]);
     if (i == root) {
-      float ulo[3], uhi[3];
-      for (int c = 0; c < 3; c++) { ulo[c] = fminf(lo[0][c], lo[1][c]); uhi[c] = fmaxf(hi[0][c], hi[1][c]); }
+      double ulo[3], uhi[3];
+      for (int c = 0; c < 3; c++) { ulo[c] = fmin(lo[0][c], lo[1][c]); uhi[c] = fmax(hi[0][c], hi[1][c]); }
       out[1] = PlaneBoxArea(ulo, uhi);
     }
   }

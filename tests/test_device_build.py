@@ -22,12 +22,11 @@ import oracle_binding as O
 from amber_amd import scenes
 from amber_amd import workloads as WL
 from bvh_parity import bits, check_band
+from tree_reference import pad_boxes, scene_extent, widened_object_boxes
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
-EPS = 5.9604644775390625e-08
 K_LEAF, K_MAX_DEPTH = 3, 30                     # bvh_build.h: kLeafSize, kMaxDepth
-F32 = np.float32
 
 
 # ---- the validator -------------------------------------------------------------------------------------------------------------------
@@ -38,47 +37,10 @@ def _objects(hs):
 
 def _padded_object_boxes(arr):
     """bvh_build.h's ObjectBox (widened: sphere slack 16 eps D^2, needle reach) and PadBox of every object, with the roundings of the C++ code:
-    binary64 where it computes in double, one rounding to binary32 where it narrows, binary32 operations where it works in float."""
-    kind, p = arr["kind"], arr["p"]
-    a = p[:, 0:3]
-    tri, sph, dsk, cyl = kind == 0, kind == 1, kind == 2, kind == 3
-    e1 = np.where(tri[:, None], p[:, 3:6] - a, p[:, 3:6]).astype(F32)
-    e2 = (p[:, 6:9] - a).astype(F32)
-    radius = np.where(sph, p[:, 3], p[:, 6]).astype(F32)
-    height = p[:, 7]
-
-    def boxes(slack2, reach):
-        mn, mx = np.empty_like(a), np.empty_like(a)
-        v1, v2 = (a + e1).astype(F32), (a + e2).astype(F32)
-        tmn, tmx = np.minimum(a, np.minimum(v1, v2)), np.maximum(a, np.maximum(v1, v2))
-        if reach > 0:
-            d1, d2_, d3 = e1.astype(np.float64), e2.astype(np.float64), e2.astype(np.float64) - e1.astype(np.float64)
-            l = np.stack([(d1 * d1).sum(1), (d2_ * d2_).sum(1), (d3 * d3).sum(1)], 1)
-            emax, emin = np.sqrt(l.max(1)), np.sqrt(l.min(1))
-            with np.errstate(divide="ignore", invalid="ignore"):
-                m = np.minimum(reach, 36.0 * EPS * reach * emax / emin)
-            ok = (emin > 0) & np.isfinite(emax)
-            tmn = np.where(ok[:, None], (tmn.astype(np.float64) - m[:, None]).astype(F32), tmn)
-            tmx = np.where(ok[:, None], (tmx.astype(np.float64) + m[:, None]).astype(F32), tmx)
-        mn[tri], mx[tri] = tmn[tri], tmx[tri]
-        r = (np.sqrt(radius.astype(np.float64) ** 2 + slack2) * 1.000001).astype(F32)
-        mn[sph], mx[sph] = (a - r[:, None]).astype(F32)[sph], (a + r[:, None]).astype(F32)[sph]
-        rd = np.abs(radius.astype(np.float64)) * 1.000001
-        nu = np.sqrt((e1.astype(np.float64) ** 2).sum(1))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            axial = np.where(nu > 1e-30, np.abs(height.astype(np.float64)) / nu, 1e30)
-        rc = np.minimum(1e30, np.hypot(radius.astype(np.float64), axial) * 1.000001)
-        for sel, rr in ((dsk, rd), (cyl, rc)):
-            mn[sel], mx[sel] = (a.astype(np.float64) - rr[:, None]).astype(F32)[sel], (a.astype(np.float64) + rr[:, None]).astype(F32)[sel]
-        return mn, mx
-
-    mn, mx = boxes(0.0, 0.0)
-    d2 = float(((np.nanmax(mx, 0).astype(np.float64) - np.nanmin(mn, 0).astype(np.float64)) ** 2).sum())
-    mn, mx = boxes(16.0 * EPS * d2, np.sqrt(d2))
-    extent = F32((np.nanmax(mx, 0) - np.nanmin(mn, 0)).astype(F32).max())
-    m = np.maximum(np.abs(mn), np.abs(mx))
-    pad = (F32(1.52587890625e-05) * (extent + m).astype(F32)).astype(F32) + F32(1e-30)
-    return (mn - pad).astype(F32).astype(np.float64), (mx + pad).astype(F32).astype(np.float64)
+    tree_reference.widened_object_boxes, then tree_reference.pad_boxes with the extent of the scene (binary32), as binary64."""
+    mn, mx = widened_object_boxes(arr)
+    mn, mx = pad_boxes(mn, mx, scene_extent(mn, mx))
+    return mn.astype(np.float64), mx.astype(np.float64)
 
 
 def _decode(dump):

@@ -5,6 +5,10 @@ AUTO, ACCEL_BVH for REFERENCE_BVH; pos and normal against oracle_cast on 4096 hi
 oracle's answer does not depend on t_max, so it is computed once per scene on the base rays and every base ray is then queried under seven t_max
 values: INFINITY, 0, a negative number, NaN, exactly its own hit distance (must be reported), the next binary32 number below it (must be a miss:
 the filter rule), a random fraction of the scene diagonal.
+
+Batch edges (the last section): counts below, at and just above a wave and a block of 256 with every ray compared and the output arrays guarded
+by sentinels; AMBER_RAYS_HOST calls of one, two and three trips through the staging buffers (2^20 rays a trip) in both orders of occluded and
+cast on one handle; the same counts through the device-pointer path in the torch child.
 """
 import json
 import os
@@ -153,12 +157,29 @@ class Case:
 
 
 FRAME = (256, 256, 12345, (120, 124), 4)
+SPHERE_FRAME = (1024, 1024, 7, (500, 502), 2)
+_cases = {}
+
+
+def _case(amber, key):
+    """the Case of one of the three scenes several tests share: built, and its rays put through the oracle, once"""
+    if key not in _cases:
+        if key == "cornell":
+            _cases[key] = Case(amber, "Cornell box", amber.HostScene.cornell_box(), O.Scene.cornell(O.ACCEL_BVH), FRAME)
+        elif key == "cornell20":
+            kw = scenes.cornell_plus(20)
+            assert 40 <= len(kw["kinds"]) + kw["n_blades"] <= 60
+            _cases[key] = Case(amber, "Cornell + 20", amber.HostScene.create_arrays(**kw), O.Scene.create_arrays(**kw, accel=O.ACCEL_BVH), FRAME)
+        else:
+            kw = scenes.random_spheres(20_000, 7)
+            _cases[key] = Case(amber, "20 000 spheres", amber.HostScene.create_arrays(**kw), O.Scene.create_arrays(**kw, accel=O.ACCEL_BVH), SPHERE_FRAME)
+    return _cases[key]
 
 
 # ---- the scenes ------------------------------------------------------------------------------------------------------------------------------
 def test_cornell_box_every_engine(amber):
     """AUTO picks TWO_PHASE (19 objects)"""
-    c = Case(amber, "Cornell box", amber.HostScene.cornell_box(), O.Scene.cornell(O.ACCEL_BVH), FRAME)
+    c = _case(amber, "cornell")
     c.check(amber.ENGINE_AUTO, "AUTO (two-phase)", pos=True)
     for engine, label in ((amber.ENGINE_LIST, "LIST"), (amber.ENGINE_TWO_PHASE, "TWO_PHASE"), (amber.ENGINE_BVH, "BVH")):
         c.check(engine, label)
@@ -169,17 +190,15 @@ def test_cornell_box_every_engine(amber):
 
 def test_grouped_two_phase_scene(amber):
     """45 objects: AUTO is the two-phase engine over groups of 32"""
-    kw = scenes.cornell_plus(20)
-    assert 40 <= len(kw["kinds"]) + kw["n_blades"] <= 60
-    c = Case(amber, "Cornell + 20", amber.HostScene.create_arrays(**kw), O.Scene.create_arrays(**kw, accel=O.ACCEL_BVH), FRAME)
+    c = _case(amber, "cornell20")
+    assert 40 <= len(c.arr) <= 60
     c.check(amber.ENGINE_AUTO, "AUTO (grouped two-phase)", pos=True)
     for engine, label in ((amber.ENGINE_TWO_PHASE, "TWO_PHASE"), (amber.ENGINE_LIST, "LIST"), (amber.ENGINE_BVH, "BVH"), (amber.ENGINE_REFERENCE_BVH, "REFERENCE_BVH")):
         c.check(engine, label)
 
 
 def test_sphere_scene_host_and_device_trees(amber):
-    kw = scenes.random_spheres(20_000, 7)
-    c = Case(amber, "20 000 spheres", amber.HostScene.create_arrays(**kw), O.Scene.create_arrays(**kw, accel=O.ACCEL_BVH), (1024, 1024, 7, (500, 502), 2))
+    c = _case(amber, "spheres")
     host = c.check(amber.ENGINE_AUTO, "AUTO (BVH), host tree", pos=True)
     dev = c.check(amber.ENGINE_AUTO, "AUTO (BVH), device tree", device=True)
     for a, b in zip(host, dev):
@@ -231,7 +250,7 @@ def test_queries_follow_update_objects(amber):
 
 # ---- side effects and errors -------------------------------------------------------------------------------------------------------------
 def test_queries_leave_the_render_alone(amber):
-    c = Case(amber, "Cornell box", amber.HostScene.cornell_box(), O.Scene.cornell(O.ACCEL_BVH), FRAME)
+    c = _case(amber, "cornell")
     kw = scenes.random_spheres(20_000, 7)
     for hs in (c.hs, amber.HostScene.create_arrays(**kw)):
         res = []
@@ -270,6 +289,135 @@ def test_errors_leave_the_handle_as_it_was(amber):
         pt.close()
 
 
+# ---- batch edges ---------------------------------------------------------------------------------------------------------------------------
+# Where the kernels count: bvh_query_kernel's claim of the last block of 256 (n - base < 256), its ballot refill with fewer rays than lanes,
+# ray_query_kernel's clamped tail lane, and AMBER_RAYS_HOST's trips through staging buffers that cast (32 bytes a ray) and occluded (1 byte) share.
+SMALL_COUNTS = (1, 2, 63, 64, 65, 255, 256, 257, 511, 513)
+STAGE_RAYS = 1 << 20                                                         # ray_query.inc: kQueryStageRays
+TRIP_COUNTS = (STAGE_RAYS - 1, STAGE_RAYS, STAGE_RAYS + 1, 2 * STAGE_RAYS, 2 * STAGE_RAYS + 257)
+N_TILE = 100_003                                                             # a prime: the trip boundary falls at another phase of the tiling each trip
+GUARD, SENTINEL = 64, 0xA5
+
+
+def mixed_t_max(t_oracle):
+    """t_max by position: INFINITY, the number below the hit distance (a miss), NaN (a miss), INFINITY, half the hit distance (a miss), NaN, ..."""
+    known = np.where(np.isnan(t_oracle), F32(1.0), t_oracle).astype(F32)
+    tm = np.full(len(t_oracle), np.inf, F32)
+    tm[1::6] = np.nextafter(known, F32(-np.inf))[1::6]
+    tm[4::6] = (F32(0.5) * known)[4::6]
+    tm[2::3] = np.nan
+    return tm
+
+
+def head_order(obj_oracle, window=4096):
+    """The head of the base rays (the engine's own path rays) in an order that alternates rays the oracle hits with rays it misses while both last:
+    in a sparse scene the first hundreds of eye rays all miss, in a closed room all hit."""
+    head = np.arange(min(window, len(obj_oracle)))
+    hit, miss = head[obj_oracle[head] >= 0], head[obj_oracle[head] < 0]
+    m = min(len(hit), len(miss))
+    return np.concatenate([np.stack([hit[:m], miss[:m]], 1).ravel(), hit[m:], miss[m:]])
+
+
+def pack_rays(amber, o, d, tm):
+    packed = np.zeros(len(o), amber.api._RAY)
+    packed["origin"], packed["dir"], packed["t_max"] = o, d, tm
+    return packed
+
+
+def guarded_queries(amber, pt, packed, n, first="cast", bufs=None):
+    """cast_rays and occluded of packed[:n] through AMBER_RAYS_HOST, in the order given, into arrays with GUARD sentinel elements behind element n,
+    which must come back untouched.  Returns (hits[:n], occluded[:n])."""
+    lib = amber.load_library()
+    hits, occ = bufs if bufs is not None else (np.empty(n + GUARD, amber.api._RAY_HIT), np.empty(n + GUARD, np.uint8))
+    hits[:n + GUARD].view(np.uint8)[:] = SENTINEL
+    occ[:n + GUARD] = SENTINEL
+    calls = {"cast": lambda: lib.amber_hip_pt_cast_rays(pt._h, n, packed.ctypes.data, hits.ctypes.data, amber.RAYS_HOST),
+             "occluded": lambda: lib.amber_hip_pt_occluded(pt._h, n, packed.ctypes.data, occ.ctypes.data, amber.RAYS_HOST)}
+    for name in (first, "occluded" if first == "cast" else "cast"):
+        assert calls[name]() == 0, (name, lib.amber_hip_last_error())
+    assert (hits[n:n + GUARD].view(np.uint8) == SENTINEL).all() and (occ[n:n + GUARD] == SENTINEL).all(), "a query wrote behind its last ray"
+    return hits[:n], occ[:n]
+
+
+def check_batch(label, hits, occ, exp):
+    """every ray: object and t bit for bit, a miss is -1 / NaN / zeros, occluded is the same rule"""
+    rep, obj_e, t_e = exp
+    b = lambda x: np.ascontiguousarray(x, F32).view(np.uint32)
+    obj = np.ascontiguousarray(hits["object"])
+    assert np.array_equal(obj, obj_e), (label, np.flatnonzero(obj != obj_e)[:8])
+    assert np.array_equal(b(hits["t"])[rep], b(t_e)[rep]), label
+    miss = ~rep
+    assert np.isnan(hits["t"][miss]).all() and not hits["pos"][miss].any() and not hits["normal"][miss].any(), label
+    assert np.array_equal(occ, rep.astype(np.uint8)), (label, np.flatnonzero(occ != rep)[:8])
+
+
+SMALL_ENGINES = {"cornell": (("ENGINE_AUTO", False), ("ENGINE_TWO_PHASE", False), ("ENGINE_LIST", False), ("ENGINE_BVH", False), ("ENGINE_REFERENCE_BVH", False)),
+                 "cornell20": (("ENGINE_AUTO", False),),                        # the grouped two-phase engine
+                 "spheres": (("ENGINE_AUTO", False), ("ENGINE_AUTO", True))}    # engine BVH on the host's tree and on the device's
+
+
+@pytest.mark.parametrize("key", ["cornell", "cornell20", "spheres"])
+def test_batches_smaller_than_a_block_and_around_its_edges(amber, key):
+    c = _case(amber, key)
+    for engine_name, device in SMALL_ENGINES[key]:
+        engine = getattr(amber, engine_name)
+        obj_o, t_o = c.oracle[O.ACCEL_BVH if engine == amber.ENGINE_REFERENCE_BVH else O.ACCEL_LIST]
+        pt = c.tracer(engine, device)
+        if key == "spheres":
+            assert pt.build_info()["where"] == (amber.BUILD_DEVICE if device else amber.BUILD_HOST)
+        head = head_order(obj_o)
+        tm = mixed_t_max(t_o[head])                                             # by position in the batch: a batch is a prefix of the largest one
+        for n in SMALL_COUNTS:
+            k = head[:n]
+            exp = expected(obj_o[k], t_o[k], tm[:n])
+            assert n < 8 or (exp[0].any() and not exp[0].all())                # hits and misses
+            hits, occ = guarded_queries(amber, pt, pack_rays(amber, c.org[k], c.dirs[k], tm[:n]), n, first="cast" if n % 2 else "occluded")
+            check_batch(f"{c.name}, {engine_name}{', device tree' if device else ''}, {n} rays", hits, occ, exp)
+        pt.close()
+
+
+def tile_base(c):
+    """N_TILE oracle-checked rays of the case (List semantics): its base rays, and as many more towards its objects as it takes"""
+    if not hasattr(c, "tile"):
+        org, dirs, (obj_o, t_o) = c.org, c.dirs, c.oracle[O.ACCEL_LIST]
+        more = N_TILE - len(org)
+        if more > 0:
+            rng = np.random.default_rng(29)
+            lo, hi, _ = scene_box(c.arr)
+            o = rng.uniform(lo, hi, (more, 3))
+            d = c.arr["p"][rng.integers(0, len(c.arr), more), :3] + rng.normal(size=(more, 3)) * 0.02 - o
+            o, d = np.ascontiguousarray(o, F32), np.ascontiguousarray(d / np.linalg.norm(d, axis=1, keepdims=True), F32)
+            io, to = c.osc.cast_many(o, d, O.ACCEL_LIST, threads=16)
+            org, dirs, obj_o, t_o = np.concatenate([org, o]), np.concatenate([dirs, d]), np.concatenate([obj_o, io]), np.concatenate([t_o, to])
+        c.tile = tuple(x[:N_TILE] for x in (org, dirs, obj_o, t_o))
+    return c.tile
+
+
+@pytest.mark.parametrize("key,engine_name", [("spheres", "ENGINE_AUTO"), ("cornell", "ENGINE_LIST"), ("cornell", "ENGINE_TWO_PHASE")])
+def test_host_pointer_calls_of_one_two_and_three_staging_trips(amber, key, engine_name):
+    """ray[i] = base[i % 100 003]: the expectation is tiled the same way and costs the oracle 10^5 rays.  One handle answers every count with occluded
+    first (its output buffer grows from 1 byte a ray to 32), a second one with cast first and the counts from the largest down; each then answers 65 rays."""
+    c = _case(amber, key)
+    org, dirs, obj_o, t_o = tile_base(c)
+    tm = mixed_t_max(t_o)
+    exp = expected(obj_o, t_o, tm)
+    assert exp[0].sum() > 10_000 and (~exp[0]).sum() > 10_000
+    n_max = max(TRIP_COUNTS)
+    idx = np.arange(n_max) % N_TILE
+    packed = pack_rays(amber, org, dirs, tm)[idx]
+    tiled = tuple(x[idx] for x in exp)
+    bufs = (np.empty(n_max + GUARD, amber.api._RAY_HIT), np.empty(n_max + GUARD, np.uint8))
+    for first, counts in (("occluded", TRIP_COUNTS), ("cast", TRIP_COUNTS[::-1])):
+        pt = c.tracer(getattr(amber, engine_name))
+        for n in counts + (65,):
+            label = f"{c.name}, {engine_name}, {first} first, {n} rays"
+            hits, occ = guarded_queries(amber, pt, packed, n, first, bufs)
+            check_batch(label, hits, occ, tuple(x[:n] for x in tiled))
+            records = hits.view(np.uint8).reshape(n, 32)                        # position and normal too: every trip repeats the first one's records
+            assert np.array_equal(records, records[:N_TILE][idx[:n]]), label
+        pt.close()
+
+
 # ---- torch tensors, the device-pointer path, memory, the product library, speed: child processes (torch's runtime up before the engine's library) ------
 TORCH_CHILD = r"""
 import os, sys, json
@@ -290,7 +438,7 @@ o, d = _random_rays(rec["A"], 1_000_000, 17)
 tm = np.random.default_rng(1).uniform(0.2, 3.0, len(o)).astype(np.float32); tm[::5] = np.inf; tm[1::50] = np.nan
 same = lambda x, y: all(np.ascontiguousarray(p).tobytes() == np.ascontiguousarray(q).tobytes() for p, q in zip(x, y))
 cpu = lambda ts: [t.cpu().numpy() for t in ts]
-ident = {{}}
+ident, batches = {{}}, {{}}
 for name, hs, engine in (("bvh", hs_a, A.ENGINE_AUTO), ("cornell", A.HostScene.cornell_box(), A.ENGINE_AUTO), ("ref_bvh", hs_a, A.ENGINE_REFERENCE_BVH)):
     pt = A.PathTracer(hs, A.Sensor.default(64, 64), engine=engine)
     to, td, tt = (torch.from_numpy(x).to(dev) for x in (o, d, tm))
@@ -303,8 +451,14 @@ for name, hs, engine in (("bvh", hs_a, A.ENGINE_AUTO), ("cornell", A.HostScene.c
                 got, occ = pt.cast_rays(to, td, tt), pt.occluded(to, td, tt)
             stream.synchronize()
         ident[name].append(bool(same(cpu(got), pt.cast_rays(o, d, tm)) and np.array_equal(occ.cpu().numpy(), pt.occluded(o, d, tm))))
+    for n in ((1 << 20) + 1, 257):                                               # two staging trips on the host side; a block and one ray
+        k = np.arange(n) % len(o)
+        o2, d2, t2 = o[k], d[k], tm[k]
+        got, occ = pt.cast_rays(*(torch.from_numpy(x).to(dev) for x in (o2, d2, t2))), pt.occluded(*(torch.from_numpy(x).to(dev) for x in (o2, d2, t2)))
+        batches.setdefault(name, []).append(bool(len(occ) == n and same(cpu(got), pt.cast_rays(o2, d2, t2)) and np.array_equal(occ.cpu().numpy(), pt.occluded(o2, d2, t2))))
     pt.close()
 out["torch_equals_numpy"] = ident
+out["device_pointer_batches"] = batches
 
 # a query enqueued before an update answers for the old scene, one after it for the new scene (device pointers: nothing waits in between)
 lib = A.load_library()
@@ -354,6 +508,9 @@ def test_torch_tensors_device_pointers_ordering_and_memory(amber):
     print("\n" + json.dumps({k: v for k, v in res.items() if k != "growth"}))
     for name, flags in res["torch_equals_numpy"].items():
         assert flags == [True, True], name                                     # the device-pointer path and AMBER_RAYS_HOST: identical bytes
+    assert set(res["device_pointer_batches"]) == {"bvh", "cornell", "ref_bvh"}
+    for name, flags in res["device_pointer_batches"].items():
+        assert flags == [True, True], name                                     # 2^20 + 1 and 257 rays through device pointers: the AMBER_RAYS_HOST bytes
     for mode, (old_scene, new_scene, scenes_differ) in res["order"].items():
         assert old_scene and new_scene and scenes_differ, mode
     for name, free in res["growth"].items():
