@@ -113,7 +113,7 @@ UPDATE_REFIT, UPDATE_REBUILD = 0, 1     # amber_hip_pt_update_objects: keep the 
 # every symbol include/amber_hip.h and include/amber_host.h declare: what libamber_hip.so (the product) exports
 ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
-    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects",
+    "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_update_lens",
     "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_destroy",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
@@ -173,6 +173,8 @@ def load_library() -> C.CDLL:
         lib.amber_hip_pt_build_info.argtypes = [vp, C.POINTER(BuildInfo)]
     if hasattr(lib, "amber_hip_pt_update_objects"):
         lib.amber_hip_pt_update_objects.argtypes = [vp, u32, u32, vp, u32, C.POINTER(UpdateInfo)]
+    if hasattr(lib, "amber_hip_pt_update_lens"):
+        lib.amber_hip_pt_update_lens.argtypes = [vp, C.POINTER(FlatThinLens), vp, u32, C.POINTER(UpdateInfo)]
     if hasattr(lib, "amber_hip_pt_cast_rays"):
         lib.amber_hip_pt_cast_rays.argtypes = [vp, u64, vp, vp, u32]
         lib.amber_hip_pt_occluded.argtypes = [vp, u64, vp, vp, u32]
@@ -433,6 +435,28 @@ class PathTracer:
             assert records.itemsize == C.sizeof(FlatObject)
             ptr, n = records.ctypes.data, len(records) if count is None else count
         _check(load_library().amber_hip_pt_update_objects(self._h, first, n, ptr, mode, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in UpdateInfo._fields_}
+
+    def update_lens(self, scene_or_lens, mode: int = UPDATE_REFIT) -> dict:
+        """amber_hip_pt_update_lens: the camera of a live handle moved.  scene_or_lens is a HostScene -- the same scene with another lens; it is
+        flattened and its lens and blade records are taken -- or an explicit (FlatThinLens, records) pair, records being the lens's n_blades
+        AmberFlatObject records (HostScene.flatten()'s layout; None passes a null pointer, as a None lens does).  Engine BVH's tree is refitted
+        (UPDATE_REFIT) or rebuilt (UPDATE_REBUILD) on the device.  Returns AmberUpdateInfo as a dict, like update_objects.  The framebuffer is
+        not cleared."""
+        if isinstance(scene_or_lens, HostScene):
+            objs, _, lens = scene_or_lens.flatten()
+            records = np.frombuffer(objs, dtype=_RECORD)[lens.first_blade_object:lens.first_blade_object + lens.n_blades].copy()
+        else:
+            lens, records = scene_or_lens
+        ptr = None
+        if records is not None:
+            records = np.ascontiguousarray(records)
+            assert records.itemsize == C.sizeof(FlatObject)
+            if lens is not None and len(records) < lens.n_blades:
+                raise AmberError(f"update_lens: {len(records)} blade records for a lens of {lens.n_blades} blades")
+            ptr = records.ctypes.data
+        info = UpdateInfo()
+        _check(load_library().amber_hip_pt_update_lens(self._h, C.byref(lens) if lens is not None else None, ptr, mode, C.byref(info)))
         return {k: getattr(info, k) for k, _ in UpdateInfo._fields_}
 
     # ---- the caller's own rays ----------------------------------------------------------------

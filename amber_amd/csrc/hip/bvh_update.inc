@@ -1,5 +1,5 @@
 // bvh_update.inc -- amber_hip_pt_update_objects: new geometry for the objects of a live handle, and engine BVH's tree made valid again on the
-// device.  Part of the one translation unit pt_host.hip; uses the kernels and the scratch of bvh_device_build.inc.
+// device; amber_hip_pt_update_lens: the same for the aperture blades, with the lens they belong to (UpdateLens, at the end).  Part of the one translation unit pt_host.hip; uses the kernels and the scratch of bvh_device_build.inc.
 //
 // An update is always a pass over the WHOLE scene: the sphere slack 16 eps D^2 and the needle reach depend on the scene diagonal, so when one
 // object moves the widened box of every object may change, and the binary16 grid changes with the bounds, so every plane word changes.  Only
@@ -190,21 +190,31 @@ int RefitTree(amber_hip_pt* h, const DevObject* objs, const float bmn[3], const 
 
 }  // namespace dupd
 
-int UpdateObjects(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode, AmberUpdateInfo* info) {
+// amber_hip_pt_update_lens: what the handle's lens becomes at the commit point of the update that carries its blade records
+struct LensChange {
+  DevLens lens;
+  std::vector<DevBlade> blades;
+  float aperture_rect[4][3];
+};
+constexpr size_t kLensBladesOffset = (sizeof(DevLens) + 15u) / 16u * 16u;
+
+// amber_hip_pt_update_objects (lens_change == nullptr), and amber_hip_pt_update_lens: the same update with the blade records as the changed objects
+// and the new lens swapped in at the same commit point.  t0: when the public call began (update_ms).
+int UpdateScene(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode, AmberUpdateInfo* info,
+                const LensChange* lens_change, const std::string& who, std::chrono::steady_clock::time_point t0) {
   using namespace dupd;
-  const auto t0 = std::chrono::steady_clock::now();
-  if (mode != AMBER_UPDATE_REFIT && mode != AMBER_UPDATE_REBUILD) return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: unknown mode " + std::to_string(mode));
+  if (mode != AMBER_UPDATE_REFIT && mode != AMBER_UPDATE_REBUILD) return Fail(AMBER_EINVAL, who + ": unknown mode " + std::to_string(mode));
 #if AMBER_BVH_WIDE
-  return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: not in an AMBER_BVH_WIDE measurement build (the device writes 2-wide nodes only): re-create the handle");
+  return Fail(AMBER_EINVAL, who + ": not in an AMBER_BVH_WIDE measurement build (the device writes 2-wide nodes only): re-create the handle");
 #endif
   if (h->hit_engine != AMBER_ENGINE_BVH || h->engine == AMBER_ENGINE_WAVEFRONT)
-    return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: only engine BVH's tree is updated on the device (AUTO past 80 objects, AMBER_ENGINE_BVH); with this "
+    return Fail(AMBER_EINVAL, who + ": only engine BVH's tree is updated on the device (AUTO past 80 objects, AMBER_ENGINE_BVH); with this "
                               "handle's engine a create costs no more than an update would: re-create the handle");
   DevScene& sc = h->scene;
   const uint32_t n = sc.n_objects;
-  if (first > n || count > n - first) return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: objects [" + std::to_string(first) + ", " + std::to_string(uint64_t(first) + count) +
+  if (first > n || count > n - first) return Fail(AMBER_EINVAL, who + ": objects [" + std::to_string(first) + ", " + std::to_string(uint64_t(first) + count) +
                                                                 ") are not all in the scene (" + std::to_string(n) + " objects)");
-  if (count && !objects) return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: null objects");
+  if (count && !objects) return Fail(AMBER_EINVAL, who + ": null objects");
   auto fill = [&](uint32_t mode_used, uint32_t reason, float before) {
     if (!info) return;
     info->mode_used = mode_used; info->fallback_reason = reason; info->n_nodes = h->build.n_nodes; info->depth = h->build.depth;
@@ -222,12 +232,12 @@ int UpdateObjects(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFl
     return AMBER_OK;
   }
 
-  // the aperture blades stay what they are (lens, DevBlade and p_area derive from them); does a light's object change?
-  const uint32_t n_blades = static_cast<uint32_t>(h->blade_records.size());
+  // the aperture blades stay what they are unless their lens comes with them (lens, DevBlade and p_area derive from them); does a light's object change?
+  const uint32_t n_blades = lens_change ? 0u : static_cast<uint32_t>(h->blade_records.size());
   for (uint32_t b = 0; b < n_blades; b++) {
     const uint32_t i = h->first_blade + b;
     if (i - first < count && std::memcmp(&objects[i - first], &h->blade_records[b], sizeof(AmberFlatObject)) != 0)
-      return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: object " + std::to_string(i) + " is an aperture blade and its record differs from the resident one (the lens is not part of an update)");
+      return Fail(AMBER_EINVAL, who + ": object " + std::to_string(i) + " is an aperture blade and its record differs from the resident one (the lens and its blades change through amber_hip_pt_update_lens)");
   }
   bool lights_change = false;
   for (size_t l = 0; l < h->light_object.size() && !lights_change; l++) {
@@ -251,13 +261,24 @@ int UpdateObjects(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFl
   hipLaunchKernelGGL(dbuild::db_init, dim3(1), dim3(64), 0, st, s.red.p);
   hipLaunchKernelGGL(bu_convert, dim3((count + 255u) / 256u), dim3(256), 0, st, const_cast<const AmberFlatObject*>(s.staged.p), first, count, sc.objects, fresh, n, s.red.p);
   HIP_TRY(hipGetLastError());
+  uint8_t* fresh_lens = nullptr;                               // ... and the new lens and blades, into the buffer no enqueued pass reads
+  if (lens_change) {
+    const size_t blade_bytes = lens_change->blades.size() * sizeof(DevBlade);
+    DevBuf<uint8_t>& buf = h->lens_alt[h->lens_alt_next];
+    HIP_TRY(buf.need(kLensBladesOffset + blade_bytes));
+    h->lens_stage.assign(kLensBladesOffset + blade_bytes, 0);
+    std::memcpy(h->lens_stage.data(), &lens_change->lens, sizeof(DevLens));
+    std::memcpy(h->lens_stage.data() + kLensBladesOffset, lens_change->blades.data(), blade_bytes);
+    HIP_TRY(hipMemcpyAsync(buf.p, h->lens_stage.data(), h->lens_stage.size(), hipMemcpyHostToDevice, st));
+    fresh_lens = buf.p;
+  }
 
   const DevScene saved = sc;                                   // (restored on every refusal below: all or nothing)
   const auto refused = [&](const dbuild::Reduced& red) -> int {
     sc = saved;
     if (red.bad_index != kNoParent)
-      return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: object " + std::to_string(red.bad_index) + ": kind or material differs from the resident record's (an update moves geometry only)");
-    return Fail(AMBER_EINVAL, "amber_hip_pt_update_objects: the new scene has no finite bounds");
+      return Fail(AMBER_EINVAL, who + ": object " + std::to_string(red.bad_index) + ": kind or material differs from the resident record's (an update moves geometry only)");
+    return Fail(AMBER_EINVAL, who + ": the new scene has no finite bounds");
   };
   uint32_t mode_used = mode, reason = AMBER_BUILD_REASON_NONE;
   dbuild::Reduced red;
@@ -301,12 +322,46 @@ int UpdateObjects(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFl
   h->objects_buf.swap(h->objects_alt);
   sc.objects = fresh;
   h->lights_stale = h->lights_stale || lights_change;
+  if (lens_change) {                                           // the host's readers of the lens (h->lens, aperture_rect, blade_records) see the new one from here on
+    sc.lens = reinterpret_cast<const DevLens*>(fresh_lens);
+    sc.blades = reinterpret_cast<const DevBlade*>(fresh_lens + kLensBladesOffset);
+    h->lens_alt_next ^= 1u;
+    h->lens = lens_change->lens;
+    std::memcpy(h->aperture_rect, lens_change->aperture_rect, sizeof h->aperture_rect);
+    h->blade_records.assign(objects, objects + count);
+  }
   { const int rc = QueueArea(h, 1); if (rc != AMBER_OK) return rc; }
   HIP_TRY(hipStreamSynchronize(st));                           // the second and last wait: the caller's records have been read, update_ms covers the work
   s.retired_nodes.reset();
   h->tree_area = AreaOf(h, 1); h->area_known = true;
   fill(mode_used, reason, area_before);
   return AMBER_OK;
+}
+
+int UpdateObjects(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode, AmberUpdateInfo* info) {
+  return UpdateScene(h, first, count, objects, mode, info, nullptr, "amber_hip_pt_update_objects", std::chrono::steady_clock::now());
+}
+
+// The lens of a live handle replaced: the values create derives from it come from create's own function (amber_prep::DeriveLens), the blades'
+// scene objects go through the update above -- bu_convert writes them into the scene-order array, db_gather into the leaf-order arrays at the
+// slots the tree uses, the whole-scene pass makes every box valid for the new bounds -- and the lens changes at that update's commit point.
+int UpdateLens(amber_hip_pt* h, const AmberFlatThinLens* lens, const AmberFlatObject* blades, uint32_t mode, AmberUpdateInfo* info) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string who = "amber_hip_pt_update_lens";
+  if (!lens || !blades) return Fail(AMBER_EINVAL, who + ": null lens or blades");
+  if (h->hit_engine != AMBER_ENGINE_BVH || h->engine == AMBER_ENGINE_WAVEFRONT || AMBER_BVH_WIDE)   // (UpdateScene's refusals, before the lens is looked at)
+    return UpdateScene(h, h->first_blade, static_cast<uint32_t>(h->blade_records.size()), blades, mode, info, nullptr, who, t0);
+  const uint32_t n_blades = static_cast<uint32_t>(h->blade_records.size());
+  if (lens->kind != h->lens.kind || lens->n_blades != n_blades || lens->first_blade_object != h->first_blade)
+    return Fail(AMBER_EINVAL, who + ": kind " + std::to_string(lens->kind) + ", n_blades " + std::to_string(lens->n_blades) + ", first_blade_object " +
+                                  std::to_string(lens->first_blade_object) + " differ from the resident lens's (" + std::to_string(h->lens.kind) + ", " + std::to_string(n_blades) +
+                                  ", " + std::to_string(h->first_blade) + "): a lens update keeps them; re-create the handle");
+  for (uint32_t b = 0; b < n_blades; b++)
+    if (blades[b].kind != AMBER_PRIM_TRIANGLE || blades[b].material != h->blade_records[b].material)
+      return Fail(AMBER_EINVAL, who + ": blade " + std::to_string(b) + " is not a triangle of the resident blade's material");
+  LensChange change;
+  amber_prep::DeriveLensOfState(*h, *lens, blades, change.lens, change.blades, change.aperture_rect);
+  return UpdateScene(h, h->first_blade, n_blades, blades, mode, info, &change, who, t0);
 }
 
 }  // namespace

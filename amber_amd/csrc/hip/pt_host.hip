@@ -158,7 +158,12 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   bool has_spheres = false;
   uint32_t small_kinds[3] = {0, 0, 0};      // kinds of a scene that is one leaf
   uint32_t first_blade = 0;
-  std::vector<AmberFlatObject> blade_records;   // the aperture blades as create received them (an update must leave them as they are)
+  std::vector<AmberFlatObject> blade_records;   // the aperture blades as create or the last amber_hip_pt_update_lens received them (an update of objects must leave them as they are)
+  // ---- amber_hip_pt_update_lens: a DevLens and, kLensBladesOffset bytes behind it, the DevBlade array.  A lens update fills the buffer not in use
+  // and commits by pointing scene.lens / scene.blades at it (create's own copies are in scene_arrays); passes enqueued before keep the old pointers
+  DevBuf<uint8_t> lens_alt[2];
+  uint32_t lens_alt_next = 0;
+  std::vector<uint8_t> lens_stage;          // the host image of that buffer: lives until the copy has been waited for
   std::vector<uint32_t> light_object;       // object of every light, and its parameters as the lights table was computed from them
   std::vector<float> light_p;
   bool lights_stale = false;                // an update has changed an object the lights table names: light tracing needs a new handle
@@ -966,6 +971,15 @@ int amber_hip_pt_update_objects(amber_hip_pt* h, uint32_t first, uint32_t count,
     return UpdateObjects(h, first, count, objects, mode, info);
   } catch (const std::bad_alloc&) {
     return Fail(AMBER_ENOMEM, "amber_hip_pt_update_objects: out of host memory");
+  }
+}
+
+int amber_hip_pt_update_lens(amber_hip_pt* h, const AmberFlatThinLens* lens, const AmberFlatObject* blades, uint32_t mode, AmberUpdateInfo* info) {
+  if (!h) return Fail(AMBER_EINVAL, "null handle");
+  try {
+    return UpdateLens(h, lens, blades, mode, info);
+  } catch (const std::bad_alloc&) {
+    return Fail(AMBER_ENOMEM, "amber_hip_pt_update_lens: out of host memory");
   }
 }
 

@@ -133,6 +133,82 @@ inline void SetBvhRayMargin(DevScene& sc, const float bounds_min[3], const float
 }
 
 
+// Everything create derives from the lens and its aperture blades alone (the sensor and the two-phase model box given): the DevLens record with
+// its constants, the DevBlade array and the aperture's bounding rectangle.  amber_hip_pt_create (PrepareScene) and amber_hip_pt_update_lens
+// (DeriveLensOfState) both come here, so the two cannot drift.  blade_records: L.n_blades records, the scene objects [L.first_blade_object, ...).
+// A blade's filter-program slot is the two-phase engines' (PrepareScene assigns it); it is -1 here and stays -1 on engine BVH.
+// lens and aperture_rect are written in place (the record is cleared first, padding included).
+inline void DeriveLens(const AmberFlatThinLens& L, const AmberFlatObject* blade_records, const AmberSensor& sensor, const float fp_center[3], float fp_reach,
+                       DevLens& lens, std::vector<DevBlade>& blades, float aperture_rect[4][3]) {
+  blades.resize(L.n_blades);
+  for (uint32_t i = 0; i < L.n_blades; i++) {
+    const AmberFlatObject& f = blade_records[i];
+    for (int c = 0; c < 3; c++) { blades[i].v0[c] = f.p[c]; blades[i].v1[c] = f.p[3 + c]; blades[i].v2[c] = f.p[6 + c]; blades[i].n[c] = f.p[9 + c]; }
+    blades[i].slot = -1; blades[i].pad[0] = blades[i].pad[1] = blades[i].pad[2] = 0;
+  }
+  {
+    // bounding rectangle of the aperture in the lens plane (lens-local x, y; the blades lie in z = 0), inflated, as four world points
+    double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
+    for (const DevBlade& bl : blades)
+      for (const float* v : {bl.v0, bl.v1, bl.v2}) {
+        const double r[3] = {double(v[0]) - L.origin[0], double(v[1]) - L.origin[1], double(v[2]) - L.origin[2]};
+        for (int c = 0; c < 2; c++) {
+          const double x = L.local_[3 * c] * r[0] + L.local_[3 * c + 1] * r[1] + L.local_[3 * c + 2] * r[2];
+          lo[c] = std::min(lo[c], x); hi[c] = std::max(hi[c], x);
+        }
+      }
+    double world_mag = 0;
+    for (int c = 0; c < 3; c++) world_mag = std::max({world_mag, std::fabs(double(fp_center[c])) + fp_reach, std::fabs(double(L.origin[c]))});
+    for (int c = 0; c < 2; c++) { const double m = 1e-3 * (hi[c] - lo[c]) + 1e-6 + 1e-5 * fp_reach + 32.0 * 5.9604644775390625e-08 * world_mag; lo[c] -= m; hi[c] += m; }
+    for (int i = 0; i < 4; i++) {
+      const double x = (i & 1) ? hi[0] : lo[0], y = (i & 2) ? hi[1] : lo[1];
+      for (int c = 0; c < 3; c++) aperture_rect[i][c] = static_cast<float>(L.origin[c] + (L.kind == AMBER_LENS_PINHOLE ? 0.0 : L.global_[3 * c] * x + L.global_[3 * c + 1] * y));
+    }
+  }
+  std::memset(&lens, 0, sizeof lens);
+  std::memcpy(lens.origin, L.origin, sizeof L.origin);
+  std::memcpy(lens.global_, L.global_, sizeof L.global_);
+  std::memcpy(lens.local_, L.local_, sizeof L.local_);
+  lens.focus_distance = L.focus_distance; lens.sensor_distance = L.sensor_distance; lens.p_area = L.p_area;
+  { volatile float q = -L.focus_distance / L.sensor_distance; lens.neg_fd_over_sd = q; }
+  {
+    // sensor.Size() / sensor.SceneArea(): uint -> float, float*float, float/float (lens_thin.cc:145, sensor.cc:40-50)
+    volatile float size_f = static_cast<float>(static_cast<uint64_t>(sensor.width) * sensor.height);
+    volatile float area = sensor.scene_width * sensor.scene_height;
+    volatile float r = size_f / area;
+    lens.size_over_area = r;
+  }
+  lens.sd2 = static_cast<double>(L.sensor_distance) * static_cast<double>(L.sensor_distance);
+  lens.n_blades = L.n_blades; lens.n_blades_f = static_cast<float>(L.n_blades);
+  lens.kind = L.kind;
+  { volatile float area = sensor.scene_width * sensor.scene_height; volatile float inv = 1.0f / area; lens.inv_scene_area = inv; }
+  { volatile float q = -L.sensor_distance / L.focus_distance; lens.neg_sd_over_fd = q; }
+  {
+    // a ray that starts on blade b is seen by another blade's exact test only if its origin lies within the rounding of WORLD
+    // coordinates of that blade: a few ulp of the lens position, in units of the blade's size
+    double world_mag = 0, min_edge = 1e300;
+    for (int c = 0; c < 3; c++) world_mag = std::max(world_mag, std::fabs(double(L.origin[c])));
+    for (const DevBlade& bl : blades) {
+      const float* v[3] = {bl.v0, bl.v1, bl.v2};
+      for (int k = 0; k < 3; k++) {
+        double e2 = 0;
+        for (int c = 0; c < 3; c++) { const double e = double(v[k][c]) - v[(k + 1) % 3][c]; e2 += e * e; world_mag = std::max(world_mag, std::fabs(double(v[k][c]))); }
+        min_edge = std::min(min_edge, std::sqrt(e2));
+      }
+    }
+    const double tol = min_edge > 0 ? std::max(1e-3, 64.0 * 5.9604644775390625e-08 * world_mag / min_edge) : 1.0;
+    lens.edge_tol = static_cast<float>(std::min(1.0, tol));
+  }
+}
+
+// The same records for a new lens on a resident scene (amber_hip_pt_update_lens): the sensor is the handle's, and so is the two-phase model box --
+// engine BVH, the only engine whose handles take a lens update, reads neither the box nor the rectangle whose margin derives from it.
+inline void DeriveLensOfState(const SceneState& st, const AmberFlatThinLens& L, const AmberFlatObject* blade_records,
+                              DevLens& lens, std::vector<DevBlade>& blades, float aperture_rect[4][3]) {
+  const AmberSensor sensor{st.scene.sensor.w, st.scene.sensor.h, st.scene.sensor.sw, st.scene.sensor.sh};
+  DeriveLens(L, blade_records, sensor, st.scene.fp_center, st.scene.fp_reach, lens, blades, aperture_rect);
+}
+
 struct PreparedScene : SceneState {
   std::string error;                         // not empty: create refuses the scene (AMBER_EINVAL) with this message
   bool bvh_pending = false;                  // AMBER_PT_FLAG_DEVICE_BUILD on engine BVH: no tree yet -- create builds it on the device (bvh_device_build.inc) or calls HostBvh
@@ -255,12 +331,6 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
   }
   const AmberFlatThinLens& L = s->lens;
   std::vector<DevBlade>& blades = p.blades;
-  blades.resize(L.n_blades);
-  for (uint32_t i = 0; i < L.n_blades; i++) {
-    const AmberFlatObject& f = s->objects[L.first_blade_object + i];
-    for (int c = 0; c < 3; c++) { blades[i].v0[c] = f.p[c]; blades[i].v1[c] = f.p[3 + c]; blades[i].v2[c] = f.p[6 + c]; blades[i].n[c] = f.p[9 + c]; }
-    blades[i].slot = -1; blades[i].pad[0] = blades[i].pad[1] = blades[i].pad[2] = 0;
-  }
 
   // AUTO: <= 32 objects the two-phase engine; up to env.two_phase_auto its grouped form (one Phase-A program per 32 objects: cheaper than a per-lane
   // tree traversal while the groups are few -- tools/object_count_curve.py); beyond that engine BVH.  Asked for explicitly, two-phase takes up to 128 objects.
@@ -308,6 +378,7 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
     for (int c = 0; c < 3; c++) { fp_center[c] = static_cast<float>(0.5 * (lo[c] + hi[c])); reach = std::max(reach, 0.5 * (hi[c] - lo[c])); }
     fp_reach = static_cast<float>(std::min(3.0e38, 2.0 * reach + 1e-3));
   }
+  DeriveLens(L, s->objects + L.first_blade_object, *sensor, fp_center, fp_reach, p.lens, blades, p.aperture_rect);   // (the blades' slots follow below)
   std::vector<amber_filter::FilterProgram> more_progs;          // engine TWO_PHASE_N: the programs of groups 1, 2, ... (fprog is group 0's)
   if (p.hit_engine == kHitTwoPhaseN) {
     // groups of 32 in scene order, the aperture blades first (the primary rounds' masks and the blades' own slots live in group 0)
@@ -393,64 +464,11 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
   sc.n_groups = static_cast<uint32_t>(p.groups.empty() ? 1 : p.groups.size()); sc.n_lds_objects = static_cast<uint32_t>(prog.size());
   sc.blade_mask = 0u;
   for (const DevBlade& bl : blades) if (bl.slot >= 0 && bl.slot < 32) sc.blade_mask |= 1u << bl.slot;
-  {
-    // bounding rectangle of the aperture in the lens plane (lens-local x, y; the blades lie in z = 0), inflated, as four world points
-    double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
-    for (const DevBlade& bl : blades)
-      for (const float* v : {bl.v0, bl.v1, bl.v2}) {
-        const double r[3] = {double(v[0]) - L.origin[0], double(v[1]) - L.origin[1], double(v[2]) - L.origin[2]};
-        for (int c = 0; c < 2; c++) {
-          const double x = L.local_[3 * c] * r[0] + L.local_[3 * c + 1] * r[1] + L.local_[3 * c + 2] * r[2];
-          lo[c] = std::min(lo[c], x); hi[c] = std::max(hi[c], x);
-        }
-      }
-    double world_mag = 0;
-    for (int c = 0; c < 3; c++) world_mag = std::max({world_mag, std::fabs(double(fp_center[c])) + fp_reach, std::fabs(double(L.origin[c]))});
-    for (int c = 0; c < 2; c++) { const double m = 1e-3 * (hi[c] - lo[c]) + 1e-6 + 1e-5 * fp_reach + 32.0 * 5.9604644775390625e-08 * world_mag; lo[c] -= m; hi[c] += m; }
-    for (int i = 0; i < 4; i++) {
-      const double x = (i & 1) ? hi[0] : lo[0], y = (i & 2) ? hi[1] : lo[1];
-      for (int c = 0; c < 3; c++) p.aperture_rect[i][c] = static_cast<float>(L.origin[c] + (L.kind == AMBER_LENS_PINHOLE ? 0.0 : L.global_[3 * c] * x + L.global_[3 * c + 1] * y));
-    }
-  }
   sc.n_objects = s->n_objects; sc.max_depth = params->max_depth;
-  DevLens& lens = p.lens;
-  std::memcpy(lens.origin, L.origin, sizeof L.origin);
-  std::memcpy(lens.global_, L.global_, sizeof L.global_);
-  std::memcpy(lens.local_, L.local_, sizeof L.local_);
-  lens.focus_distance = L.focus_distance; lens.sensor_distance = L.sensor_distance; lens.p_area = L.p_area;
-  { volatile float q = -L.focus_distance / L.sensor_distance; lens.neg_fd_over_sd = q; }
-  {
-    // sensor.Size() / sensor.SceneArea(): uint -> float, float*float, float/float (lens_thin.cc:145, sensor.cc:40-50)
-    volatile float size_f = static_cast<float>(static_cast<uint64_t>(sensor->width) * sensor->height);
-    volatile float area = sensor->scene_width * sensor->scene_height;
-    volatile float r = size_f / area;
-    lens.size_over_area = r;
-  }
-  lens.sd2 = static_cast<double>(L.sensor_distance) * static_cast<double>(L.sensor_distance);
-  lens.n_blades = L.n_blades; lens.n_blades_f = static_cast<float>(L.n_blades);
-  lens.kind = L.kind;
-  { volatile float area = sensor->scene_width * sensor->scene_height; volatile float inv = 1.0f / area; lens.inv_scene_area = inv; }
   sc.sensor.w = sensor->width; sc.sensor.h = sensor->height;
   sc.sensor.wf = static_cast<float>(sensor->width); sc.sensor.hf = static_cast<float>(sensor->height);
   sc.sensor.sw = sensor->scene_width; sc.sensor.sh = sensor->scene_height;
   sc.sensor.size_f = static_cast<float>(static_cast<uint64_t>(sensor->width) * sensor->height);
-  { volatile float q = -L.sensor_distance / L.focus_distance; lens.neg_sd_over_fd = q; }
-  {
-    // a ray that starts on blade b is seen by another blade's exact test only if its origin lies within the rounding of WORLD
-    // coordinates of that blade: a few ulp of the lens position, in units of the blade's size
-    double world_mag = 0, min_edge = 1e300;
-    for (int c = 0; c < 3; c++) world_mag = std::max(world_mag, std::fabs(double(L.origin[c])));
-    for (const DevBlade& bl : blades) {
-      const float* v[3] = {bl.v0, bl.v1, bl.v2};
-      for (int k = 0; k < 3; k++) {
-        double e2 = 0;
-        for (int c = 0; c < 3; c++) { const double e = double(v[k][c]) - v[(k + 1) % 3][c]; e2 += e * e; world_mag = std::max(world_mag, std::fabs(double(v[k][c]))); }
-        min_edge = std::min(min_edge, std::sqrt(e2));
-      }
-    }
-    const double tol = min_edge > 0 ? std::max(1e-3, 64.0 * 5.9604644775390625e-08 * world_mag / min_edge) : 1.0;
-    lens.edge_tol = static_cast<float>(std::min(1.0, tol));
-  }
   return p;
 }
 

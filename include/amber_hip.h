@@ -32,7 +32,8 @@ extern "C" {
                                     amber_hip_pt_device_framebuffer() needs amber_hip_pt_sync() first when a launch may have run out of record slots.
                                     Still 3 with AMBER_PT_FLAG_DEVICE_BUILD and amber_hip_pt_build_info(): a flag bit that older libraries ignore and
                                     a new function; nothing that existed changed its layout or meaning.  Still 3 with amber_hip_pt_update_objects(): a new function.
-                                    Still 3 with amber_hip_pt_cast_rays() / amber_hip_pt_occluded(): two new functions and their two structs */
+                                    Still 3 with amber_hip_pt_cast_rays() / amber_hip_pt_occluded(): two new functions and their two structs.
+                                    Still 3 with amber_hip_pt_update_lens(): a new function */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -228,7 +229,7 @@ int  amber_hip_pt_build_info(amber_hip_pt*, AmberBuildInfo* out);
  *            replaced by it, amber_hip_pt_build_info then reports the new tree.  A Morton tree deeper than the traversal's limit is not used:
  *            the call refits the tree in use instead and says so (mode_used, fallback_reason).
  * Geometry only: every new record keeps the kind and the material of the one it replaces, and an aperture blade in the range must equal the
- * resident record bit for bit (the lens is not part of an update).  Objects with NaN parameters are accepted as create accepts them.
+ * resident record bit for bit (the lens and its blades change through amber_hip_pt_update_lens, below).  Objects with NaN parameters are accepted as create accepts them.
  * Lights: path tracing does not read the lights table, so emitting objects move like any other; but cum_power and pdf_area were computed by
  * the caller from the old geometry, so once the record of an object named by an AmberFlatLight has changed, amber_hip_lt_trace / _range
  * answer AMBER_EINVAL until the handle is re-created.
@@ -253,6 +254,30 @@ typedef struct {
 } AmberUpdateInfo;
 int  amber_hip_pt_update_objects(amber_hip_pt*, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode,
                                  AmberUpdateInfo* info /* may be NULL */);
+/* The camera of a live handle moved: a new lens and the new records of its aperture blades (blades[0 .. lens->n_blades), host memory; the blades
+ * are scene objects and sit in engine BVH's tree), and that tree made valid again on the device.  Afterwards the handle renders, light-traces and
+ * answers ray queries exactly as a handle created on the same scene with the new lens and the new blade records does, bit for bit: images, ray
+ * counts, amber_hip_lt_trace records, amber_hip_pt_cast_rays hits (the answer never depends on the tree).  Still ABI version 3: a new function.
+ * What may change: every value of AmberFlatThinLens -- origin, both matrices, focus_distance, sensor_distance, p_area -- and the geometry of the
+ * blades.  kind, n_blades and first_blade_object must equal the resident lens's, and every blade record stays a triangle of the resident
+ * blade's material; otherwise AMBER_EINVAL.  The arrays keep their sizes; nothing is reallocated in the steady state.  NaN values are accepted
+ * as create accepts them.  The sensor is not part of the call.  Everything create derives from the lens and the blades (the constants of the
+ * device's lens record, the blade array) is derived again by create's own function.
+ * Engines, modes, order and failure are amber_hip_pt_update_objects': it is that update with the blades as the changed objects, and the lens
+ * changes at its commit point.
+ *   Engines  only where the closest-hit engine is BVH (AUTO past 80 objects, AMBER_ENGINE_BVH).  LIST, TWO_PHASE, REFERENCE_BVH, the lab engine
+ *            WAVEFRONT and AMBER_BVH_WIDE measurement builds answer AMBER_EINVAL: re-create the handle (on LIST / TWO_PHASE the create is the update).
+ *   Modes    REFIT and REBUILD as above; a Morton tree deeper than the traversal's limit falls back to REFIT (mode_used, fallback_reason);
+ *            amber_hip_pt_build_info follows a REBUILD.
+ *   Cost     a pass over the WHOLE scene on the device, whatever moved: a camera that leaves the old bounds changes the scene diagonal and with it
+ *            every box and every plane word.  What amber_hip_pt_update_objects costs for n_blades objects in the same mode.
+ *   Order    stream-ordered after everything enqueued on the handle before it and before everything after; a pass or a ray query enqueued before
+ *            sees the old lens.  The framebuffer and the ray counter are NOT cleared.  The call waits for the handle's stream before it returns.
+ *   Failure  all or nothing on AMBER_EINVAL / AMBER_ENOMEM; after AMBER_EHIP the handle is to be destroyed.  A NULL lens or blades: AMBER_EINVAL.
+ * Lights: blades are never lights, so the lights table stays valid; amber_hip_lt_trace keeps working and its lens response uses the new lens.
+ * Later amber_hip_pt_update_objects calls whose range covers a blade compare against the records of the last lens update. */
+int  amber_hip_pt_update_lens(amber_hip_pt*, const AmberFlatThinLens* lens, const AmberFlatObject* blades /* lens->n_blades records, host memory */,
+                              uint32_t mode /* AMBER_UPDATE_REFIT | AMBER_UPDATE_REBUILD */, AmberUpdateInfo* info /* may be NULL */);
 /* The caller's own rays through the handle's closest-hit engine: Scene::Cast (cast_rays) and the visibility test built on it (occluded).  Still
  * ABI version 3: two new functions.
  *   cast_rays  hits[i] = what the handle's engine returns for Scene::Cast(rays[i]): LIST, TWO_PHASE (both forms) and BVH the closest finite hit, ties
@@ -265,7 +290,7 @@ int  amber_hip_pt_update_objects(amber_hip_pt*, uint32_t first, uint32_t count, 
  *   occluded   occluded[i] = 1 iff cast_rays on the same ray would report a hit, else 0.  Defined through the closest hit; computed by an any-hit walk
  *              where the engine has one (BVH: the walk ends at the first primitive hit with t <= t_max), by the closest hit elsewhere.
  * Memory: by default rays and the output are DEVICE pointers on the handle's device, and the call is asynchronous and stream-ordered on the
- * handle's stream like amber_hip_pt_render_pass: a query enqueued before amber_hip_pt_update_objects sees the old scene, one enqueued after it the
+ * handle's stream like amber_hip_pt_render_pass: a query enqueued before amber_hip_pt_update_objects / amber_hip_pt_update_lens sees the old scene, one enqueued after it the
  * new one; read the output after amber_hip_pt_sync, or from work enqueued on amber_hip_pt_stream.  With AMBER_RAYS_HOST both are HOST pointers: the
  * call stages through buffers the handle owns (a million rays at a time) and returns after the copy back.
  * Neither function touches the framebuffer, the ray counter or amber_hip_pt_kernel_time.  Scratch (engine BVH's traversal stacks and work counter,
