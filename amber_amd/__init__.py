@@ -28,6 +28,11 @@ from .api import (  # noqa: F401
     UPDATE_REBUILD,
     UpdateInfo,
     RAYS_HOST,
+    RESOLVE_MEAN_F32,
+    RESOLVE_RGB8,
+    RESOLVE_RGBA8,
+    RESOLVE_HOST,
+    RESOLVE_MIRROR_X,
     Ray,
     RayHit,
     AmberError,

@@ -108,13 +108,15 @@ BUILD_REASON_NONE, BUILD_REASON_DEPTH, BUILD_REASON_WIDE, BUILD_REASON_BOUNDS = 
 RAYS_HOST = 1                # amber_hip_pt_cast_rays / amber_hip_pt_occluded: rays and output are host pointers
 _RAY = np.dtype([("origin", np.float32, (3,)), ("t_max", np.float32), ("dir", np.float32, (3,)), ("pad", np.uint32)])       # AmberRay
 _RAY_HIT = np.dtype([("t", np.float32), ("object", np.int32), ("pos", np.float32, (3,)), ("normal", np.float32, (3,))])    # AmberRayHit
+RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8 = 0, 1, 2     # amber_hip_pt_resolve: format
+RESOLVE_HOST, RESOLVE_MIRROR_X = 1, 2                        # ... and flags: out is a host pointer / columns written right to left
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1     # amber_hip_pt_update_objects: keep the tree's topology and recompute its boxes / build the Morton tree again
 
 # every symbol include/amber_hip.h and include/amber_host.h declare: what libamber_hip.so (the product) exports
 ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
     "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_update_lens",
-    "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_destroy",
+    "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_resolve", "amber_hip_pt_destroy",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -178,6 +180,8 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "amber_hip_pt_cast_rays"):
         lib.amber_hip_pt_cast_rays.argtypes = [vp, u64, vp, vp, u32]
         lib.amber_hip_pt_occluded.argtypes = [vp, u64, vp, vp, u32]
+    if hasattr(lib, "amber_hip_pt_resolve"):
+        lib.amber_hip_pt_resolve.argtypes = [vp, u32, u32, vp, u64, u32]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -537,6 +541,35 @@ class PathTracer:
     def _torch_leave(self, same: bool) -> None:
         if not same:
             self.sync()
+
+    def resolve(self, n_samples: int, format: int = RESOLVE_RGB8, mirror: bool = False, out=None):
+        """amber_hip_pt_resolve: the band's sums divided by n_samples (RESOLVE_MEAN_F32: float32, 3 channels) or taken through Filmic + Gamma 2.2 to
+        8 bits (RESOLVE_RGB8: uint8, 3 channels; RESOLVE_RGBA8: uint8, 4 channels, alpha 255) on the device; the bytes equal tonemap(sum / n).
+        mirror: columns written right to left, as the PNG / EXR writers do.
+
+        out=None: returns a numpy array of shape band_shape[:2] + (3 or 4,), through AMBER_RESOLVE_HOST (staged by the handle; the call returns
+        with the answer).  out = a contiguous torch tensor on the handle's device, of that dtype and exactly that many elements: zero-copy and
+        asynchronous on the handle's stream, `out` is returned.  ORDERING as cast_rays: under `with torch.cuda.stream(ExternalStream(pt.stream()))`
+        nothing is waited for; otherwise torch's current stream is waited for before the call and the handle's stream after it."""
+        if format not in (RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8):
+            raise AmberError(f"resolve: unknown format {format}")
+        rows, width, _ = self.band_shape
+        channels, flags = (4 if format == RESOLVE_RGBA8 else 3), (RESOLVE_MIRROR_X if mirror else 0)
+        lib = load_library()
+        if out is None:
+            res = np.empty((rows, width, channels), np.float32 if format == RESOLVE_MEAN_F32 else np.uint8)
+            _check(lib.amber_hip_pt_resolve(self._h, n_samples, format, res.ctypes.data, res.nbytes, flags | RESOLVE_HOST))
+            return res
+        if not self._is_torch(out):
+            raise AmberError("resolve: out must be None or a torch tensor on the handle's device")
+        import torch
+        dtype = torch.float32 if format == RESOLVE_MEAN_F32 else torch.uint8
+        if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or out.numel() != rows * width * channels:
+            raise AmberError(f"resolve: out must be a contiguous {dtype} tensor of {rows} x {width} x {channels} elements on the handle's device")
+        same = self._torch_enter(torch, out.device)
+        _check(lib.amber_hip_pt_resolve(self._h, n_samples, format, out.data_ptr(), out.numel() * out.element_size(), flags))
+        self._torch_leave(same)
+        return out
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

@@ -14,6 +14,8 @@
 //                          tree made valid again on the device: refitted (any tree, topology kept) or rebuilt (the Morton tree, in place).
 //   ray_query.inc          amber_hip_pt_cast_rays / amber_hip_pt_occluded: the caller's rays through the handle's engine -- engine BVH in a persistent refill
 //                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>.
+//   resolve.inc            amber_hip_pt_resolve: the framebuffer's sums as the mean or, through Filmic + Gamma, as 8-bit RGB / RGBA, in device memory --
+//                          a streaming kernel, four output pixels per thread, bytes equal to the host's output stage.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -178,6 +180,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<unsigned int> d_query_next;        // engine BVH: the work counter
   DevBuf<float4> d_query_rays;              // AMBER_RAYS_HOST: staging of the rays and of the results, at most kQueryStageRays rays
   DevBuf<uint8_t> d_query_out;
+  DevBuf<uint8_t> d_resolve_out;            // amber_hip_pt_resolve with AMBER_RESOLVE_HOST (resolve.inc): staging of the output, grown on first use and reused
   DevBuf<float> d_fb;
   DevBuf<unsigned long long> d_rays;
   DevBuf<unsigned int> d_next;
@@ -758,6 +761,7 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 }  // namespace
 
 #include "ray_query.inc"
+#include "resolve.inc"
 
 extern "C" {
 
@@ -989,6 +993,10 @@ int amber_hip_pt_cast_rays(amber_hip_pt* h, uint64_t n, const AmberRay* rays, Am
 
 int amber_hip_pt_occluded(amber_hip_pt* h, uint64_t n, const AmberRay* rays, uint8_t* occluded, uint32_t flags) {
   return RayQuery(h, n, rays, occluded, flags, true, "amber_hip_pt_occluded");
+}
+
+int amber_hip_pt_resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
+  return Resolve(h, n_samples, format, out, out_bytes, flags);
 }
 
 int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) {

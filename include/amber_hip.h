@@ -33,7 +33,7 @@ extern "C" {
                                     Still 3 with AMBER_PT_FLAG_DEVICE_BUILD and amber_hip_pt_build_info(): a flag bit that older libraries ignore and
                                     a new function; nothing that existed changed its layout or meaning.  Still 3 with amber_hip_pt_update_objects(): a new function.
                                     Still 3 with amber_hip_pt_cast_rays() / amber_hip_pt_occluded(): two new functions and their two structs.
-                                    Still 3 with amber_hip_pt_update_lens(): a new function */
+                                    Still 3 with amber_hip_pt_update_lens(): a new function.  Still 3 with amber_hip_pt_resolve(): a new function */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -302,6 +302,38 @@ typedef struct { float t; int32_t object; float pos[3]; float normal[3]; } Amber
 enum { AMBER_RAYS_HOST = 1u };   /* rays / out are host pointers: the call stages them and waits */
 int  amber_hip_pt_cast_rays(amber_hip_pt*, uint64_t n, const AmberRay* rays, AmberRayHit* hits, uint32_t flags);
 int  amber_hip_pt_occluded(amber_hip_pt*, uint64_t n, const AmberRay* rays, uint8_t* occluded, uint32_t flags);
+/* The output stage on the device: the framebuffer's sums as the mean image or as the 8-bit image the reference's command line writes
+ * (postprocess::Filmic, then postprocess::Gamma(2.2): filmic.cc:30-66, gamma.cc:36-52), without the round trip amber_hip_pt_download + a host tone
+ * map.  Covers every pixel of the handle's band in amber_hip_pt_download's layout: amber_hip_pt_local_rows rows in increasing y, compact, width
+ * pixels each.  Still ABI version 3: a new function.
+ * Arithmetic, with s the RGB sum of a pixel; every operation binary32 and rounded alone, in this order, per component:
+ *   mean   = s / (float)n_samples                               (what HipPathTracing::Render divides by)
+ *   AMBER_RESOLVE_MEAN_F32   writes mean: 3 floats, 12 bytes per pixel, NaN payloads as the division leaves them
+ *   mapped = Map(mean * 16) / Map(0.70f),  Map(h) = (h*(h*kA + kB*kC) + kD*kE) / (h*(h*kA + kB) + kD*kF) - kE/kF   (the constant products and
+ *            kE/kF are binary32 constants; kA .. kF = 0.22, 0.30, 0.10, 0.20, 0.01, 0.30)
+ *   v      = 255 * min(1, powf(mapped, 1 / 2.2f)),  min(1, p) = (p < 1) ? p : 1 -- std::min<float>(1, p): a NaN p gives 1
+ *   byte   = v >= 0 ? (uint8_t)v : 0                            (truncation)
+ *   AMBER_RESOLVE_RGB8       3 bytes per pixel: R, G, B
+ *   AMBER_RESOLVE_RGBA8      4 bytes per pixel: R, G, B, 255 -- one aligned 32-bit word, the layout of a display surface
+ * Negative, NaN and infinite means therefore give 255, as they do on the host.  The bytes EQUAL those of the host's output stage (amber_host_tonemap,
+ * the reference's Filmic + Gamma with glibc 2.35's powf) in the product's arithmetic, AMBER_MATH_GLIBC.  In an AMBER_MATH_PORTABLE measurement build
+ * powf is the portable form and single bytes may differ by one; MEAN_F32 is the same in both.
+ * AMBER_RESOLVE_MIRROR_X: input column i of a row is written to column width-1-i, the x-mirror ExportPNG and ExportEXR apply (cli/image.cc:45-71);
+ * rows stay where they are.
+ * Memory and order: by default out is a DEVICE pointer on the handle's device and the call is asynchronous and stream-ordered on the handle's
+ * stream, like amber_hip_pt_render_pass: a resolve enqueued after a pass sees that pass, one enqueued before amber_hip_pt_clear the sums before the
+ * clear; read the output after amber_hip_pt_sync or from work enqueued on amber_hip_pt_stream.  (One exception to "asynchronous": after a pass
+ * whose record buffer was sized from an estimate -- see AMBER_HIP_ABI_VERSION, 2 -- the call first waits for that pass, as amber_hip_pt_clear does.)
+ * A 16-byte aligned out (any allocation's start) takes the vector path; MEAN_F32 and RGBA8 need 4-byte alignment at least.  With AMBER_RESOLVE_HOST
+ * out is a HOST pointer of any alignment: the call stages through a buffer the handle owns -- grown on first use, reused, released by destroy -- and
+ * returns after the copy back.  The call never writes the framebuffer, the ray counter or amber_hip_pt_kernel_time, and it does not read the
+ * scene: every engine, both builds.
+ * out_bytes must be exactly rows * width * {12, 3, 4}, so that a wrong buffer cannot be overrun; an empty band: AMBER_OK with out_bytes == 0.
+ * AMBER_EINVAL, with no effect: a NULL handle, n_samples == 0, an unknown format, unknown flag bits, out == NULL with a non-empty band, any other
+ * out_bytes, a misaligned device pointer. */
+enum { AMBER_RESOLVE_MEAN_F32 = 0, AMBER_RESOLVE_RGB8 = 1, AMBER_RESOLVE_RGBA8 = 2 };   /* format */
+enum { AMBER_RESOLVE_HOST = 1u, AMBER_RESOLVE_MIRROR_X = 2u };                          /* flags */
+int  amber_hip_pt_resolve(amber_hip_pt*, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);
