@@ -178,14 +178,15 @@ __device__ __forceinline__ void GenerateLightRay(const DevScene& sc, uint64_t& r
 // The lens record (40 dwords) is needed once per path, not per bounce: it is read from constant memory next to its
 // use.  The empty asm makes the pointer opaque per use, otherwise the compiler hoists the 40 scalar loads out of the
 // persistent loop, keeps them live across the whole bounce loop and spills SGPRs to VGPR lanes in the hot code.
-__device__ __forceinline__ DevLens LoadLens(const DevScene& sc) {
-  ConstWords w = (ConstWords)(sc.lens);
+__device__ __forceinline__ DevLens LoadLens(const DevLens* lens) {
+  ConstWords w = (ConstWords)(lens);
   asm volatile("" : "+s"(w));
   union { DevLens lens; uint32_t words[sizeof(DevLens) / 4]; } u;
 #pragma unroll
   for (unsigned k = 0; k < sizeof(DevLens) / 4; ++k) u.words[k] = w[k];
   return u.lens;
 }
+__device__ __forceinline__ DevLens LoadLens(const DevScene& sc) { return LoadLens(sc.lens); }
 
 // Lens::Response for Ray(position, direction_out) (scene/scene.h:299-307, lens_thin.cc:109-130, lens_pinhole.cc:70-85,
 // Sensor::ResponsePixel sensor.cc:46-59).  Returns false when the ray does not reach the sensor.
@@ -217,11 +218,14 @@ __device__ __forceinline__ bool LensResponse(const DevScene& sc, V3 position, V3
 // eye ray: BasicThin::GenerateRay (lens_thin.cc:70-107) + Sensor::PixelBound::Uniform
 // (sensor.cc:111-120, jitter draw order Y then X -- the g++ order the reference outputs were made with)
 // ---------------------------------------------------------------------------------------------
+// Scene: DevScene, or any record with its members lens, blades and sensor (pt_megakernel hands over cold kernel arguments, EyeRayScene).
 // near_edge (optional): the aperture sample lies within DevLens.edge_tol (barycentric) of its blade's boundary -- only then can the exact
 // test of ANOTHER blade accept the ray's own origin (pt_megakernel's primary rounds: which blades are candidates).
-__device__ __forceinline__ void GenerateEyeRay(const DevScene& sc, uint32_t px, uint32_t py, uint64_t& rng,
+struct EyeRayScene { const DevLens* lens; const DevBlade* blades; DevSensor sensor; };
+template <typename Scene>
+__device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uint32_t py, uint64_t& rng,
                                                V3& origin, V3& dir, float& weight, int& origin_slot, bool* near_edge = nullptr) {
-  const DevLens L = LoadLens(sc);
+  const DevLens L = LoadLens(sc.lens);
   if (L.kind == 1u) {                                      // BasicPinhole::GenerateRay lens_pinhole.cc:48-68
     const float jy = Uniform(rng);
     const float jx = Uniform(rng);

@@ -30,6 +30,30 @@ struct RenderArgs {
   uint32_t shade_batch;      // pt_bvh_megakernel: lanes that must have finished their traversal before the wave shades (the handle's choice, BvhShadeBatch)
 };
 
+// COLD kernel arguments of pt_megakernel.  A field of RenderArgs that the kernel reads as `a.field` is loaded once at the kernel's entry and then
+// lives in SGPRs for the whole persistent loop; the per-bounce code needs every SGPR it can get, so the compiler parks such values in the lanes
+// of a VGPR and fetches them back with v_readlane_b32 wherever they are used -- VALU instructions (plus hazard s_nops) that compute nothing, in
+// a kernel bound by VALU issue.  What the every-bounce path never touches (the claim, the primary round's pixel bookkeeping, the record buffers,
+// the carried measurements) is therefore read from the kernarg segment NEXT TO ITS USE, like the lens record (LoadLens): a scalar load that hits
+// the constant cache once per 64 paths.  The empty asm makes the pointer opaque per use -- otherwise the loads are hoisted back out of the loop.
+// Only valid in a kernel whose FIRST parameter is a by-value RenderArgs (the explicit arguments start at offset 0 of the segment).
+struct ColdArgs {
+  ConstWords w;
+  __device__ __forceinline__ static ColdArgs Open() {
+    ConstWords w = (ConstWords)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(w));
+    return ColdArgs{w};
+  }
+  template <typename T> __device__ __forceinline__ T Get(size_t byte_offset) const {
+    static_assert(sizeof(T) % 4 == 0 && alignof(T) <= 8, "whole dwords");
+    union U { T value; uint32_t words[sizeof(T) / 4]; __device__ U() {} } u;
+#pragma unroll
+    for (unsigned k = 0; k < sizeof(T) / 4; ++k) u.words[k] = w[byte_offset / 4 + k];
+    return u.value;
+  }
+};
+#define AMBER_COLD(cold, field) (cold).Get<decltype(static_cast<const RenderArgs*>(nullptr)->field)>(offsetof(RenderArgs, field))
+
 // FNV-1a-32 step over the four bytes of v (path signatures: amber_hip_kat_signatures, amber_hip_pt_signatures)
 __device__ __forceinline__ uint32_t Fnv32(uint32_t h, uint32_t v) {
 #pragma unroll
@@ -45,9 +69,13 @@ __device__ __forceinline__ uint32_t Fnv32(uint32_t h, uint32_t v) {
 // the launch with a larger buffer (RenderPassPaths).
 #define AMBER_REC_BLOCK 64u
 #define AMBER_REC_UNUSED 0xffffffffu
-__device__ __forceinline__ void EmitRecords(const RenderArgs& a, bool emit, uint32_t q, V3 meas, uint32_t& rec_next, uint32_t& rec_end) {
+// The buffers are handed over by a callable that is asked for them only when the wave has a record to write (pt_megakernel: cold arguments).
+struct RecordSink { uint4* records; uint32_t* flags; uint32_t* touched; unsigned int* rec_count; uint32_t rec_capacity, n_samples; };
+template <typename SinkOf>
+__device__ __forceinline__ void EmitRecords(SinkOf sink_of, bool emit, uint32_t q, V3 meas, uint32_t& rec_next, uint32_t& rec_end) {
   const unsigned long long me = __ballot(emit);
   if (me == 0ull) return;                                     // wave-uniform
+  const RecordSink a = sink_of();
   const uint32_t n = static_cast<uint32_t>(__popcll(me));
   const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(me >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(me), 0u));
   const uint32_t room = rec_end - rec_next;
@@ -65,6 +93,9 @@ __device__ __forceinline__ void EmitRecords(const RenderArgs& a, bool emit, uint
   }
   if (n > room) { rec_next = fresh + (n - room); rec_end = fresh + AMBER_REC_BLOCK; }
   else rec_next += n;
+}
+__device__ __forceinline__ void EmitRecords(const RenderArgs& a, bool emit, uint32_t q, V3 meas, uint32_t& rec_next, uint32_t& rec_end) {
+  EmitRecords([&]() { return RecordSink{a.records, a.flags, a.touched, a.rec_count, a.rec_capacity, a.n_samples}; }, emit, q, meas, rec_next, rec_end);
 }
 // At the end of a wave: the slots of its open block that were never used are marked.
 __device__ __forceinline__ void CloseRecords(const RenderArgs& a, uint32_t rec_next, uint32_t rec_end) {

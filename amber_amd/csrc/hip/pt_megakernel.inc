@@ -55,6 +55,12 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
   const uint32_t lane = threadIdx.x & 63u;
   constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
   constexpr int kChunks = PoolLayout<kLight>::kChunks;
+  constexpr bool kCold = !kLight && kEngine != ENGINE_BVH;    // cold kernel arguments are read next to their use (AMBER_ARG below)
+  // a cold argument, read next to its use (pt_args.h).  Two families keep the plain form: the light tracer (its bounces read n_samples and
+  // first_sample themselves, and with these reads the kernel reserved scratch) and engine BVH's one-shot traversal (measured: Cornell through
+  // ENGINE_BVH 118.6 -> 120.0 ms, the room mesh 52.7 -> 53.6 ms with cold reads, EXPERIMENTS.md).
+#define AMBER_ARG(cold, field) (kCold ? AMBER_COLD(cold, field) : a.field)
+#define AMBER_COLD_OPEN() (kCold ? ColdArgs::Open() : ColdArgs{nullptr})
   __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
   __shared__ uint4 lds_pool[4][64 * kChunks];                 // [wave][slot * kChunks + chunk]
   // engine BVH on a SHALLOW tree (mid-size scenes, RenderPassPaths): the closest hit is one uninterrupted per-lane traversal (ClosestHitBvh),
@@ -79,13 +85,13 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
   //  persistent loop, the pointer is the one value the register cap pushes into scratch)
   auto carried_slot = [&]() -> float* {
     const uint32_t t = wave_in_block * 64u + BvhStackHybrid::LaneId();     // = threadIdx.x, from an SGPR and two v_mbcnt
-    return a.carried + (static_cast<size_t>(blockIdx.x) * 256u + t) * 3u;
+    return AMBER_ARG(AMBER_COLD_OPEN(), carried) + (static_cast<size_t>(blockIdx.x) * 256u + t) * 3u;
   };
 #define AMBER_CARRIED() carried_slot()
   // a carried measurement travels with its ray: parked with it (a second block of slots, one per pool slot of the wave) and handed to
   // the lane that pops the ray -- rays change lanes since the primary rounds
   auto carried_parked = [&](uint32_t pool_slot) -> float* {
-    return a.carried + (static_cast<size_t>(gridDim.x) * 256u + (static_cast<size_t>(blockIdx.x) * 4u + wave_in_block) * 64u + pool_slot) * 3u;
+    return AMBER_ARG(AMBER_COLD_OPEN(), carried) + (static_cast<size_t>(gridDim.x) * 256u + (static_cast<size_t>(blockIdx.x) * 4u + wave_in_block) * 64u + pool_slot) * 3u;
   };
   V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f), w = v3(0.f, 0.f, 0.f);
   uint64_t rng = 1;
@@ -133,12 +139,14 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
         // (first hits, materials) at full width; the parked rays go to whichever lanes lose their path afterwards.
         AMBER_STAMP(0);
         if (claim_next == claim_end) {                        // claim the next block of paths from the global queue
+          const ColdArgs cold = AMBER_COLD_OPEN();   // the queue: cold arguments, read here (pt_args.h)
           const uint32_t size = AMBER_CLAIM_PATHS;                         // (claims sized from what is left of the queue were measured neutral and removed: EXPERIMENTS.md, round 4)
           uint32_t base = 0;
-          if (lane == 0) base = atomicAdd(a.next_item, size);
+          const uint32_t n_items = AMBER_ARG(cold, n_items);
+          if (lane == 0) base = atomicAdd(AMBER_ARG(cold, next_item), size);
           base = __builtin_amdgcn_readfirstlane(base);
-          if (base >= a.n_items) exhausted = true;
-          else { claim_next = base; claim_end = a.n_items - base < size ? a.n_items : base + size; }
+          if (base >= n_items) exhausted = true;
+          else { claim_next = base; claim_end = n_items - base < size ? n_items : base + size; }
 #ifdef AMBER_STAMPS
           if (wave_times && lane == 0) { if (exhausted) wave_times[2] = wall_clock64(); else if (wave_times[1] == 0) wave_times[1] = wall_clock64(); }
 #endif
@@ -159,32 +167,39 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
           pool_count = static_cast<uint32_t>(__popcll(m_alive));
           __builtin_amdgcn_wave_barrier();
           alive = lane < n_new;
+          // what places the 64 new paths in the frame is needed once per round, never by a bounce: cold arguments, read here (pt_args.h)
+          const ColdArgs cold = AMBER_COLD_OPEN();
+          const uint32_t* const pixel_mask = kTwoPhase && !kLight ? AMBER_ARG(cold, pixel_mask) : nullptr;
           if (alive) {
             q = gbase + lane;
-            const uint32_t plocal = q / a.n_samples, k = q - plocal * a.n_samples;
+            const uint32_t n_samples = AMBER_ARG(cold, n_samples), first_sample = AMBER_ARG(cold, first_sample);
+            const uint64_t hashed_seed = AMBER_ARG(cold, hashed_seed);
+            const uint32_t plocal = q / n_samples, k = q - plocal * n_samples;
             if (kLight) {
-              rng = XorShiftSeed(a.hashed_seed, a.path_offset + plocal, a.first_sample + k);
+              rng = XorShiftSeed(hashed_seed, a.path_offset + plocal, first_sample + k);
               GenerateLightRay(sc, rng, o, d, w, origin_slot);
             } else {
-              const uint32_t lrow = plocal / sc.sensor.w;
-              const uint32_t px = plocal - lrow * sc.sensor.w;
-              const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);
-              rng = XorShiftSeed(a.hashed_seed, px + py * sc.sensor.w, a.first_sample + k);   // Image index x + y*W (image.h:116-124)
+              const EyeRayScene eye{AMBER_ARG(cold, scene.lens), AMBER_ARG(cold, scene.blades), AMBER_ARG(cold, scene.sensor)};
+              const uint32_t row_begin = AMBER_ARG(cold, row_begin), stripe_rows = AMBER_ARG(cold, stripe_rows), stripe_period = AMBER_ARG(cold, stripe_period);
+              const uint32_t lrow = plocal / eye.sensor.w;
+              const uint32_t px = plocal - lrow * eye.sensor.w;
+              const uint32_t py = row_begin + (stripe_rows ? (lrow / stripe_rows) * stripe_period + lrow % stripe_rows : lrow);
+              rng = XorShiftSeed(hashed_seed, px + py * eye.sensor.w, first_sample + k);   // Image index x + y*W (image.h:116-124)
               float ew;
               bool near_edge = false;
-              GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot, &near_edge);
+              GenerateEyeRay(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
               w = v3(ew, ew, ew);                             // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
-              if (kTwoPhase && a.pixel_mask) {
+              if (kTwoPhase && pixel_mask) {
                 // the candidates of this pixel's beam, plus the ray's own aperture blade (the self trip decides it exactly), plus
                 // every blade when the aperture sample lies on a blade's boundary (only then can a neighbour's exact test see it)
-                premask = a.pixel_mask[plocal] | (origin_slot >= 0 ? 1u << origin_slot : 0u) | (near_edge ? sc.blade_mask : 0u);
+                premask = pixel_mask[plocal] | (origin_slot >= 0 ? 1u << origin_slot : 0u) | (near_edge ? AMBER_ARG(cold, scene.blade_mask) : 0u);
               }
             }
             carries = false;
             casts = 0;
             if (kSig) { sig_obj = 2166136261u; sig_t = 2166136261u; }
           }
-          primary = !kLight && kTwoPhase && a.pixel_mask != nullptr;
+          primary = pixel_mask != nullptr;
           AMBER_STAMP(1);
         }
       }
@@ -206,7 +221,7 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
         alive = PathStep<true, kEngine>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
         sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
         if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
-        if (!alive) a.sig[q] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
+        if (!alive) AMBER_ARG(AMBER_COLD_OPEN(), sig)[q] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
       } else {
         alive = PathStep<false, kEngine>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
       }
@@ -216,9 +231,17 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
         if (alive && nz) { float* c = AMBER_CARRIED(); c[0] = meas.x; c[1] = meas.y; c[2] = meas.z; carries = true; }
       }
     }
-    if (!kLight) EmitRecords(a, emit, q, meas, rec_next, rec_end);
+    if (!kLight && !kCold) EmitRecords(a, emit, q, meas, rec_next, rec_end);
+    if (kCold) {
+      EmitRecords([]() {                                      // the record buffers: cold arguments, read when a wave has a record to write (2e-5 of the Cornell paths)
+        const ColdArgs cold = ColdArgs::Open();
+        return RecordSink{AMBER_COLD(cold, records), AMBER_COLD(cold, flags), AMBER_COLD(cold, touched), AMBER_COLD(cold, rec_count), AMBER_COLD(cold, rec_capacity), AMBER_COLD(cold, n_samples)};
+      }, emit, q, meas, rec_next, rec_end);
+    }
   }
 
+#undef AMBER_COLD_OPEN
+#undef AMBER_ARG
 #undef AMBER_CARRIED
   if (!kLight) CloseRecords(a, rec_next, rec_end);
 #ifdef AMBER_STAMPS
