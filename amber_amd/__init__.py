@@ -35,6 +35,7 @@ from .api import (  # noqa: F401
     RESOLVE_MIRROR_X,
     Ray,
     RayHit,
+    AovPixel,
     AmberError,
     FlatMaterial,
     FlatObject,

@@ -87,6 +87,11 @@ class RayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("object", C.c_int32), ("pos", C.c_float * 3), ("normal", C.c_float * 3)]
 
 
+class AovPixel(C.Structure):
+    """AmberAovPixel: the sums of albedo, depth, normal and coverage of a pixel's first hits -- 32 bytes (amber_hip_pt_aov_pass)."""
+    _fields_ = [("albedo", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("coverage", C.c_float)]
+
+
 class BvhDumpInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_prims", C.c_uint32), ("root", C.c_int32), ("depth", C.c_uint32),
                 ("gmin", C.c_float * 3), ("step", C.c_float * 3), ("reach", C.c_float * 3)]
@@ -117,6 +122,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
     "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_update_lens",
     "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_resolve", "amber_hip_pt_destroy",
+    "amber_hip_pt_aov_pass", "amber_hip_pt_aov_clear", "amber_hip_pt_aov_download", "amber_hip_pt_device_aov",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -182,6 +188,11 @@ def load_library() -> C.CDLL:
         lib.amber_hip_pt_occluded.argtypes = [vp, u64, vp, vp, u32]
     if hasattr(lib, "amber_hip_pt_resolve"):
         lib.amber_hip_pt_resolve.argtypes = [vp, u32, u32, vp, u64, u32]
+    if hasattr(lib, "amber_hip_pt_aov_pass"):
+        lib.amber_hip_pt_aov_pass.argtypes = [vp, u32, u32]
+        lib.amber_hip_pt_aov_clear.argtypes = [vp]
+        lib.amber_hip_pt_aov_download.argtypes = [vp, vp]
+        lib.amber_hip_pt_device_aov.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -570,6 +581,38 @@ class PathTracer:
         _check(lib.amber_hip_pt_resolve(self._h, n_samples, format, out.data_ptr(), out.numel() * out.element_size(), flags))
         self._torch_leave(same)
         return out
+
+    # ---- first-hit AOVs -----------------------------------------------------------------------
+    def aov_pass(self, first_sample: int, n_samples: int) -> None:
+        """amber_hip_pt_aov_pass: for every pixel of the band and the samples [first_sample, first_sample + n_samples) in this order, the first hit of
+        the eye ray the render kernels generate for that pixel and sample adds the hit material's rho, the distance t, the reference's Intersect()
+        normal and 1 to the pixel's eight sums (one binary32 addition each; a miss adds nothing).  Asynchronous and stream-ordered on the handle's
+        stream like render_pass: a pass enqueued before update_objects / update_lens sees the old scene and lens, one enqueued after it the new
+        ones.  Never touches the framebuffer, the ray counter or kernel_time().  The buffer is allocated and zeroed by the first aov_* call."""
+        _check(load_library().amber_hip_pt_aov_pass(self._h, first_sample, n_samples))
+
+    def aov_clear(self) -> None:
+        """amber_hip_pt_aov_clear: zeroes the AOV buffer (asynchronous, on the handle's stream).  The framebuffer is not cleared; clear() in turn
+        leaves the AOV buffer alone."""
+        _check(load_library().amber_hip_pt_aov_clear(self._h))
+
+    def aov_download(self) -> np.ndarray:
+        """amber_hip_pt_aov_download: a float32 array of shape band_shape[:2] + (8,) in AmberAovPixel's order -- albedo r g b, depth, normal x y z,
+        coverage -- rows as download() lays them out.  Raw SUMS: divide by the sample count, or by coverage for a mean over the samples that hit.
+        Synchronises."""
+        rows, width, _ = self.band_shape
+        out = np.zeros((rows, width, 8), np.float32)
+        _check(load_library().amber_hip_pt_aov_download(self._h, out.ctypes.data))
+        return out
+
+    def device_aov(self):
+        """amber_hip_pt_device_aov: (device pointer, number of band pixels) of the AOV buffer, 8 float32 per pixel, for zero-copy consumers
+        (torch.from_dlpack / a __cuda_array_interface__ wrapper, a denoiser).  ORDERING: the engine works on the handle's stream, not on torch's
+        current stream.  Wrap the handle's stream -- torch.cuda.ExternalStream(pt.stream()) -- and read the buffer under `with torch.cuda.stream(...)`
+        of it, so that aov_pass and the reader are ordered on one stream; otherwise call sync() first."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(load_library().amber_hip_pt_device_aov(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

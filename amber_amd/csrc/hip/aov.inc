@@ -1,0 +1,163 @@
+// aov.inc -- amber_hip_pt_aov_pass / _aov_clear / _aov_download / amber_hip_pt_device_aov: the first-hit guide images of the band (albedo, depth,
+// shading normal, coverage), summed over samples on the device.  Part of the one translation unit pt_host.hip; the device functions are the render
+// kernels': GenerateEyeRay with the render kernels' seed, draw order and origin_slot, ClosestHit<kEngine>, ResolveHit.
+//
+//   aov_kernel<kEngine>   ONE THREAD PER BAND PIXEL, looping over the samples first_sample .. first_sample + n_samples - 1 in this order.  The eight
+//                         sums (AmberAovPixel: two float4) live in registers: read once, one binary32 addition per component and hit, written once.
+//                         No sort, no atomics: the sums are the sequential definition of include/amber_hip.h by construction, and a pass over
+//                         [a, a + m + n) leaves the bits of the two passes [a, a + m), [a + m, a + m + n).
+//                         LIST, TWO_PHASE, TWO_PHASE_N, REFERENCE_BVH as ray_query_kernel runs them: the two-phase image staged once per workgroup,
+//                         object loops wave-uniform (a lane beyond the band repeats the last pixel and stores nothing), a grid no larger than the render
+//                         kernels' (REFERENCE_BVH's traversal stack has one column per thread of THAT grid), each thread taking every
+//                         gridDim.x * 256-th pixel.  Engine BVH: the one-shot per-lane traversal of pt_megakernel<ENGINE_BVH> (BvhRoundOn on
+//                         BvhStackLds) with the whole AMBER_BVH_STACK levels in LDS, so a tree of any depth the builders emit is walked; a stack
+//                         overflow, and an origin outside the scene's bounding sphere (BvhOriginInRange, as bvh_query_kernel), take the leaf-list scan.
+// Parallelism is the band's pixel count: a band of few pixels with many samples keeps few lanes busy however long the pass is.  That is accepted --
+// guide images are taken at a handful of samples over a whole frame, where every CU has work.
+// Waves per SIMD: engine BVH takes the point of the ray queries (AMBER_QUERY_WAVES = 5: five workgroups of 32 KiB of LDS stack fill a CU's 160 KiB);
+// the other engines leave the registers to the compiler, as ray_query_kernel does.  No tuning surface.
+namespace {
+
+struct AovArgs {
+  DevScene scene;
+  float4* aov;                                    // AmberAovPixel per band pixel: {albedo.rgb, depth} {normal.xyz, coverage}
+  uint64_t hashed_seed;
+  uint32_t n_pixels, first_sample, n_samples;
+  uint32_t row_begin, stripe_rows, stripe_period;
+};
+
+template <int kEngine>
+__global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? AMBER_QUERY_WAVES : 1) aov_kernel(const AovArgs a) {
+  const DevScene& sc = a.scene;
+  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
+  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
+  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? AMBER_BVH_STACK * 256 : 1];
+  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * 256u; base < a.n_pixels; base += static_cast<uint64_t>(gridDim.x) * 256u) {   // uniform over the workgroup
+    const uint64_t i = base + threadIdx.x;
+    const bool mine = i < a.n_pixels;
+    const uint32_t plocal = mine ? static_cast<uint32_t>(i) : a.n_pixels - 1u;      // keep the object loops wave-uniform for every lane
+    const uint32_t lrow = plocal / sc.sensor.w, px = plocal - lrow * sc.sensor.w;
+    const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);
+    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+    if (mine) { s0 = a.aov[2u * i]; s1 = a.aov[2u * i + 1u]; }
+    for (uint32_t k = 0; k < a.n_samples; ++k) {
+      uint64_t rng = XorShiftSeed(a.hashed_seed, px + py * sc.sensor.w, a.first_sample + k);   // Image index x + y*W, as the render kernels seed it
+      V3 o, d; float ew; int origin_slot;
+      GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot);
+      HitRec h;
+      if constexpr (kEngine == ENGINE_BVH) {
+        BvhTrav tr;
+        BvhBegin(sc, o, d, tr, h);
+        if (tr.cur != AMBER_BVH_DONE && !BvhOriginInRange(sc, o)) { tr.cur = AMBER_BVH_DONE; tr.overflow = true; }   // the tree does not cover this origin: the scan below
+        const BvhStackLds stack{lds_stack + threadIdx.x, AMBER_BVH_STACK};
+        while (BvhRoundOn<BvhStackLds, AMBER_ONE_SHOT_BVH_BUDGET>(sc, stack, o, d, tr, h)) {}
+        if (tr.overflow) ClosestHitLeafList(sc, o, d, h);
+        BvhResolveIndex(sc, h);
+      } else {
+#ifdef AMBER_STAMPS
+        StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
+#endif
+        ClosestHit<kEngine>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG);
+      }
+      // every exact test forms dot products over all components of o and d: a NaN component makes every distance NaN, which no hit accepts
+      const bool nan_ray = !(o.x == o.x && o.y == o.y && o.z == o.z && d.x == d.x && d.y == d.y && d.z == d.z);
+      if (h.idx >= 0 && !nan_ray) {
+        V3 pos, nrm; uint32_t mat;
+        ResolveHit<kEngine == ENGINE_TWO_PHASE_N ? 0x7fu : 0xffu>(kTwoPhase ? lds_objects : (kEngine == ENGINE_BVH || kEngine == ENGINE_REF_BVH ? sc.bvh_objects : sc.objects), h, o, d, pos, nrm, mat);
+        const float* rho = sc.materials[mat].rho;
+        s0.x = s0.x + rho[0]; s0.y = s0.y + rho[1]; s0.z = s0.z + rho[2]; s0.w = s0.w + h.t;
+        s1.x = s1.x + nrm.x; s1.y = s1.y + nrm.y; s1.z = s1.z + nrm.z; s1.w = s1.w + 1.0f;
+      }
+    }
+    if (mine) { a.aov[2u * i] = s0; a.aov[2u * i + 1u] = s1; }
+  }
+}
+
+static_assert(sizeof(AmberAovPixel) == 32, "an AOV pixel is two float4");
+
+// The AOV buffer of the band: allocated and zeroed (on the handle's stream) by the first of the four entry points; nothing for an empty band.
+int EnsureAov(amber_hip_pt* h, const char* name) {
+  const uint64_t n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
+  if (n_pixels == 0 || h->d_aov) return AMBER_OK;
+  const hipError_t e = h->d_aov.alloc(static_cast<size_t>(n_pixels) * 2u);
+  if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string(name) + ": hipMalloc(AOV buffer): " + hipGetErrorString(e));
+  HIP_TRY(hipMemsetAsync(h->d_aov, 0, static_cast<size_t>(n_pixels) * sizeof(AmberAovPixel), h->stream));
+  return AMBER_OK;
+}
+
+int AovPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
+  const char* name = "amber_hip_pt_aov_pass";
+  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
+  if (n_samples == 0) return AMBER_OK;
+  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, std::string(name) + ": sample index overflow");
+#if AMBER_BVH_WIDE
+  return Fail(AMBER_EINVAL, std::string(name) + ": not part of an AMBER_BVH_WIDE measurement build");
+#endif
+  HIP_TRY(hipSetDevice(h->device));
+  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  if (n_pixels == 0) return AMBER_OK;                                         // empty band
+  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
+  AovArgs a{};
+  a.scene = h->scene; a.aov = h->d_aov; a.hashed_seed = h->hashed_seed;
+  a.n_pixels = n_pixels; a.first_sample = first_sample; a.n_samples = n_samples;
+  a.row_begin = h->row_begin; a.stripe_rows = h->stripe_rows; a.stripe_period = h->stripe_period;
+  const uint32_t by_work = (n_pixels + 255u) / 256u;                          // n_pixels < 2^32
+  const uint32_t max_blocks = h->hit_engine == AMBER_ENGINE_BVH ? static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_QUERY_WAVES) : PersistentBlocks(h);
+  const uint32_t n_blocks = by_work < max_blocks ? by_work : max_blocks;
+  { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
+  WithHitEngine(h->hit_engine, [&](auto engine) -> int {
+    constexpr int kEngine = decltype(engine)::value;
+    hipLaunchKernelGGL((aov_kernel<kEngine>), dim3(n_blocks), dim3(256), 0, h->stream, a);
+    return AMBER_OK;
+  });
+  HIP_TRY(hipGetLastError());
+  return AMBER_OK;
+}
+
+int AovClear(amber_hip_pt* h) {
+  const char* name = "amber_hip_pt_aov_clear";
+  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const bool fresh = !h->d_aov;
+  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
+  if (!fresh) HIP_TRY(hipMemsetAsync(h->d_aov, 0, static_cast<size_t>(h->local_rows) * h->scene.sensor.w * sizeof(AmberAovPixel), h->stream));
+  return AMBER_OK;
+}
+
+int AovDownload(amber_hip_pt* h, AmberAovPixel* out) {
+  const char* name = "amber_hip_pt_aov_download";
+  if (!h || !out) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or output pointer");
+  HIP_TRY(hipSetDevice(h->device));
+  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
+  const size_t n_pixels = static_cast<size_t>(h->local_rows) * h->scene.sensor.w;
+  if (n_pixels) HIP_TRY(hipMemcpyAsync(out, h->d_aov, n_pixels * sizeof(AmberAovPixel), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return AMBER_OK;
+}
+
+int DeviceAov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
+  const char* name = "amber_hip_pt_device_aov";
+  if (!h || !dptr) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or pointer");
+  HIP_TRY(hipSetDevice(h->device));
+  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
+  *dptr = h->d_aov;                                                           // (null for an empty band)
+  if (n_pixels) *n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
+  return AMBER_OK;
+}
+
+// No exception crosses the C boundary (the messages are std::strings: forming one may throw, so the handlers form none).
+template <typename F>
+int AovGuarded(F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    g_last_error.clear();
+    return AMBER_ENOMEM;
+  } catch (...) {
+    g_last_error.clear();
+    return AMBER_EHIP;
+  }
+}
+
+}  // namespace

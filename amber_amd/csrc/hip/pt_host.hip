@@ -16,6 +16,8 @@
 //                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>.
 //   resolve.inc            amber_hip_pt_resolve: the framebuffer's sums as the mean or, through Filmic + Gamma, as 8-bit RGB / RGBA, in device memory --
 //                          a streaming kernel, four output pixels per thread, bytes equal to the host's output stage.
+//   aov.inc                amber_hip_pt_aov_pass and its three companions: the first-hit guide images (albedo, depth, normal, coverage) of the band --
+//                          one thread per band pixel looping over the samples, the eight sums in registers, every engine's own closest hit.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -181,6 +183,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<float4> d_query_rays;              // AMBER_RAYS_HOST: staging of the rays and of the results, at most kQueryStageRays rays
   DevBuf<uint8_t> d_query_out;
   DevBuf<uint8_t> d_resolve_out;            // amber_hip_pt_resolve with AMBER_RESOLVE_HOST (resolve.inc): staging of the output, grown on first use and reused
+  DevBuf<float4> d_aov;                     // amber_hip_pt_aov_* (aov.inc): two float4 per band pixel, allocated and zeroed by the first of those calls
   DevBuf<float> d_fb;
   DevBuf<unsigned long long> d_rays;
   DevBuf<unsigned int> d_next;
@@ -762,6 +765,7 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 
 #include "ray_query.inc"
 #include "resolve.inc"
+#include "aov.inc"
 
 extern "C" {
 
@@ -997,6 +1001,22 @@ int amber_hip_pt_occluded(amber_hip_pt* h, uint64_t n, const AmberRay* rays, uin
 
 int amber_hip_pt_resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
   return Resolve(h, n_samples, format, out, out_bytes, flags);
+}
+
+int amber_hip_pt_aov_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
+  return AovGuarded([&] { return AovPass(h, first_sample, n_samples); });
+}
+
+int amber_hip_pt_aov_clear(amber_hip_pt* h) {
+  return AovGuarded([&] { return AovClear(h); });
+}
+
+int amber_hip_pt_aov_download(amber_hip_pt* h, AmberAovPixel* out) {
+  return AovGuarded([&] { return AovDownload(h, out); });
+}
+
+int amber_hip_pt_device_aov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
+  return AovGuarded([&] { return DeviceAov(h, dptr, n_pixels); });
 }
 
 int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) {

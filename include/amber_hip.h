@@ -33,7 +33,8 @@ extern "C" {
                                     Still 3 with AMBER_PT_FLAG_DEVICE_BUILD and amber_hip_pt_build_info(): a flag bit that older libraries ignore and
                                     a new function; nothing that existed changed its layout or meaning.  Still 3 with amber_hip_pt_update_objects(): a new function.
                                     Still 3 with amber_hip_pt_cast_rays() / amber_hip_pt_occluded(): two new functions and their two structs.
-                                    Still 3 with amber_hip_pt_update_lens(): a new function.  Still 3 with amber_hip_pt_resolve(): a new function */
+                                    Still 3 with amber_hip_pt_update_lens(): a new function.  Still 3 with amber_hip_pt_resolve(): a new function.
+                                    Still 3 with amber_hip_pt_aov_pass() / _aov_clear() / _aov_download() / amber_hip_pt_device_aov(): four new functions and their struct */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -334,6 +335,39 @@ int  amber_hip_pt_occluded(amber_hip_pt*, uint64_t n, const AmberRay* rays, uint
 enum { AMBER_RESOLVE_MEAN_F32 = 0, AMBER_RESOLVE_RGB8 = 1, AMBER_RESOLVE_RGBA8 = 2 };   /* format */
 enum { AMBER_RESOLVE_HOST = 1u, AMBER_RESOLVE_MIRROR_X = 2u };                          /* flags */
 int  amber_hip_pt_resolve(amber_hip_pt*, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags);
+/* First-hit AOVs: the guide images a denoiser, an edge-aware filter or a compositor takes with a low-sample image -- albedo, depth, shading normal
+ * and coverage of the first surface each pixel's eye rays see -- summed over samples on the device.  Still ABI version 3: four new functions and one struct.
+ * Definition.  For a band pixel p = (px, py) and a sample index s, ray(p, s) is the eye ray the render kernels generate for that pixel and sample
+ * (the sampler seeded by (seed, px + py * width, s), the same draw order, the same aperture blade), and hit(p, s) is what the handle's closest-hit
+ * engine returns for the first Scene::Cast of that path: the answer amber_hip_pt_cast_rays gives for that ray with t_max = INFINITY.
+ * amber_hip_pt_aov_pass(h, first_sample, n_samples) visits s = first_sample ... first_sample + n_samples - 1 in this order, for every pixel of the
+ * band; where hit(p, s) is a hit every component of the pixel's AmberAovPixel gets ONE binary32 addition, v = v + term:
+ *   albedo    rho[3] of the hit object's material exactly as AmberFlatMaterial stores it, whatever the material kind: a DiffuseLight's radiance,
+ *             an Eye blade's whatever the table holds
+ *   depth     the hit's t (in units of |dir|; eye-ray directions are normalised)
+ *   normal    the reference's Intersect() normal, AmberRayHit.normal: not flipped towards the ray, not renormalised
+ *   coverage  1.0f
+ * A miss adds nothing.  The buffer starts at +0 and there is no chunking: one call over [a, a + m + n) and the two calls [a, a + m), [a + m, a + m + n)
+ * leave the same bits.  The values are raw SUMS: divide by the sample count (a mean over all samples, misses counting as 0) or by coverage (a mean
+ * over the samples that hit).
+ * Buffer and order.  The first of these four calls on a handle allocates the buffer (rows * width * 32 bytes) and zeroes it; amber_hip_pt_destroy
+ * releases it; a handle that never calls them pays nothing.  aov_pass and aov_clear are asynchronous and stream-ordered on the handle's stream like
+ * amber_hip_pt_render_pass: a pass enqueued before amber_hip_pt_update_objects / amber_hip_pt_update_lens sees the old scene and lens, one enqueued
+ * after it the new ones.  None of the four touches the framebuffer, the ray counter or amber_hip_pt_kernel_time; amber_hip_pt_clear does not clear the
+ * AOV buffer and aov_clear does not clear the framebuffer.
+ *   aov_download  copies the band's pixels to the host in amber_hip_pt_download's layout (local rows in increasing y, width pixels each); synchronises.
+ *   device_aov    the device pointer of the buffer and the band's pixel count, for zero-copy consumers: read it after amber_hip_pt_sync or from work
+ *                 enqueued on amber_hip_pt_stream.  n_pixels may be NULL.
+ * Engines: every product engine in both builds; AMBER_PT_FLAG_DEVICE_BUILD and AMBER_PT_FLAG_BVH_ITEMS change nothing in the answer; a handle of the
+ * lab engine WAVEFRONT answers as engine AUTO does.  The work is one thread per band pixel looping over the samples, so a band of few pixels is slow
+ * however many samples it takes.
+ * n_samples == 0: AMBER_OK.  An empty band: AMBER_OK, nothing written, n_pixels == 0 (and a NULL device pointer).  AMBER_EINVAL: a NULL handle, a NULL
+ * out or dptr, first_sample + n_samples > 2^32 - 1, aov_pass in an AMBER_BVH_WIDE measurement build.  AMBER_ENOMEM: the buffer could not be allocated. */
+typedef struct { float albedo[3]; float depth; float normal[3]; float coverage; } AmberAovPixel;   /* 32 bytes: two float4 */
+int  amber_hip_pt_aov_pass(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples);
+int  amber_hip_pt_aov_clear(amber_hip_pt*);
+int  amber_hip_pt_aov_download(amber_hip_pt*, AmberAovPixel* out);      /* band layout of amber_hip_pt_download: local rows in increasing y, width pixels each; synchronises */
+int  amber_hip_pt_device_aov(amber_hip_pt*, void** dptr, uint64_t* n_pixels);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);
