@@ -24,6 +24,11 @@ struct AovArgs {
   uint64_t hashed_seed;
   uint32_t n_pixels, first_sample, n_samples;
   uint32_t row_begin, stripe_rows, stripe_period;
+  ExactDiv div_stripe_rows, div_width;            // lrow / stripe_rows (unused when 0), plocal / scene.sensor.w: exact dividers (exact_div.h)
+  void SetBand(uint32_t row_begin_, uint32_t stripe_rows_, uint32_t stripe_period_) {    // the fields and their dividers together (as RenderArgs::SetBand; call once `scene` is set)
+    row_begin = row_begin_; stripe_rows = stripe_rows_; stripe_period = stripe_period_;
+    div_stripe_rows = MakeExactDiv(stripe_rows_); div_width = MakeExactDiv(scene.sensor.w);
+  }
 };
 
 template <int kEngine>
@@ -37,8 +42,8 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? AMBER_QUERY_WAVES
     const uint64_t i = base + threadIdx.x;
     const bool mine = i < a.n_pixels;
     const uint32_t plocal = mine ? static_cast<uint32_t>(i) : a.n_pixels - 1u;      // keep the object loops wave-uniform for every lane
-    const uint32_t lrow = plocal / sc.sensor.w, px = plocal - lrow * sc.sensor.w;
-    const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);
+    const uint32_t lrow = Quotient(a.div_width, plocal), px = plocal - lrow * sc.sensor.w;
+    const uint32_t py = FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow);
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
     if (mine) { s0 = a.aov[2u * i]; s1 = a.aov[2u * i + 1u]; }
     for (uint32_t k = 0; k < a.n_samples; ++k) {
@@ -101,7 +106,7 @@ int AovPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
   AovArgs a{};
   a.scene = h->scene; a.aov = h->d_aov; a.hashed_seed = h->hashed_seed;
   a.n_pixels = n_pixels; a.first_sample = first_sample; a.n_samples = n_samples;
-  a.row_begin = h->row_begin; a.stripe_rows = h->stripe_rows; a.stripe_period = h->stripe_period;
+  a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period);
   const uint32_t by_work = (n_pixels + 255u) / 256u;                          // n_pixels < 2^32
   const uint32_t max_blocks = h->hit_engine == AMBER_ENGINE_BVH ? static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_QUERY_WAVES) : PersistentBlocks(h);
   const uint32_t n_blocks = by_work < max_blocks ? by_work : max_blocks;

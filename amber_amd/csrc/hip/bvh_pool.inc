@@ -231,10 +231,10 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
         mw = __ballot(want_path);
       }
       if (got_path) {                                                 // algorithm_pt.cc:125-136: the path's sampler and eye ray
-        const uint32_t plocal = sq / a.n_samples, k = sq - plocal * a.n_samples;
-        const uint32_t lrow = plocal / sc.sensor.w;
+        const uint32_t plocal = Quotient(a.div_samples, sq), k = sq - plocal * a.n_samples;   // exact dividers formed by the host (exact_div.h)
+        const uint32_t lrow = Quotient(a.div_width, plocal);
         const uint32_t px = plocal - lrow * sc.sensor.w;
-        const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);
+        const uint32_t py = FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow);
         srng = XorShiftSeed(a.hashed_seed, px + py * sc.sensor.w, a.first_sample + k);     // Image index x + y*W (image.h:116-124)
         float ew; int os;
         GenerateEyeRay(sc, px, py, srng, so, sd, ew, os);

@@ -40,7 +40,7 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
     HIP_TRY(hipMemsetAsync(counts, 0, n_counts * sizeof(unsigned int), h->stream));
     WfArgs a;
     a.scene = h->scene; a.meas = meas; a.counts = counts; a.ray_count = h->d_rays; a.hashed_seed = h->hashed_seed;
-    a.row_begin = h->row_begin; a.stripe_rows = h->stripe_rows; a.stripe_period = h->stripe_period; a.n_pixels = n_pixels;
+    a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels;
     a.first_sample = first_sample + done; a.n_samples = n; a.n_paths = static_cast<uint32_t>(n_paths); a.bounce = 0; a.shard_capacity = static_cast<uint32_t>(shard_capacity);
     const uint32_t n_blocks = 2048u;                          // 8192 waves = 32 per shard
     std::pair<Event, Event>* evp = nullptr;

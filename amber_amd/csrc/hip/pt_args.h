@@ -23,12 +23,32 @@ struct RenderArgs {
   uint64_t hashed_seed;      // SplitMix64(global_seed)
   uint32_t row_begin;
   uint32_t stripe_rows, stripe_period;   // 0,0 = contiguous rows
+  ExactDiv div_stripe_rows;  // lrow / stripe_rows without a divide (exact_div.h); unused when stripe_rows == 0
+  ExactDiv div_width;        // plocal / scene.sensor.w
   uint32_t n_pixels;         // pixels of the band
   uint32_t first_sample, n_samples;
   uint32_t n_chunks, n_items;   // pt_bvh_megakernel: items = (pixel, chunk); path-granular kernels: n_items = paths of the launch
+  ExactDiv div_samples;      // q / n_samples
   uint32_t path_offset;      // light tracing: index of the first light path of this launch's range (amber_hip_lt_trace_range)
   uint32_t shade_batch;      // pt_bvh_megakernel: lanes that must have finished their traversal before the wave shades (the handle's choice, BvhShadeBatch)
+
+  // The divisors of the pixel bookkeeping are the same for every path of a launch: their dividers are formed here, together with the fields
+  // they belong to, for every launch anew (nothing is cached: a handle's next launch may have another sample count).  SetBand reads the
+  // sensor width: call it once `scene` is set.
+  void SetBand(uint32_t row_begin_, uint32_t stripe_rows_, uint32_t stripe_period_) {
+    row_begin = row_begin_; stripe_rows = stripe_rows_; stripe_period = stripe_period_;
+    div_stripe_rows = MakeExactDiv(stripe_rows_); div_width = MakeExactDiv(scene.sensor.w);
+  }
+  void SetSamples(uint32_t first_sample_, uint32_t n_samples_) { first_sample = first_sample_; n_samples = n_samples_; div_samples = MakeExactDiv(n_samples_); }
 };
+
+// Local row of a band -> row of the frame: contiguous rows from row_begin (stripe_rows == 0: the divider is not used), or stripes of stripe_rows rows
+// every stripe_period rows.  The kernels that read these fields as plain arguments share it; pt_megakernel reads them cold, one by one (pt_megakernel.inc).
+__device__ __forceinline__ uint32_t FrameRow(uint32_t row_begin, uint32_t stripe_rows, uint32_t stripe_period, ExactDiv div_stripe_rows, uint32_t lrow) {
+  if (stripe_rows == 0u) return row_begin + lrow;
+  const uint32_t band = Quotient(div_stripe_rows, lrow);
+  return row_begin + band * stripe_period + (lrow - band * stripe_rows);
+}
 
 // COLD kernel arguments of pt_megakernel.  A field of RenderArgs that the kernel reads as `a.field` is loaded once at the kernel's entry and then
 // lives in SGPRs for the whole persistent loop; the per-bounce code needs every SGPR it can get, so the compiler parks such values in the lanes
@@ -70,7 +90,7 @@ __device__ __forceinline__ uint32_t Fnv32(uint32_t h, uint32_t v) {
 #define AMBER_REC_BLOCK 64u
 #define AMBER_REC_UNUSED 0xffffffffu
 // The buffers are handed over by a callable that is asked for them only when the wave has a record to write (pt_megakernel: cold arguments).
-struct RecordSink { uint4* records; uint32_t* flags; uint32_t* touched; unsigned int* rec_count; uint32_t rec_capacity, n_samples; };
+struct RecordSink { uint4* records; uint32_t* flags; uint32_t* touched; unsigned int* rec_count; uint32_t rec_capacity; ExactDiv div_samples; };
 template <typename SinkOf>
 __device__ __forceinline__ void EmitRecords(SinkOf sink_of, bool emit, uint32_t q, V3 meas, uint32_t& rec_next, uint32_t& rec_end) {
   const unsigned long long me = __ballot(emit);
@@ -88,14 +108,14 @@ __device__ __forceinline__ void EmitRecords(SinkOf sink_of, bool emit, uint32_t 
     const uint32_t slot = rank < room ? rec_next + rank : fresh + (rank - room);
     if (slot < a.rec_capacity) a.records[slot] = make_uint4(q, __float_as_uint(meas.x), __float_as_uint(meas.y), __float_as_uint(meas.z));
     atomicOr(a.flags + (q >> 5), 1u << (q & 31u));
-    const uint32_t p = q / a.n_samples;
+    const uint32_t p = Quotient(a.div_samples, q);
     atomicOr(a.touched + (p >> 5), 1u << (p & 31u));
   }
   if (n > room) { rec_next = fresh + (n - room); rec_end = fresh + AMBER_REC_BLOCK; }
   else rec_next += n;
 }
 __device__ __forceinline__ void EmitRecords(const RenderArgs& a, bool emit, uint32_t q, V3 meas, uint32_t& rec_next, uint32_t& rec_end) {
-  EmitRecords([&]() { return RecordSink{a.records, a.flags, a.touched, a.rec_count, a.rec_capacity, a.n_samples}; }, emit, q, meas, rec_next, rec_end);
+  EmitRecords([&]() { return RecordSink{a.records, a.flags, a.touched, a.rec_count, a.rec_capacity, a.div_samples}; }, emit, q, meas, rec_next, rec_end);
 }
 // At the end of a wave: the slots of its open block that were never used are marked.
 __device__ __forceinline__ void CloseRecords(const RenderArgs& a, uint32_t rec_next, uint32_t rec_end) {

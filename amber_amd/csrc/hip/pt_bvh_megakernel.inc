@@ -78,6 +78,7 @@ __global__ void __launch_bounds__(256, kStack <= 24 && !kSig ? AMBER_BVH_WGS : 4
       if (need && rank < avail) {
         const uint32_t item = pool_next + rank;
         const uint32_t plocal = item / a.n_chunks, chunk = item - plocal * a.n_chunks;
+        // (plain divisions, once per item: the exact dividers of exact_div.h were measured here and the kernel was no faster, EXPERIMENTS.md)
         const uint32_t lrow = plocal / sc.sensor.w;
         const uint32_t px = plocal - lrow * sc.sensor.w;
         const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);

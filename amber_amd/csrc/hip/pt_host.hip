@@ -1,6 +1,7 @@
 // pt_host.hip -- the ONE translation unit of the gfx950 path-tracing engine: the handle, the host side of every launch and the C ABI
 // (include/amber_hip.h).  The kernels live in files of their own and are included here, where they are launched:
 //   pt_args.h              RenderArgs; record emission (accumulation without owners)
+//   exact_div.h            exact division by a launch constant without a divide (the pixel bookkeeping of the render kernels)
 //   pt_megakernel.inc      pt_megakernel: persistent waves, work unit = ONE PATH (q = band pixel * n_samples + sample), a wave claims 1024 paths with
 //                          one atomicAdd; lanes are decoupled from pixels through the wave's LDS pool; 64 fresh paths of one pixel start together
 //                          (primary round, candidates from the per-pixel masks).  Engines LIST / TWO_PHASE (<= 32 objects; groups of 32 up to 128), engine BVH on trees of depth <= 12
@@ -49,6 +50,7 @@
 #include "../../../include/amber_hip_lab.h"
 #endif
 #include "pt_device.h"
+#include "exact_div.h"
 #include "bvh_build.h"
 #include "filter_build.h"
 #include "ref_bvh_build.h"
@@ -663,7 +665,7 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
   a.scene = h->scene; a.flags = h->d_flags; a.touched = h->d_touched; a.records = h->d_records; a.rec_count = h->d_rec_count; a.rec_capacity = h->rec_capacity;
   a.ray_count = h->d_rays_launch; a.next_item = h->d_launch_ctl; a.stamps = h->d_stamps; a.hashed_seed = h->hashed_seed;
   a.bvh_stack = h->d_bvh_stack; a.carried = h->d_carried; a.sig = sig;
-  a.row_begin = h->row_begin; a.stripe_rows = h->stripe_rows; a.stripe_period = h->stripe_period; a.n_pixels = n_pixels; a.first_sample = first; a.n_samples = n;
+  a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels; a.SetSamples(first, n);
   a.n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK; a.n_items = static_cast<uint32_t>(n_paths);
   HIP_TRY(hipMemsetAsync(h->d_launch_ctl, 0, 4 * sizeof(unsigned int), h->stream));
   // The bitmap is cleared by the reduction itself where it can be (whole words per pixel); the host clears all of it only when a
@@ -687,7 +689,7 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
   hipLaunchKernelGGL(rec_rank_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, h->d_flags, h->d_touched, n_pixels, n, h->d_excl, h->d_block_sum);
   hipLaunchKernelGGL(rec_scan_blocks_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_block_sum, n_rank_blocks, h->d_rec_count, h->rec_capacity, h->d_rays, h->d_rays_launch);
   hipLaunchKernelGGL(rec_place_kernel, dim3(static_cast<uint32_t>(h->n_cus) * 8u), dim3(256), 0, h->stream, h->d_records, h->d_rec_count, h->rec_capacity, h->d_flags,
-                     h->d_excl, h->d_block_sum, n, h->d_sorted);
+                     h->d_excl, h->d_block_sum, n, MakeExactDiv(n), h->d_sorted);
   hipLaunchKernelGGL(reduce_flagged_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, h->d_fb, h->d_flags, h->d_touched, h->d_sorted, h->d_excl, h->d_block_sum,
                      h->d_rec_count, h->rec_capacity, n_pixels, n);
   HIP_TRY(hipGetLastError());
@@ -812,7 +814,7 @@ static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n
     if (sig) { const int rc = EnsureLaunchCtl(h); if (rc != AMBER_OK) return rc; }
     RenderArgs a{};
     a.scene = h->scene; a.partial = h->d_partial; a.ray_count = sig ? h->d_rays_launch : h->d_rays; a.next_item = h->d_next; a.stamps = h->d_stamps; a.hashed_seed = h->hashed_seed;
-    a.row_begin = h->row_begin; a.stripe_rows = h->stripe_rows; a.stripe_period = h->stripe_period; a.n_pixels = n_pixels; a.first_sample = first_sample + done; a.n_samples = n;
+    a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels; a.SetSamples(first_sample + done, n);
     a.n_chunks = n_chunks; a.n_items = n_pixels * n_chunks; a.sig = sig; a.shade_batch = h->bvh_shade_batch;
     // persistent workers: one workgroup of 4 waves per CU and resident wave slot, fewer if the queue is short
     const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
@@ -876,7 +878,8 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
     RenderArgs a{};
     a.scene = h->scene; a.ray_count = h->d_rays; a.next_item = h->d_next;
     a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = dev_capacity; a.hashed_seed = h->hashed_seed_lt;
-    a.n_pixels = n_paths; a.first_sample = first_sample + done; a.n_samples = n; a.path_offset = path_begin;
+    a.SetBand(0u, 0u, 0u);                                    // light paths have no band; every divider of the launch is a valid record all the same
+    a.n_pixels = n_paths; a.SetSamples(first_sample + done, n); a.path_offset = path_begin;
     a.n_chunks = n_chunks; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
     const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
     { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }

@@ -169,26 +169,32 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
           alive = lane < n_new;
           // what places the 64 new paths in the frame is needed once per round, never by a bounce: cold arguments, read here (pt_args.h)
           const ColdArgs cold = AMBER_COLD_OPEN();
-          const uint32_t* const pixel_mask = kTwoPhase && !kLight ? AMBER_ARG(cold, pixel_mask) : nullptr;
           if (alive) {
             q = gbase + lane;
+            // the divisors are launch constants: exact multiply-and-shift dividers formed by the host (exact_div.h), no divide sequences here
             const uint32_t n_samples = AMBER_ARG(cold, n_samples), first_sample = AMBER_ARG(cold, first_sample);
-            const uint64_t hashed_seed = AMBER_ARG(cold, hashed_seed);
-            const uint32_t plocal = q / n_samples, k = q - plocal * n_samples;
+            const uint32_t plocal = Quotient(AMBER_ARG(cold, div_samples), q), sample = first_sample + (q - plocal * n_samples);
             if (kLight) {
-              rng = XorShiftSeed(hashed_seed, a.path_offset + plocal, first_sample + k);
+              rng = XorShiftSeed(a.hashed_seed, a.path_offset + plocal, sample);
               GenerateLightRay(sc, rng, o, d, w, origin_slot);
             } else {
+              const uint32_t lrow = Quotient(AMBER_ARG(cold, div_width), plocal);
               const EyeRayScene eye{AMBER_ARG(cold, scene.lens), AMBER_ARG(cold, scene.blades), AMBER_ARG(cold, scene.sensor)};
-              const uint32_t row_begin = AMBER_ARG(cold, row_begin), stripe_rows = AMBER_ARG(cold, stripe_rows), stripe_period = AMBER_ARG(cold, stripe_period);
-              const uint32_t lrow = plocal / eye.sensor.w;
+              const uint32_t row_begin = AMBER_ARG(cold, row_begin), stripe_rows = AMBER_ARG(cold, stripe_rows);
               const uint32_t px = plocal - lrow * eye.sensor.w;
-              const uint32_t py = row_begin + (stripe_rows ? (lrow / stripe_rows) * stripe_period + lrow % stripe_rows : lrow);
-              rng = XorShiftSeed(hashed_seed, px + py * eye.sensor.w, first_sample + k);   // Image index x + y*W (image.h:116-124)
+              uint32_t py = row_begin + lrow;
+              if (stripe_rows) {                              // 0 = contiguous rows: no divider
+                const uint32_t band = Quotient(AMBER_ARG(cold, div_stripe_rows), lrow);
+                py = row_begin + band * AMBER_ARG(cold, stripe_period) + (lrow - band * stripe_rows);
+              }
+              rng = XorShiftSeed(AMBER_ARG(cold, hashed_seed), px + py * eye.sensor.w, sample);   // Image index x + y*W (image.h:116-124)
               float ew;
               bool near_edge = false;
               GenerateEyeRay(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
               w = v3(ew, ew, ew);                             // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
+              // (the pointer is read here and once more below, not held across the bookkeeping above: the two scalar registers it would occupy
+              //  there are what the dividers need, and the loop has none to spare -- tests/test_headline_kernel_spills.py)
+              const uint32_t* const pixel_mask = kTwoPhase ? AMBER_ARG(cold, pixel_mask) : nullptr;
               if (kTwoPhase && pixel_mask) {
                 // the candidates of this pixel's beam, plus the ray's own aperture blade (the self trip decides it exactly), plus
                 // every blade when the aperture sample lies on a blade's boundary (only then can a neighbour's exact test see it)
@@ -199,7 +205,7 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
             casts = 0;
             if (kSig) { sig_obj = 2166136261u; sig_t = 2166136261u; }
           }
-          primary = pixel_mask != nullptr;
+          primary = kTwoPhase && !kLight && AMBER_ARG(AMBER_COLD_OPEN(), pixel_mask) != nullptr;
           AMBER_STAMP(1);
         }
       }
@@ -213,7 +219,7 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
     if (alive) {
       if (!kLight && carries) meas = ld3(AMBER_CARRIED());
       if (kLight) {
-        const uint32_t plocal = q / a.n_samples;
+        const uint32_t plocal = Quotient(a.div_samples, q);
         const SplatSink sink{a.splats, a.splat_count, a.splat_capacity, a.path_offset + plocal, a.first_sample + (q - plocal * a.n_samples), sc.sensor.size_f};
         alive = PathStep<false, kEngine, true>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
       } else if (kSig) {
@@ -235,7 +241,7 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
     if (kCold) {
       EmitRecords([]() {                                      // the record buffers: cold arguments, read when a wave has a record to write (2e-5 of the Cornell paths)
         const ColdArgs cold = ColdArgs::Open();
-        return RecordSink{AMBER_COLD(cold, records), AMBER_COLD(cold, flags), AMBER_COLD(cold, touched), AMBER_COLD(cold, rec_count), AMBER_COLD(cold, rec_capacity), AMBER_COLD(cold, n_samples)};
+        return RecordSink{AMBER_COLD(cold, records), AMBER_COLD(cold, flags), AMBER_COLD(cold, touched), AMBER_COLD(cold, rec_count), AMBER_COLD(cold, rec_capacity), AMBER_COLD(cold, div_samples)};
       }, emit, q, meas, rec_next, rec_end);
     }
   }

@@ -65,13 +65,13 @@ __global__ void rec_scan_blocks_kernel(uint32_t* __restrict__ block_sum, uint32_
   }
 }
 __global__ void rec_place_kernel(const uint4* __restrict__ records, const unsigned int* __restrict__ rec_count, uint32_t rec_capacity, const uint32_t* __restrict__ flags,
-                                 const uint32_t* __restrict__ excl, const uint32_t* __restrict__ block_sum, uint32_t n_samples, float* __restrict__ sorted) {
+                                 const uint32_t* __restrict__ excl, const uint32_t* __restrict__ block_sum, uint32_t n_samples, ExactDiv div_samples, float* __restrict__ sorted) {
   const uint32_t n = *rec_count;
   if (n > rec_capacity) return;                               // out of slots: the launch is repeated
   for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
     const uint4 r = records[k];
     if (r.x == AMBER_REC_UNUSED) continue;
-    const uint32_t p = r.x / n_samples;
+    const uint32_t p = Quotient(div_samples, r.x);
     const uint32_t at = block_sum[p >> 8] + excl[p] + PixelBits(flags, p * n_samples, r.x);
     float* s = sorted + static_cast<size_t>(at) * 3u;
     s[0] = __uint_as_float(r.y); s[1] = __uint_as_float(r.z); s[2] = __uint_as_float(r.w);

@@ -31,6 +31,11 @@ struct WfArgs {
   unsigned long long* ray_count;
   uint64_t hashed_seed;
   uint32_t row_begin, stripe_rows, stripe_period, n_pixels;
+  ExactDiv div_stripe_rows, div_width;   // lrow / stripe_rows (unused when 0), plocal / scene.sensor.w: exact dividers (exact_div.h)
+  void SetBand(uint32_t row_begin_, uint32_t stripe_rows_, uint32_t stripe_period_) {    // the fields and their dividers together (as RenderArgs::SetBand; call once `scene` is set)
+    row_begin = row_begin_; stripe_rows = stripe_rows_; stripe_period = stripe_period_;
+    div_stripe_rows = MakeExactDiv(stripe_rows_); div_width = MakeExactDiv(scene.sensor.w);
+  }
   uint32_t first_sample, n_samples; // samples of this batch
   uint32_t n_paths;                 // n_chunks * n_pixels * AMBER_ACCUM_CHUNK
   uint32_t bounce;
@@ -47,9 +52,9 @@ __global__ void __launch_bounds__(256) wf_generate_kernel(const WfArgs a) {
     float* m = a.meas + static_cast<size_t>(pid) * 3u;
     m[0] = 0.f; m[1] = 0.f; m[2] = 0.f;
     const bool live = s_rel < a.n_samples;             // the last chunk may be short
-    const uint32_t lrow = plocal / sc.sensor.w;
+    const uint32_t lrow = Quotient(a.div_width, plocal);
     const uint32_t px = plocal - lrow * sc.sensor.w;
-    const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);
+    const uint32_t py = FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow);
     uint64_t rng = XorShiftSeed(a.hashed_seed, px + py * sc.sensor.w, a.first_sample + s_rel);
     V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f); float ew = 0.f; int origin_slot = -1;
     if (live) GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot);
