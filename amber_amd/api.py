@@ -642,8 +642,9 @@ class PathTracer:
                                                  pos.ctypes.data, nrm.ctypes.data))
         return obj, t, pos, nrm
 
-    def kat_sample(self, material, normals, dirs_out, rng_state):
-        m = np.ascontiguousarray(material, np.uint32)
+    def kat_sample(self, material, normals, dirs_out, rng_state, importance: bool = False):
+        """SampleLight of material[i], or (importance) SampleImportance, the light-tracing side: bit 31 of the index (amber_hip_lab.h)."""
+        m = np.ascontiguousarray(material, np.uint32) | np.uint32(0x80000000 if importance else 0)
         nn, dd = _f32(normals).reshape(-1, 3), _f32(dirs_out).reshape(-1, 3)
         st = np.ascontiguousarray(rng_state, np.uint64).copy()
         n = len(m)

@@ -109,7 +109,7 @@ int amber_hip_kat_sample(amber_hip_pt* h, uint32_t n, const uint32_t* material, 
   if (!h || !material || !normals || !dirs_out || !rng_state || !out_dir_in || !out_weight) return Fail(AMBER_EINVAL, "null argument");
   if (n == 0) return AMBER_OK;
   for (uint32_t i = 0; i < n; i++)
-    if (material[i] >= h->n_materials) return Fail(AMBER_EINVAL, "material index out of range");
+    if ((material[i] & 0x7fffffffu) >= h->n_materials) return Fail(AMBER_EINVAL, "material index out of range");   // bit 31: SampleImportance
   HIP_TRY(hipSetDevice(h->device));
   DevBuf<uint32_t> d_m; DevBuf<float> d_n, d_d, d_o, d_w; DevBuf<uint64_t> d_r;
   HIP_TRY(d_m.alloc(n)); HIP_TRY(d_n.alloc(3 * n)); HIP_TRY(d_d.alloc(3 * n)); HIP_TRY(d_o.alloc(3 * n)); HIP_TRY(d_w.alloc(3 * n)); HIP_TRY(d_r.alloc(n));

@@ -37,10 +37,11 @@ __global__ void kat_sample_kernel(const DevScene sc, uint32_t n, const uint32_t*
                                   const float* dirs_out, uint64_t* rng_state, float* out_dir, float* out_w) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const DevMaterial m = sc.materials[material[i]];
+  const DevMaterial m = sc.materials[material[i] & 0x7fffffffu];
   uint64_t rng = rng_state[i];
   V3 di, w;
-  SampleLight(m, ld3(normals + 3 * i), ld3(dirs_out + 3 * i), rng, di, w);
+  if (material[i] >> 31) SampleImportance(m, ld3(normals + 3 * i), ld3(dirs_out + 3 * i), rng, di, w);   // bit 31: the light-tracing side
+  else SampleLight(m, ld3(normals + 3 * i), ld3(dirs_out + 3 * i), rng, di, w);
   rng_state[i] = rng;
   out_dir[3 * i] = di.x; out_dir[3 * i + 1] = di.y; out_dir[3 * i + 2] = di.z;
   out_w[3 * i] = w.x; out_w[3 * i + 1] = w.y; out_w[3 * i + 2] = w.z;

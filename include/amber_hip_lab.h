@@ -23,7 +23,8 @@ extern "C" {
 /* closest hit: out_object = object index or -1 */
 int amber_hip_kat_cast(amber_hip_pt*, uint32_t n, const float* origins /*n*3*/, const float* dirs /*n*3*/,
                        int32_t* out_object, float* out_t, float* out_pos /*n*3*/, float* out_normal /*n*3*/);
-/* material sampling with a per-item XorShift state; returns dir_in, weight and the advanced state */
+/* material sampling with a per-item XorShift state; returns dir_in, weight and the advanced state.
+ * material[i]: the material index, | 0x80000000 for SampleImportance (the light-tracing side) instead of SampleLight */
 int amber_hip_kat_sample(amber_hip_pt*, uint32_t n, const uint32_t* material /*n*/, const float* normals,
                          const float* dirs_out, uint64_t* rng_state /*n, in/out*/, float* out_dir_in, float* out_weight);
 /* eye rays for (pixel index, sample) pairs: out = origin[3] dir[3] weight */

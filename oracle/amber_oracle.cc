@@ -1761,6 +1761,18 @@ uint32_t oracle_sample_material(const oracle_material* m, const float normal[3],
   dir_in[0] = s.dir.x; dir_in[1] = s.dir.y; dir_in[2] = s.dir.z; weight[0] = s.weight.x; weight[1] = s.weight.y; weight[2] = s.weight.z;
   return smp.i;
 }
+// oracle_sample_material with the uniforms of an XorShift state; importance != 0: Scene::SampleImportance (the light-tracing side)
+uint32_t oracle_sample_material_xorshift(const oracle_material* m, const float normal[3], const float dir_out[3], uint64_t state,
+                                         int importance, int math, float dir_in[3], float weight[3]) {
+  const Math M{math};
+  Material mm; mm.kind = m->kind; mm.rho = v3(m->rho[0], m->rho[1], m->rho[2]); mm.param = m->param;
+  if (mm.kind == ORACLE_MAT_REFRACTION) mm.r0 = Fresnel(mm.param, Math{ORACLE_MATH_LIBM});
+  struct Counting : XorShiftSampler { uint32_t n = 0; using XorShiftSampler::XorShiftSampler; double operator()() override { n++; return XorShiftSampler::operator()(); } } smp(state);
+  const V3 nn = v3(normal[0], normal[1], normal[2]), dd = v3(dir_out[0], dir_out[1], dir_out[2]);
+  const Scatter s = importance ? SampleImportance(mm, nn, dd, smp, M) : SampleLight(mm, nn, dd, smp, M);
+  dir_in[0] = s.dir.x; dir_in[1] = s.dir.y; dir_in[2] = s.dir.z; weight[0] = s.weight.x; weight[1] = s.weight.y; weight[2] = s.weight.z;
+  return smp.n;
+}
 void oracle_radiance(const oracle_material* m, const float normal[3], const float dir_out[3], float out[3]) {
   Material mm; mm.kind = m->kind; mm.rho = v3(m->rho[0], m->rho[1], m->rho[2]); mm.param = m->param;
   const V3 r = Radiance(mm, v3(normal[0], normal[1], normal[2]), v3(dir_out[0], dir_out[1], dir_out[2]));

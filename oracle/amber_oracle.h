@@ -191,6 +191,9 @@ int oracle_aabb_intersect(const float bmin[3], const float bmax[3], const float 
 /* material sampling: uniforms consumed in order from u[]; returns number consumed */
 uint32_t oracle_sample_material(const oracle_material* m, const float normal[3], const float dir_out[3],
                                 const double* u, uint32_t n_u, int math, float dir_in[3], float weight[3]);
+/* the same with the uniforms of the XorShift stream that starts at `state`; importance != 0: Scene::SampleImportance (light tracing) */
+uint32_t oracle_sample_material_xorshift(const oracle_material* m, const float normal[3], const float dir_out[3], uint64_t state,
+                                         int importance, int math, float dir_in[3], float weight[3]);
 void oracle_radiance(const oracle_material* m, const float normal[3], const float dir_out[3], float out[3]);
 /* eye ray: 5 uniforms in draw order (blade, tri-u, tri-v, jitter-Y, jitter-X -- g++ order) */
 void oracle_eye_ray(const oracle_scene*, const oracle_sensor*, uint32_t px, uint32_t py, const double u[5],

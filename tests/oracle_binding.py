@@ -104,6 +104,8 @@ def load():
     L.oracle_sample_material.restype = u32
     L.oracle_sample_material.argtypes = [C.POINTER(OMaterial), C.POINTER(f), C.POINTER(f), C.POINTER(C.c_double), u32, C.c_int,
                                          C.POINTER(f), C.POINTER(f)]
+    L.oracle_sample_material_xorshift.restype = u32
+    L.oracle_sample_material_xorshift.argtypes = [C.POINTER(OMaterial), vp, vp, u64, C.c_int, C.c_int, vp, vp]
     L.oracle_radiance.argtypes = [C.POINTER(OMaterial), C.POINTER(f), C.POINTER(f), C.POINTER(f)]
     L.oracle_eye_ray.argtypes = [vp, C.POINTER(OSensor), u32, u32, C.POINTER(C.c_double), C.c_int, C.POINTER(f), C.POINTER(f),
                                  C.POINTER(f), C.POINTER(f), C.POINTER(u32)]
