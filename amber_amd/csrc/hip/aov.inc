@@ -6,12 +6,10 @@
 //                         sums (AmberAovPixel: two float4) live in registers: read once, one binary32 addition per component and hit, written once.
 //                         No sort, no atomics: the sums are the sequential definition of include/amber_hip.h by construction, and a pass over
 //                         [a, a + m + n) leaves the bits of the two passes [a, a + m), [a + m, a + m + n).
-//                         LIST, TWO_PHASE, TWO_PHASE_N, REFERENCE_BVH as ray_query_kernel runs them: the two-phase image staged once per workgroup,
-//                         object loops wave-uniform (a lane beyond the band repeats the last pixel and stores nothing), a grid no larger than the render
-//                         kernels' (REFERENCE_BVH's traversal stack has one column per thread of THAT grid), each thread taking every
-//                         gridDim.x * 256-th pixel.  Engine BVH: the one-shot per-lane traversal of pt_megakernel<ENGINE_BVH> (BvhRoundOn on
-//                         BvhStackLds) with the whole AMBER_BVH_STACK levels in LDS, so a tree of any depth the builders emit is walked; a stack
-//                         overflow, and an origin outside the scene's bounding sphere (BvhOriginInRange, as bvh_query_kernel), take the leaf-list scan.
+//                         LIST, TWO_PHASE, TWO_PHASE_N, REFERENCE_BVH as ray_query_kernel runs them, on the front end they share (dev_closest_hit.h:
+//                         StageEngineLds, ClampToLastItem; LaunchPerItem's grid), each thread taking every gridDim.x * 256-th pixel.  Engine BVH: the one-shot
+//                         per-lane traversal of pt_megakernel<ENGINE_BVH> with the whole AMBER_BVH_STACK levels in LDS, so a tree of any depth the builders
+//                         emit is walked; a stack overflow, and an origin outside the scene's bounding sphere, take the leaf-list scan (ClosestHitBvh<true>).
 // Parallelism is the band's pixel count: a band of few pixels with many samples keeps few lanes busy however long the pass is.  That is accepted --
 // guide images are taken at a handful of samples over a whole frame, where every CU has work.
 // Waves per SIMD: engine BVH takes the point of the ray queries (AMBER_QUERY_WAVES = 5: five workgroups of 32 KiB of LDS stack fill a CU's 160 KiB);
@@ -34,14 +32,11 @@ struct AovArgs {
 template <int kEngine>
 __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? AMBER_QUERY_WAVES : 1) aov_kernel(const AovArgs a) {
   const DevScene& sc = a.scene;
-  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
-  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
-  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? AMBER_BVH_STACK * 256 : 1];
-  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  const EngineLds lds = StageEngineLds<kEngine, AMBER_BVH_STACK>(sc);
   for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * 256u; base < a.n_pixels; base += static_cast<uint64_t>(gridDim.x) * 256u) {   // uniform over the workgroup
     const uint64_t i = base + threadIdx.x;
     const bool mine = i < a.n_pixels;
-    const uint32_t plocal = mine ? static_cast<uint32_t>(i) : a.n_pixels - 1u;      // keep the object loops wave-uniform for every lane
+    const uint32_t plocal = static_cast<uint32_t>(ClampToLastItem<uint64_t>(i, a.n_pixels));
     const uint32_t lrow = Quotient(a.div_width, plocal), px = plocal - lrow * sc.sensor.w;
     const uint32_t py = FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow);
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
@@ -52,24 +47,16 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? AMBER_QUERY_WAVES
       GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot);
       HitRec h;
       if constexpr (kEngine == ENGINE_BVH) {
-        BvhTrav tr;
-        BvhBegin(sc, o, d, tr, h);
-        if (tr.cur != AMBER_BVH_DONE && !BvhOriginInRange(sc, o)) { tr.cur = AMBER_BVH_DONE; tr.overflow = true; }   // the tree does not cover this origin: the scan below
-        const BvhStackLds stack{lds_stack + threadIdx.x, AMBER_BVH_STACK};
-        while (BvhRoundOn<BvhStackLds, AMBER_ONE_SHOT_BVH_BUDGET>(sc, stack, o, d, tr, h)) {}
-        if (tr.overflow) ClosestHitLeafList(sc, o, d, h);
-        BvhResolveIndex(sc, h);
+        ClosestHitBvh<true>(sc, lds.stack, o, d, h);
       } else {
 #ifdef AMBER_STAMPS
         StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-        ClosestHit<kEngine>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG);
+        ClosestHit<kEngine>(sc, lds.objects, lds.stack, o, d, origin_slot, h AMBER_STAMP_ARG);
       }
-      // every exact test forms dot products over all components of o and d: a NaN component makes every distance NaN, which no hit accepts
-      const bool nan_ray = !(o.x == o.x && o.y == o.y && o.z == o.z && d.x == d.x && d.y == d.y && d.z == d.z);
-      if (h.idx >= 0 && !nan_ray) {
+      if (h.idx >= 0 && !IsNanRay(o, d)) {
         V3 pos, nrm; uint32_t mat;
-        ResolveHit<kEngine == ENGINE_TWO_PHASE_N ? 0x7fu : 0xffu>(kTwoPhase ? lds_objects : (kEngine == ENGINE_BVH || kEngine == ENGINE_REF_BVH ? sc.bvh_objects : sc.objects), h, o, d, pos, nrm, mat);
+        ResolveHit<kEngine>(sc, lds.objects, h, o, d, pos, nrm, mat);
         const float* rho = sc.materials[mat].rho;
         s0.x = s0.x + rho[0]; s0.y = s0.y + rho[1]; s0.z = s0.z + rho[2]; s0.w = s0.w + h.t;
         s1.x = s1.x + nrm.x; s1.y = s1.y + nrm.y; s1.z = s1.z + nrm.z; s1.w = s1.w + 1.0f;
@@ -107,17 +94,9 @@ int AovPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
   a.scene = h->scene; a.aov = h->d_aov; a.hashed_seed = h->hashed_seed;
   a.n_pixels = n_pixels; a.first_sample = first_sample; a.n_samples = n_samples;
   a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period);
-  const uint32_t by_work = (n_pixels + 255u) / 256u;                          // n_pixels < 2^32
-  const uint32_t max_blocks = h->hit_engine == AMBER_ENGINE_BVH ? static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_QUERY_WAVES) : PersistentBlocks(h);
-  const uint32_t n_blocks = by_work < max_blocks ? by_work : max_blocks;
-  { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
-  WithHitEngine(h->hit_engine, [&](auto engine) -> int {
-    constexpr int kEngine = decltype(engine)::value;
-    hipLaunchKernelGGL((aov_kernel<kEngine>), dim3(n_blocks), dim3(256), 0, h->stream, a);
-    return AMBER_OK;
+  return LaunchPerItem(h, n_pixels, [&](auto engine, uint32_t n_blocks) {
+    hipLaunchKernelGGL((aov_kernel<decltype(engine)::value>), dim3(n_blocks), dim3(256), 0, h->stream, a);
   });
-  HIP_TRY(hipGetLastError());
-  return AMBER_OK;
 }
 
 int AovClear(amber_hip_pt* h) {
@@ -149,20 +128,6 @@ int DeviceAov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
   *dptr = h->d_aov;                                                           // (null for an empty band)
   if (n_pixels) *n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
   return AMBER_OK;
-}
-
-// No exception crosses the C boundary (the messages are std::strings: forming one may throw, so the handlers form none).
-template <typename F>
-int AovGuarded(F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    g_last_error.clear();
-    return AMBER_ENOMEM;
-  } catch (...) {
-    g_last_error.clear();
-    return AMBER_EHIP;
-  }
 }
 
 }  // namespace

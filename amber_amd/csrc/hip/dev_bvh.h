@@ -495,9 +495,12 @@ __device__ __forceinline__ bool AnyHitLeafList(const DevScene& sc, V3 o, V3 d, f
   return best.slot >= 0;
 }
 
+// kAnyOrigin (aov_kernel; bvh_query_kernel does this in its resumable form): the ray may start anywhere -- an origin outside the scene's bounding sphere takes the leaf-list scan.
+template <bool kAnyOrigin = false>
 __device__ __forceinline__ void ClosestHitBvh(const DevScene& sc, int32_t* lds_stack, V3 o, V3 d, HitRec& best, const int stack_cap = AMBER_BVH_STACK) {
   BvhTrav tr;
   BvhBegin(sc, o, d, tr, best);
+  if (kAnyOrigin && tr.cur != AMBER_BVH_DONE && !BvhOriginInRange(sc, o)) { tr.cur = AMBER_BVH_DONE; tr.overflow = true; }   // the tree does not cover this origin: the scan below
   const BvhStackLds stack{lds_stack + threadIdx.x, stack_cap};
   while (BvhRoundOn<BvhStackLds, AMBER_ONE_SHOT_BVH_BUDGET>(sc, stack, o, d, tr, best)) {}
   if (__any(tr.overflow)) { if (tr.overflow) ClosestHitLeafList(sc, o, d, best); }

@@ -1,4 +1,4 @@
-// dev_closest_hit.h -- part of pt_device.h (included from there, in order; not a stand-alone header): engine REFERENCE_BVH (the reference's own tree in the reference's order); the engine switch ClosestHit<kEngine>; ResolveHit.
+// dev_closest_hit.h -- part of pt_device.h (included from there, in order; not a stand-alone header): engine REFERENCE_BVH (the reference's own tree in the reference's order); the engine switch ClosestHit<kEngine>; ResolveHit; what a kernel states about its engine (EngineTraits, StageEngineLds, HitObjects).
 #pragma once
 
 namespace amber_dev {
@@ -164,5 +164,39 @@ __device__ __forceinline__ void StageObjects(const DevScene& sc, DevObject* lds_
   for (uint32_t k = threadIdx.x; k < n_dwords; k += blockDim.x) dst[k] = src[k];
   __syncthreads();
 }
+
+// What the kernels know of an engine beyond its closest hit, said once.
+template <int kEngine>
+struct EngineTraits {
+  static constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;                                         // has an LDS image of the objects
+  static constexpr int kLdsObjects = kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1);   // ... of so many records
+  static constexpr uint32_t kKindMask = kLdsKindMask<kEngine == ENGINE_TWO_PHASE_N>;                                                      // the primitive kind in the record HitRec.slot names
+};
+// The array HitRec.slot indexes: the LDS image for the two-phase engines, the leaf-order records for the two tree engines, the scene's own for LIST.
+template <int kEngine>
+__device__ __forceinline__ const DevObject* HitObjects(const DevScene& sc, const DevObject* lds_objects) {
+  return EngineTraits<kEngine>::kTwoPhase ? lds_objects : ((kEngine == ENGINE_BVH || kEngine == ENGINE_REF_BVH) ? sc.bvh_objects : sc.objects);
+}
+template <int kEngine>
+__device__ __forceinline__ void ResolveHit(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3 o, V3 d, V3& pos, V3& normal, uint32_t& material) {
+  ResolveHit<EngineTraits<kEngine>::kKindMask>(HitObjects<kEngine>(sc, lds_objects), h, o, d, pos, normal, material);
+}
+
+// The LDS of a kernel that casts through ClosestHit<kEngine>, declared and staged (the two-phase image; ends with a barrier: every thread calls it, once, before anything
+// diverges).  kStackLevels: engine BVH's one-shot traversal stack, [level][thread of 256].  What an engine does not use is one element that nothing reads: not allocated.
+struct EngineLds { DevObject* objects; int32_t* stack; };
+template <int kEngine, int kStackLevels>
+__device__ __forceinline__ EngineLds StageEngineLds(const DevScene& sc) {
+  __shared__ DevObject lds_objects[EngineTraits<kEngine>::kLdsObjects];
+  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? kStackLevels * 256 : 1];
+  if (EngineTraits<kEngine>::kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  return EngineLds{lds_objects, lds_stack};
+}
+
+// One thread per item: a lane beyond the last item repeats the last one (and stores nothing), so that the object loops of ClosestHit stay wave-uniform.
+template <typename T>
+__device__ __forceinline__ T ClampToLastItem(T i, T n) { return i < n ? i : n - 1; }
+// every exact test forms dot products over all components of o and d: a NaN component makes every distance NaN, which no hit accepts
+__device__ __forceinline__ bool IsNanRay(V3 o, V3 d) { return !(o.x == o.x && o.y == o.y && o.z == o.z && d.x == d.x && d.y == d.y && d.z == d.z); }
 
 }  // namespace amber_dev

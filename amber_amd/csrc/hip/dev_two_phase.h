@@ -47,6 +47,8 @@ __device__ __forceinline__ void ClosestHitTwoPhaseGroups(const DevScene& sc, con
     ClosestHitTwoPhaseView<true, false>(sc, fv, lds_objects, o_world, d, origin_slot, best AMBER_STAMP_ARG, false, 0u);
   }
 }
+// The primitive kind in a record of the LDS image: the two-phase engines tag `kind` with index << 8; the grouped engine's records also flag filtered triangles in bit 7.
+template <bool kGrouped> constexpr uint32_t kLdsKindMask = kGrouped ? 0x7fu : 0xffu;
 // kMulti = false: the 32-object engine -- the code of rounds 2-4, operand for operand (slot base 0, the kind byte unmasked: a 1.2 % slower config-2 kernel was
 // the price of sharing ONE instantiation with the grouped engine, tools/ab_lib.py across the round's commits).
 template <bool kMulti, bool kFirst>
@@ -56,7 +58,7 @@ __device__ __forceinline__ void ClosestHitTwoPhaseView(const DevScene& sc, const
   const int slot_base = kMulti ? fv.slot_base : 0;
   const DevObject* lds_objects = kMulti ? lds_objects_all + slot_base : lds_objects_all;
   const int origin_slot = kFirst ? origin_slot_all : ((origin_slot_all >= slot_base && origin_slot_all < slot_base + 32) ? origin_slot_all - slot_base : -1);
-  constexpr uint32_t kKindMask = kMulti ? 0x7fu : 0xffu;       // the grouped engine's LDS records flag filtered triangles in bit 7 of `kind`
+  constexpr uint32_t kKindMask = kLdsKindMask<kMulti>;
   uint32_t cand = kMulti ? fv.always_mask : sc.always_mask;      // (kMulti = false reads the scene record where rounds 2-4 read it: nothing of `fv` is live)
   // use_premask (WAVE-UNIFORM): the candidates are already known -- a primary round of pt_megakernel, whose 64 eye rays take them
   // from their pixel's mask (pixel_mask_kernel: every object some ray of the pixel's beam can hit, computed once per handle) --

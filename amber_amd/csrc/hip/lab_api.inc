@@ -85,7 +85,7 @@ extern "C" {
 
 // ---- KAT entry points -----------------------------------------------------------------------------
 int amber_hip_kat_cast(amber_hip_pt* h, uint32_t n, const float* origins, const float* dirs,
-                       int32_t* out_object, float* out_t, float* out_pos, float* out_normal) {
+                       int32_t* out_object, float* out_t, float* out_pos, float* out_normal) { return Guarded("amber_hip_kat_cast", [&]() -> int {
   if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);
   if (!h || !origins || !dirs || !out_object || !out_t || !out_pos || !out_normal) return Fail(AMBER_EINVAL, "null argument");
   if (n == 0) return AMBER_OK;
@@ -102,10 +102,10 @@ int amber_hip_kat_cast(amber_hip_pt* h, uint32_t n, const float* origins, const 
   HIP_TRY(hipMemcpy(out_pos, d_p.p, 12ull * n, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_normal, d_n.p, 12ull * n, hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
 int amber_hip_kat_sample(amber_hip_pt* h, uint32_t n, const uint32_t* material, const float* normals,
-                         const float* dirs_out, uint64_t* rng_state, float* out_dir_in, float* out_weight) {
+                         const float* dirs_out, uint64_t* rng_state, float* out_dir_in, float* out_weight) { return Guarded("amber_hip_kat_sample", [&]() -> int {
   if (!h || !material || !normals || !dirs_out || !rng_state || !out_dir_in || !out_weight) return Fail(AMBER_EINVAL, "null argument");
   if (n == 0) return AMBER_OK;
   for (uint32_t i = 0; i < n; i++)
@@ -124,9 +124,9 @@ int amber_hip_kat_sample(amber_hip_pt* h, uint32_t n, const uint32_t* material, 
   HIP_TRY(hipMemcpy(out_dir_in, d_o.p, 12ull * n, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_weight, d_w.p, 12ull * n, hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_kat_eye(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const uint32_t* sample, float* out7) {
+int amber_hip_kat_eye(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const uint32_t* sample, float* out7) { return Guarded("amber_hip_kat_eye", [&]() -> int {
   if (!h || !pixel || !sample || !out7) return Fail(AMBER_EINVAL, "null argument");
   if (n == 0) return AMBER_OK;
   const uint32_t npx = h->scene.sensor.w * h->scene.sensor.h;
@@ -141,10 +141,10 @@ int amber_hip_kat_eye(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const 
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out7, d_o.p, 28ull * n, hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
 int amber_hip_kat_trace(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const uint32_t* sample,
-                        uint32_t max_bounces, uint32_t* out_records, uint32_t* out_casts) {
+                        uint32_t max_bounces, uint32_t* out_records, uint32_t* out_casts) { return Guarded("amber_hip_kat_trace", [&]() -> int {
   if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);
   if (!h || !pixel || !sample || !out_records || !out_casts || max_bounces == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (n == 0) return AMBER_OK;
@@ -163,9 +163,9 @@ int amber_hip_kat_trace(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, cons
   HIP_TRY(hipMemcpy(out_records, d_r.p, nrec * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_casts, d_c.p, 4ull * n, hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_kat_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint64_t* out) {
+int amber_hip_kat_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint64_t* out) { return Guarded("amber_hip_kat_signatures", [&]() -> int {
   if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);
   if (!h || !out || n_samples == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
@@ -176,18 +176,18 @@ int amber_hip_kat_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   DevBuf<unsigned long long> d_out;
   HIP_TRY(d_out.alloc(n));
   const dim3 grid(static_cast<uint32_t>((n + 255) / 256));
-  WithKatEngine(h, [&](auto engine) { hipLaunchKernelGGL(kat_signature_kernel<decltype(engine)::value>, grid, dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, first_sample, n_samples, h->row_begin, h->stripe_rows, h->stripe_period, d_out.p); });
+  WithKatEngine(h, [&](auto engine) { hipLaunchKernelGGL(kat_signature_kernel<decltype(engine)::value>, grid, dim3(256), 0, h->stream, h->scene, h->hashed_seed, n, first_sample, n_samples, h->row_begin, h->stripe_rows, h->stripe_period, MakeExactDiv(h->stripe_rows), d_out.p); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
 // Traversal alone (bvh_stream.inc): closest hits of n rays through engine BVH's resumable traversal in a kernel that does nothing
 // else, `waves` resident waves per SIMD (4, 5, 6 or 8), idle lanes refilled once `refill_min` of a wave's lanes are idle.
 // Returns t (NaN = miss) and the object index per ray, and the kernel time of `repeats` launches (the best one).
 int amber_hip_kat_traversal_rate(amber_hip_pt* h, uint32_t n, const float* origins, const float* dirs, uint32_t waves, uint32_t refill_min, uint32_t repeats,
-                                 float* out_t, int32_t* out_object, double* best_ms, uint32_t* out_rounds) {
+                                 float* out_t, int32_t* out_object, double* best_ms, uint32_t* out_rounds) { return Guarded("amber_hip_kat_traversal_rate", [&]() -> int {
   // one launch walks the ray array `repeats` times (a launch of n * repeats rays); best_ms is the time of that launch
   if (!h || !origins || !dirs || !out_t || !out_object || n == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (h->hit_engine != AMBER_ENGINE_BVH) return Fail(AMBER_EINVAL, "the handle's engine is not BVH");
@@ -239,9 +239,9 @@ int amber_hip_kat_traversal_rate(amber_hip_pt* h, uint32_t n, const float* origi
   }
   if (best_ms) *best_ms = best;
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_kat_pixel_masks(amber_hip_pt* h, uint32_t* out_mask, uint32_t* out_slot_of_object, uint32_t* out_always_mask, double* kernel_ms) {
+int amber_hip_kat_pixel_masks(amber_hip_pt* h, uint32_t* out_mask, uint32_t* out_slot_of_object, uint32_t* out_always_mask, double* kernel_ms) { return Guarded("amber_hip_kat_pixel_masks", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   if (!h->two_phase) return Fail(AMBER_EINVAL, "pixel masks belong to the two-phase engine");
   HIP_TRY(hipSetDevice(h->device));
@@ -261,9 +261,9 @@ int amber_hip_kat_pixel_masks(amber_hip_pt* h, uint32_t* out_mask, uint32_t* out
   }
   if (out_always_mask) *out_always_mask = h->scene.always_mask | h->scene.blade_mask;
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_kat_bvh_dump(amber_hip_pt* h, uint32_t* nodes, uint32_t node_capacity, uint32_t* prims, uint32_t prim_capacity, AmberBvhDump* info) {
+int amber_hip_kat_bvh_dump(amber_hip_pt* h, uint32_t* nodes, uint32_t node_capacity, uint32_t* prims, uint32_t prim_capacity, AmberBvhDump* info) { return Guarded("amber_hip_kat_bvh_dump", [&]() -> int {
   if (!h || !info) return Fail(AMBER_EINVAL, "null argument");
   if (h->hit_engine != AMBER_ENGINE_BVH) return Fail(AMBER_EINVAL, "the handle's engine is not BVH");
   HIP_TRY(hipSetDevice(h->device));
@@ -276,9 +276,9 @@ int amber_hip_kat_bvh_dump(amber_hip_pt* h, uint32_t* nodes, uint32_t node_capac
   if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, h->scene.bvh_nodes, static_cast<size_t>(n_nodes) * sizeof(DevBvhNodeQ), hipMemcpyDeviceToHost));
   if (prims && n_prims) HIP_TRY(hipMemcpy(prims, h->scene.bvh_prims, static_cast<size_t>(n_prims) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint64_t* out) {
+int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint64_t* out) { return Guarded("amber_hip_pt_signatures", [&]() -> int {
   if (!h || !out || n_samples == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
   if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, "signatures come from the work-queue kernels (engines list, two_phase, bvh)");
@@ -301,9 +301,9 @@ int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_s
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, h->d_sig, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out) {
+int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out) { return Guarded("amber_hip_kat_math", [&]() -> int {
   if (!x || !out || mode < 0 || mode > 3) return Fail(AMBER_EINVAL, "bad argument");
   if (n == 0) return AMBER_OK;
   int n_dev = 0;
@@ -318,7 +318,7 @@ int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* 
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, d_o.p, n_out * 4, hipMemcpyDeviceToHost));
   return AMBER_OK;
-}
+}); }
 
 
 }  // extern "C"

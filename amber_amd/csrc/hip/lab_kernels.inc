@@ -8,17 +8,14 @@ template <int kEngine>
 __global__ void kat_cast_kernel(const DevScene sc, uint32_t n, const float* org, const float* dir,
                                 int32_t* out_obj, float* out_t, float* out_pos, float* out_n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t k = i < n ? i : n - 1;      // keep the object loop wave-uniform for every lane
-  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
-  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
-  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? AMBER_BVH_STACK * 256 : 1];
-  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  const uint32_t k = ClampToLastItem(i, n);
+  const EngineLds lds = StageEngineLds<kEngine, AMBER_BVH_STACK>(sc);
   const V3 o = ld3(org + 3 * k), d = ld3(dir + 3 * k);
   HitRec h;
 #ifdef AMBER_STAMPS
   StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-  ClosestHit<kEngine>(sc, lds_objects, lds_stack, o, d, -1, h AMBER_STAMP_ARG);
+  ClosestHit<kEngine>(sc, lds.objects, lds.stack, o, d, -1, h AMBER_STAMP_ARG);
   if (i >= n) return;
   out_obj[i] = h.idx;
   if (h.idx < 0) {
@@ -27,7 +24,7 @@ __global__ void kat_cast_kernel(const DevScene sc, uint32_t n, const float* org,
     return;
   }
   V3 pos, nrm; uint32_t mat;
-  ResolveHit<kEngine == ENGINE_TWO_PHASE_N ? 0x7fu : 0xffu>(kTwoPhase ? lds_objects : (kEngine == ENGINE_BVH ? sc.bvh_objects : sc.objects), h, o, d, pos, nrm, mat);
+  ResolveHit<kEngine>(sc, lds.objects, h, o, d, pos, nrm, mat);
   out_t[i] = h.t;
   out_pos[3 * i] = pos.x; out_pos[3 * i + 1] = pos.y; out_pos[3 * i + 2] = pos.z;
   out_n[3 * i] = nrm.x; out_n[3 * i + 1] = nrm.y; out_n[3 * i + 2] = nrm.z;
@@ -62,11 +59,8 @@ template <int kEngine>
 __global__ void kat_trace_kernel(const DevScene sc, uint64_t hashed_seed, uint32_t n, const uint32_t* pixel,
                                  const uint32_t* sample, uint32_t max_bounces, uint32_t* out_records, uint32_t* out_casts) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t k = i < n ? i : n - 1;
-  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
-  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
-  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? AMBER_BVH_STACK * 256 : 1];
-  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  const uint32_t k = ClampToLastItem(i, n);
+  const EngineLds lds = StageEngineLds<kEngine, AMBER_BVH_STACK>(sc);
   uint64_t rng = XorShiftSeed(hashed_seed, pixel[k], sample[k]);
   V3 o, d; float ew; int origin_slot;
   GenerateEyeRay(sc, pixel[k] % sc.sensor.w, pixel[k] / sc.sensor.w, rng, o, d, ew, origin_slot);
@@ -80,7 +74,7 @@ __global__ void kat_trace_kernel(const DevScene sc, uint64_t hashed_seed, uint32
 #ifdef AMBER_STAMPS
       StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-      alive = PathStep<true, kEngine>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG);
+      alive = PathStep<true, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG);
       if (i < n && casts <= max_bounces) {
         uint32_t* r = out_records + (static_cast<size_t>(i) * max_bounces + (casts - 1)) * 11u;
         r[0] = static_cast<uint32_t>(b.object);
@@ -99,16 +93,13 @@ __global__ void kat_trace_kernel(const DevScene sc, uint64_t hashed_seed, uint32
 // of every cast (low word; 0xffffffff = miss) and over the bits of every hit distance (high word).
 template <int kEngine>
 __global__ void kat_signature_kernel(const DevScene sc, uint64_t hashed_seed, uint64_t n, uint32_t first_sample, uint32_t n_samples,
-                                     uint32_t row_begin, uint32_t stripe_rows, uint32_t stripe_period, unsigned long long* out) {
+                                     uint32_t row_begin, uint32_t stripe_rows, uint32_t stripe_period, ExactDiv div_stripe_rows, unsigned long long* out) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  const uint64_t k = i < n ? i : n - 1;      // keep the scene loops wave-uniform for every lane
-  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
-  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
-  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? AMBER_BVH_STACK * 256 : 1];
-  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  const uint64_t k = ClampToLastItem(i, n);
+  const EngineLds lds = StageEngineLds<kEngine, AMBER_BVH_STACK>(sc);
   const uint32_t plocal = static_cast<uint32_t>(k / n_samples), smp = first_sample + static_cast<uint32_t>(k % n_samples);
   const uint32_t lrow = plocal / sc.sensor.w, px = plocal - lrow * sc.sensor.w;
-  const uint32_t py = row_begin + (stripe_rows ? (lrow / stripe_rows) * stripe_period + lrow % stripe_rows : lrow);
+  const uint32_t py = FrameRow(row_begin, stripe_rows, stripe_period, div_stripe_rows, lrow);
   uint64_t rng = XorShiftSeed(hashed_seed, px + py * sc.sensor.w, smp);
   V3 o, d; float ew; int origin_slot;
   GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot);
@@ -121,7 +112,7 @@ __global__ void kat_signature_kernel(const DevScene sc, uint64_t hashed_seed, ui
 #ifdef AMBER_STAMPS
       StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-      alive = PathStep<true, kEngine>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG);
+      alive = PathStep<true, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG);
       sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
       if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
     }

@@ -1,5 +1,7 @@
 // pt_host.hip -- the ONE translation unit of the gfx950 path-tracing engine: the handle, the host side of every launch and the C ABI
 // (include/amber_hip.h).  The kernels live in files of their own and are included here, where they are launched:
+//   c_boundary.h           the rule of the C ABI: no exception crosses an extern "C" function -- every entry point that can allocate or form a message runs under
+//                          Guarded(name, f) (bad_alloc / system_error -> AMBER_ENOMEM, anything else -> AMBER_EHIP); the thread-local message, Fail, HIP_TRY
 //   pt_args.h              RenderArgs; record emission (accumulation without owners)
 //   exact_div.h            exact division by a launch constant without a divide (the pixel bookkeeping of the render kernels)
 //   pt_megakernel.inc      pt_megakernel: persistent waves, work unit = ONE PATH (q = band pixel * n_samples + sample), a wave claims 1024 paths with
@@ -14,7 +16,8 @@
 //   bvh_update.inc         amber_hip_pt_update_objects: new object geometry into a live handle -- records converted and checked by a kernel, then the
 //                          tree made valid again on the device: refitted (any tree, topology kept) or rebuilt (the Morton tree, in place).
 //   ray_query.inc          amber_hip_pt_cast_rays / amber_hip_pt_occluded: the caller's rays through the handle's engine -- engine BVH in a persistent refill
-//                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>.
+//                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>;
+//                          LaunchPerItem, the launch of every kernel with a thread per item (its engine front end: dev_closest_hit.h).
 //   resolve.inc            amber_hip_pt_resolve: the framebuffer's sums as the mean or, through Filmic + Gamma, as 8-bit RGB / RGBA, in device memory --
 //                          a streaming kernel, four output pixels per thread, bytes equal to the host's output stage.
 //   aov.inc                amber_hip_pt_aov_pass and its three companions: the first-hit guide images (albedo, depth, normal, coverage) of the band --
@@ -38,9 +41,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <new>
 #include <string>
-#include <system_error>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -49,6 +50,7 @@
 #ifdef AMBER_LAB
 #include "../../../include/amber_hip_lab.h"
 #endif
+#include "c_boundary.h"
 #include "pt_device.h"
 #include "exact_div.h"
 #include "bvh_build.h"
@@ -58,16 +60,6 @@
 using namespace amber_dev;
 
 namespace {
-
-thread_local std::string g_last_error;
-
-int Fail(int code, const std::string& msg) { g_last_error = msg; return code; }
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return Fail(AMBER_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-  } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // render kernel
@@ -433,7 +425,6 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
 
 extern "C" {
 
-const char* amber_hip_last_error(void) { return g_last_error.c_str(); }
 int amber_hip_abi_version(void) { return AMBER_HIP_ABI_VERSION; }
 int amber_hip_math_mode(void) { return AMBER_MATH_MODE; }
 int amber_hip_device_count(void) {
@@ -443,15 +434,11 @@ int amber_hip_device_count(void) {
 }
 
 int amber_hip_pt_create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtParams* params, amber_hip_pt** out) {
-  if (!out || !params) return Fail(AMBER_EINVAL, "null argument");
-  *out = nullptr;
-  try {
+  return Guarded("amber_hip_pt_create", [&]() -> int {         // (std::system_error: std::async of the reference's build could not start a thread)
+    if (!out || !params) return Fail(AMBER_EINVAL, "null argument");
+    *out = nullptr;
     return Create(s, sensor, params, out);
-  } catch (const std::bad_alloc&) {
-    return Fail(AMBER_ENOMEM, "amber_hip_pt_create: out of host memory");
-  } catch (const std::system_error& e) {                       // e.g. std::async of the reference's build could not start a thread
-    return Fail(AMBER_ENOMEM, std::string("amber_hip_pt_create: ") + e.what());
-  }
+  });
 }
 
 }  // extern "C"
@@ -485,6 +472,12 @@ uint32_t ResidentBlocksPerCu(uint32_t hit_engine) {
   return hit_engine == AMBER_ENGINE_BVH ? static_cast<uint32_t>(AMBER_BVH_WGS) : (AMBER_MEGAKERNEL_WAVES_PER_SIMD > 5 ? static_cast<uint32_t>(AMBER_MEGAKERNEL_WAVES_PER_SIMD) : 5u);   // uncapped: 87 VGPRs -> 5
 }
 
+// Workgroups of 256 threads for n_items work units (one thread each), `resident` at the most.
+uint32_t BlocksFor(uint64_t n_items, uint32_t resident) {
+  const uint64_t by_work = n_items / 256u + (n_items % 256u != 0u);
+  return by_work < resident ? static_cast<uint32_t>(by_work) : resident;
+}
+
 // The grid of every persistent launch: workgroups of 256 threads, as many as fit the device at once, fewer if n_items work units (one
 // thread each) do not need them.  The default n_items gives the largest grid, for which engine REFERENCE_BVH's stack is sized.  `pool`:
 // pt_bvh_pool_kernel's grid (lab build).
@@ -493,8 +486,7 @@ uint32_t PersistentBlocks(const amber_hip_pt* h, uint64_t n_items, bool pool) {
 #ifdef AMBER_LAB
   if (pool) n_blocks = static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_BVH_POOL_WGS);
 #endif
-  const uint64_t by_work = n_items / 256u + (n_items % 256u != 0u);
-  return by_work < n_blocks ? static_cast<uint32_t>(by_work) : n_blocks;
+  return BlocksFor(n_items, n_blocks);
 }
 
 // The one mapping from a handle's closest-hit engine to the engine its kernels are instantiated with: f(std::integral_constant<int, kEngine>).
@@ -527,6 +519,14 @@ int Grow(amber_hip_pt* h, DevBuf<T>& b, size_t n, const char* what) {
   const hipError_t e = b.alloc(n);
   if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e));
   return AMBER_OK;
+}
+
+// What every launch of a render kernel states first: the scene, the seed, the handle's band, the samples and their chunks (with the dividers).
+RenderArgs MakeRenderArgs(const amber_hip_pt* h, uint64_t hashed_seed, uint32_t n_pixels, uint32_t first_sample, uint32_t n_samples) {
+  RenderArgs a{};
+  a.scene = h->scene; a.hashed_seed = hashed_seed; a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels;
+  a.SetSamples(first_sample, n_samples); a.n_chunks = (n_samples + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
+  return a;
 }
 
 }  // namespace
@@ -660,13 +660,11 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
     if (rc != AMBER_OK) return rc;
   }
 #endif
-  RenderArgs a{};
+  RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first, n);
   a.pixel_mask = h->pixel_mask_ready ? h->d_pixel_mask : nullptr;
-  a.scene = h->scene; a.flags = h->d_flags; a.touched = h->d_touched; a.records = h->d_records; a.rec_count = h->d_rec_count; a.rec_capacity = h->rec_capacity;
-  a.ray_count = h->d_rays_launch; a.next_item = h->d_launch_ctl; a.stamps = h->d_stamps; a.hashed_seed = h->hashed_seed;
-  a.bvh_stack = h->d_bvh_stack; a.carried = h->d_carried; a.sig = sig;
-  a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels; a.SetSamples(first, n);
-  a.n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK; a.n_items = static_cast<uint32_t>(n_paths);
+  a.flags = h->d_flags; a.touched = h->d_touched; a.records = h->d_records; a.rec_count = h->d_rec_count; a.rec_capacity = h->rec_capacity;
+  a.ray_count = h->d_rays_launch; a.next_item = h->d_launch_ctl; a.stamps = h->d_stamps;
+  a.bvh_stack = h->d_bvh_stack; a.carried = h->d_carried; a.sig = sig; a.n_items = static_cast<uint32_t>(n_paths);
   HIP_TRY(hipMemsetAsync(h->d_launch_ctl, 0, 4 * sizeof(unsigned int), h->stream));
   // The bitmap is cleared by the reduction itself where it can be (whole words per pixel); the host clears all of it only when a
   // launch left it dirty: the first use, sample counts that are not multiples of 32, signature launches, a launch that ran out of slots.
@@ -776,7 +774,7 @@ static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n
 namespace { int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples); }      // lab_api.inc
 #endif
 
-int amber_hip_pt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
+int amber_hip_pt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) { return Guarded("amber_hip_pt_render_pass", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   if (n_samples == 0) return AMBER_OK;
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
@@ -788,7 +786,7 @@ int amber_hip_pt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
 #endif
   if (h->hit_engine != AMBER_ENGINE_BVH || h->bvh_pool || h->bvh_paths) return RenderPassPaths(h, first_sample, n_samples, n_pixels);
   return RenderPassBvhItems(h, first_sample, n_samples, n_pixels, nullptr);
-}
+}); }
 
 // sig != null (amber_hip_pt_signatures): one launch of the signature instantiation; nothing reaches the framebuffer or the ray total
 static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t n_pixels, unsigned long long* sig) {
@@ -812,10 +810,9 @@ static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n
     { const int rc = Grow(h, h->d_partial, need, "partial sums"); if (rc != AMBER_OK) return rc; }
     if (sig && n != n_samples) return Fail(AMBER_EINVAL, "too many paths for one signature launch");
     if (sig) { const int rc = EnsureLaunchCtl(h); if (rc != AMBER_OK) return rc; }
-    RenderArgs a{};
-    a.scene = h->scene; a.partial = h->d_partial; a.ray_count = sig ? h->d_rays_launch : h->d_rays; a.next_item = h->d_next; a.stamps = h->d_stamps; a.hashed_seed = h->hashed_seed;
-    a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels; a.SetSamples(first_sample + done, n);
-    a.n_chunks = n_chunks; a.n_items = n_pixels * n_chunks; a.sig = sig; a.shade_batch = h->bvh_shade_batch;
+    RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first_sample + done, n);
+    a.partial = h->d_partial; a.ray_count = sig ? h->d_rays_launch : h->d_rays; a.next_item = h->d_next; a.stamps = h->d_stamps;
+    a.n_items = n_pixels * n_chunks; a.sig = sig; a.shade_batch = h->bvh_shade_batch;
     // persistent workers: one workgroup of 4 waves per CU and resident wave slot, fewer if the queue is short
     const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
     HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
@@ -840,7 +837,7 @@ static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n
 }
 
 int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end,
-                             AmberSplat* out, uint32_t capacity, uint32_t* n_out, uint64_t* ray_count) {
+                             AmberSplat* out, uint32_t capacity, uint32_t* n_out, uint64_t* ray_count) { return Guarded("amber_hip_lt_trace_range", [&]() -> int {
   if (!h || !n_out || (capacity && !out)) return Fail(AMBER_EINVAL, "null argument");
   *n_out = 0;
   if (ray_count) *ray_count = 0;
@@ -875,12 +872,11 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
     const uint64_t n_work = bvh ? static_cast<uint64_t>(n_paths) * n_chunks : static_cast<uint64_t>(n_paths) * n;
     HIP_TRY(hipMemsetAsync(h->d_splat_count, 0, sizeof(unsigned int), h->stream));
     HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
-    RenderArgs a{};
-    a.scene = h->scene; a.ray_count = h->d_rays; a.next_item = h->d_next;
-    a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = dev_capacity; a.hashed_seed = h->hashed_seed_lt;
+    RenderArgs a = MakeRenderArgs(h, h->hashed_seed_lt, n_paths, first_sample + done, n);
     a.SetBand(0u, 0u, 0u);                                    // light paths have no band; every divider of the launch is a valid record all the same
-    a.n_pixels = n_paths; a.SetSamples(first_sample + done, n); a.path_offset = path_begin;
-    a.n_chunks = n_chunks; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
+    a.ray_count = h->d_rays; a.next_item = h->d_next;
+    a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = dev_capacity;
+    a.path_offset = path_begin; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
     const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
     { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
     WithHitEngine(h->hit_engine, [&](auto engine) -> int {
@@ -915,15 +911,16 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   *n_out = total > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(total);
   if (total > capacity) return Fail(AMBER_ENOMEM, "splat buffer too small: " + std::to_string(total) + " splats produced");
   return AMBER_OK;
-}
+}); }
 
 int amber_hip_lt_trace(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, AmberSplat* out, uint32_t capacity,
                        uint32_t* n_out, uint64_t* ray_count) {
-  if (!h) return Fail(AMBER_EINVAL, "null argument");
-  return amber_hip_lt_trace_range(h, first_sample, n_samples, 0u, h->scene.sensor.w * h->scene.sensor.h, out, capacity, n_out, ray_count);
+  return Guarded("amber_hip_lt_trace", [&]() -> int {
+    return h ? amber_hip_lt_trace_range(h, first_sample, n_samples, 0u, h->scene.sensor.w * h->scene.sensor.h, out, capacity, n_out, ray_count) : Fail(AMBER_EINVAL, "null argument");
+  });
 }
 
-int amber_hip_pt_clear(amber_hip_pt* h) {
+int amber_hip_pt_clear(amber_hip_pt* h) { return Guarded("amber_hip_pt_clear", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
   { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
@@ -934,17 +931,17 @@ int amber_hip_pt_clear(amber_hip_pt* h) {
   //  this call have either been read by kernel_time() or are dropped here)
   h->events_used = 0; h->timed_launches = 0; h->timed_ms = 0;
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_pt_sync(amber_hip_pt* h) {
+int amber_hip_pt_sync(amber_hip_pt* h) { return Guarded("amber_hip_pt_sync", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
   { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
   HIP_TRY(hipStreamSynchronize(h->stream));
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_pt_download(amber_hip_pt* h, float* rgb_sum, uint64_t* ray_count) {
+int amber_hip_pt_download(amber_hip_pt* h, float* rgb_sum, uint64_t* ray_count) { return Guarded("amber_hip_pt_download", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
   { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
@@ -955,80 +952,70 @@ int amber_hip_pt_download(amber_hip_pt* h, float* rgb_sum, uint64_t* ray_count) 
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (ray_count) *ray_count = r;
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_pt_device_framebuffer(amber_hip_pt* h, void** dptr, uint64_t* n_floats) {
+int amber_hip_pt_device_framebuffer(amber_hip_pt* h, void** dptr, uint64_t* n_floats) { return Guarded("amber_hip_pt_device_framebuffer", [&]() -> int {
   if (!h || !dptr) return Fail(AMBER_EINVAL, "null argument");
   *dptr = h->d_fb;
   if (n_floats) *n_floats = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w * 3;
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_pt_stream(amber_hip_pt* h, void** stream) {
+int amber_hip_pt_stream(amber_hip_pt* h, void** stream) { return Guarded("amber_hip_pt_stream", [&]() -> int {
   if (!h || !stream) return Fail(AMBER_EINVAL, "null argument");
   *stream = h->stream;
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_pt_local_rows(amber_hip_pt* h, uint32_t* n_rows) {
+int amber_hip_pt_local_rows(amber_hip_pt* h, uint32_t* n_rows) { return Guarded("amber_hip_pt_local_rows", [&]() -> int {
   if (!h || !n_rows) return Fail(AMBER_EINVAL, "null argument");
   *n_rows = h->local_rows;
   return AMBER_OK;
-}
+}); }
 
 int amber_hip_pt_update_objects(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlatObject* objects, uint32_t mode, AmberUpdateInfo* info) {
-  if (!h) return Fail(AMBER_EINVAL, "null handle");
-  try {
-    return UpdateObjects(h, first, count, objects, mode, info);
-  } catch (const std::bad_alloc&) {
-    return Fail(AMBER_ENOMEM, "amber_hip_pt_update_objects: out of host memory");
-  }
+  return Guarded("amber_hip_pt_update_objects", [&]() -> int { return h ? UpdateObjects(h, first, count, objects, mode, info) : Fail(AMBER_EINVAL, "null handle"); });
 }
 
 int amber_hip_pt_update_lens(amber_hip_pt* h, const AmberFlatThinLens* lens, const AmberFlatObject* blades, uint32_t mode, AmberUpdateInfo* info) {
-  if (!h) return Fail(AMBER_EINVAL, "null handle");
-  try {
-    return UpdateLens(h, lens, blades, mode, info);
-  } catch (const std::bad_alloc&) {
-    return Fail(AMBER_ENOMEM, "amber_hip_pt_update_lens: out of host memory");
-  }
+  return Guarded("amber_hip_pt_update_lens", [&]() -> int { return h ? UpdateLens(h, lens, blades, mode, info) : Fail(AMBER_EINVAL, "null handle"); });
 }
 
 int amber_hip_pt_cast_rays(amber_hip_pt* h, uint64_t n, const AmberRay* rays, AmberRayHit* hits, uint32_t flags) {
-  return RayQuery(h, n, rays, hits, flags, false, "amber_hip_pt_cast_rays");
+  return Guarded("amber_hip_pt_cast_rays", [&] { return RayQuery(h, n, rays, hits, flags, false, "amber_hip_pt_cast_rays"); });
 }
 
 int amber_hip_pt_occluded(amber_hip_pt* h, uint64_t n, const AmberRay* rays, uint8_t* occluded, uint32_t flags) {
-  return RayQuery(h, n, rays, occluded, flags, true, "amber_hip_pt_occluded");
+  return Guarded("amber_hip_pt_occluded", [&] { return RayQuery(h, n, rays, occluded, flags, true, "amber_hip_pt_occluded"); });
 }
 
 int amber_hip_pt_resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
-  return Resolve(h, n_samples, format, out, out_bytes, flags);
+  return Guarded("amber_hip_pt_resolve", [&] { return Resolve(h, n_samples, format, out, out_bytes, flags); });
 }
 
 int amber_hip_pt_aov_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
-  return AovGuarded([&] { return AovPass(h, first_sample, n_samples); });
+  return Guarded("amber_hip_pt_aov_pass", [&] { return AovPass(h, first_sample, n_samples); });
 }
 
 int amber_hip_pt_aov_clear(amber_hip_pt* h) {
-  return AovGuarded([&] { return AovClear(h); });
+  return Guarded("amber_hip_pt_aov_clear", [&] { return AovClear(h); });
 }
 
 int amber_hip_pt_aov_download(amber_hip_pt* h, AmberAovPixel* out) {
-  return AovGuarded([&] { return AovDownload(h, out); });
+  return Guarded("amber_hip_pt_aov_download", [&] { return AovDownload(h, out); });
 }
 
 int amber_hip_pt_device_aov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
-  return AovGuarded([&] { return DeviceAov(h, dptr, n_pixels); });
+  return Guarded("amber_hip_pt_device_aov", [&] { return DeviceAov(h, dptr, n_pixels); });
 }
 
-int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) {
+int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) { return Guarded("amber_hip_pt_build_info", [&]() -> int {
   if (!h || !out) return Fail(AMBER_EINVAL, "null argument");
   *out = h->build;
   return AMBER_OK;
-}
+}); }
 
-int amber_hip_pt_kernel_time(amber_hip_pt* h, uint32_t* n_launches, double* total_ms) {
+int amber_hip_pt_kernel_time(amber_hip_pt* h, uint32_t* n_launches, double* total_ms) { return Guarded("amber_hip_pt_kernel_time", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
   { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
@@ -1042,7 +1029,7 @@ int amber_hip_pt_kernel_time(amber_hip_pt* h, uint32_t* n_launches, double* tota
   if (n_launches) *n_launches = h->timed_launches + static_cast<uint32_t>(h->events_used);
   if (total_ms) *total_ms = tot;
   return AMBER_OK;
-}
+}); }
 
 #ifdef AMBER_STAMPS
 // diagnostic build only: per wave of the last pt_megakernel launch, wall-clock ticks (100 MHz) at start, after the first claim,

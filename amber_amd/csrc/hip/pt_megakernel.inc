@@ -53,7 +53,7 @@ template <int kEngine, bool kLight = false, bool kSig = false>
 __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKERNEL_WAVES_PER_SIMD) pt_megakernel(const RenderArgs a) {
   const DevScene& sc = a.scene;
   const uint32_t lane = threadIdx.x & 63u;
-  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
+  constexpr bool kTwoPhase = EngineTraits<kEngine>::kTwoPhase;
   constexpr int kChunks = PoolLayout<kLight>::kChunks;
   constexpr bool kCold = !kLight && kEngine != ENGINE_BVH;    // cold kernel arguments are read next to their use (AMBER_ARG below)
   // a cold argument, read next to its use (pt_args.h).  Two families keep the plain form: the light tracer (its bounces read n_samples and
@@ -61,13 +61,11 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
   // ENGINE_BVH 118.6 -> 120.0 ms, the room mesh 52.7 -> 53.6 ms with cold reads, EXPERIMENTS.md).
 #define AMBER_ARG(cold, field) (kCold ? AMBER_COLD(cold, field) : a.field)
 #define AMBER_COLD_OPEN() (kCold ? ColdArgs::Open() : ColdArgs{nullptr})
-  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
   __shared__ uint4 lds_pool[4][64 * kChunks];                 // [wave][slot * kChunks + chunk]
   // engine BVH on a SHALLOW tree (mid-size scenes, RenderPassPaths): the closest hit is one uninterrupted per-lane traversal (ClosestHitBvh),
   // its stack [level][thread] in LDS -- a few dozen node visits differ little between the lanes of a wave, so nothing has to be resumable,
   // and the path-granular scheduling above (coherent primary rounds, no lane waits for a shading batch) is what a small scene gains most from
-  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? AMBER_PATH_BVH_STACK * 256 : 1];
-  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  const EngineLds lds = StageEngineLds<kEngine, AMBER_PATH_BVH_STACK>(sc);
   const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform, and the compiler knows it: what derives from it stays in SGPRs
   uint4* pool = lds_pool[wave_in_block];
 
@@ -221,15 +219,15 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
       if (kLight) {
         const uint32_t plocal = Quotient(a.div_samples, q);
         const SplatSink sink{a.splats, a.splat_count, a.splat_capacity, a.path_offset + plocal, a.first_sample + (q - plocal * a.n_samples), sc.sensor.size_f};
-        alive = PathStep<false, kEngine, true>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
+        alive = PathStep<false, kEngine, true>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
       } else if (kSig) {
         Bounce b;
-        alive = PathStep<true, kEngine>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
+        alive = PathStep<true, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
         sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
         if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
         if (!alive) AMBER_ARG(AMBER_COLD_OPEN(), sig)[q] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
       } else {
-        alive = PathStep<false, kEngine>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
+        alive = PathStep<false, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
       }
       if (!kLight) {
         const bool nz = (__float_as_uint(meas.x) | __float_as_uint(meas.y) | __float_as_uint(meas.z)) != 0u;   // anything but +0 (RGB)

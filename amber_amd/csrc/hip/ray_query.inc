@@ -105,13 +105,10 @@ __global__ void __launch_bounds__(256, AMBER_QUERY_WAVES) bvh_query_kernel(const
 
 template <int kEngine, bool kAnyHit>
 __global__ void __launch_bounds__(256) ray_query_kernel(const DevScene sc, uint64_t n, const float4* __restrict__ rays, float4* __restrict__ hits, uint8_t* __restrict__ occluded) {
-  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE || kEngine == ENGINE_TWO_PHASE_N;
-  __shared__ DevObject lds_objects[kEngine == ENGINE_TWO_PHASE_N ? AMBER_MAX_GROUP_OBJECTS : (kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1)];
-  __shared__ int32_t lds_stack[1];
-  if (kTwoPhase) StageObjects<kEngine == ENGINE_TWO_PHASE_N>(sc, lds_objects);
+  const EngineLds lds = StageEngineLds<kEngine, 1>(sc);          // (never engine BVH: no traversal stack)
   for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * 256u; base < n; base += static_cast<uint64_t>(gridDim.x) * 256u) {   // uniform over the workgroup
     const uint64_t i = base + threadIdx.x;
-    const uint64_t k = i < n ? i : n - 1;      // keep the object loop wave-uniform for every lane
+    const uint64_t k = ClampToLastItem(i, n);
     const float4 ro = rays[2u * k], rd = rays[2u * k + 1u];
     const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rd.x, rd.y, rd.z);
     const float t_max = ro.w;
@@ -119,16 +116,14 @@ __global__ void __launch_bounds__(256) ray_query_kernel(const DevScene sc, uint6
 #ifdef AMBER_STAMPS
     StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-    ClosestHit<kEngine>(sc, lds_objects, lds_stack, o, d, -1, h AMBER_STAMP_ARG);
+    ClosestHit<kEngine>(sc, lds.objects, lds.stack, o, d, -1, h AMBER_STAMP_ARG);
     if (i >= n) continue;
-    // every exact test forms dot products over all components of o and d: a NaN component makes every distance NaN, which no hit accepts
-    const bool nan_ray = !(o.x == o.x && o.y == o.y && o.z == o.z && d.x == d.x && d.y == d.y && d.z == d.z);
-    const bool found = h.idx >= 0 && !nan_ray && h.t <= t_max;
+    const bool found = h.idx >= 0 && !IsNanRay(o, d) && h.t <= t_max;
     if constexpr (kAnyHit) {
       occluded[i] = found ? 1 : 0;
     } else if (found) {
       V3 pos, nrm; uint32_t mat;
-      ResolveHit<kEngine == ENGINE_TWO_PHASE_N ? 0x7fu : 0xffu>(kTwoPhase ? lds_objects : (kEngine == ENGINE_REF_BVH ? sc.bvh_objects : sc.objects), h, o, d, pos, nrm, mat);
+      ResolveHit<kEngine>(sc, lds.objects, h, o, d, pos, nrm, mat);
       StoreRayHit(hits, i, h.t, h.idx, pos, nrm);
     } else {
       StoreRayMiss(hits, i);
@@ -140,42 +135,50 @@ static_assert(sizeof(AmberRay) == 32 && sizeof(AmberRayHit) == 32, "a ray and a 
 constexpr uint64_t kQueryMaxRays = 1ull << 31;
 constexpr uint64_t kQueryStageRays = 1ull << 20;          // AMBER_RAYS_HOST: rays per trip through the staging buffers (32 MiB + 32 MiB)
 
+// Engine BVH's query grid at its largest: AMBER_QUERY_WAVES workgroups per CU (the launch bounds of bvh_query_kernel and aov_kernel<ENGINE_BVH>).
+uint32_t QueryGridCap(const amber_hip_pt* h) { return static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_QUERY_WAVES); }
+
+// One launch of a kernel with a thread per item (ray, band pixel), instantiated for the handle's engine by launch(engine, n_blocks).  The grid is no larger than
+// the render kernels' (REFERENCE_BVH's traversal stack has one column per thread of THAT grid); engine BVH, whose per-item kernels keep their stacks in LDS, takes its query grid.
+template <typename F>
+int LaunchPerItem(amber_hip_pt* h, uint64_t n_items, F&& launch) {
+  const uint32_t n_blocks = h->hit_engine == AMBER_ENGINE_BVH ? BlocksFor(n_items, QueryGridCap(h)) : PersistentBlocks(h, n_items);
+  { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
+  WithHitEngine(h->hit_engine, [&](auto engine) -> int { launch(engine, n_blocks); return AMBER_OK; });
+  HIP_TRY(hipGetLastError());
+  return AMBER_OK;
+}
+
 // One launch over n rays in device memory.  Engine BVH's scratch (the global levels of the hybrid stack for the largest grid, the work counter)
 // is allocated by the first query and kept.
 int LaunchRayQuery(amber_hip_pt* h, uint64_t n, const float4* d_rays, void* d_out, bool any_hit) {
   float4* hits = any_hit ? nullptr : static_cast<float4*>(d_out);
   uint8_t* occluded = any_hit ? static_cast<uint8_t*>(d_out) : nullptr;
-  const uint64_t by_work = (n + 255u) / 256u;
   if (h->hit_engine == AMBER_ENGINE_BVH) {
-    const uint32_t max_blocks = static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_QUERY_WAVES);
+    const uint32_t max_blocks = QueryGridCap(h);
     if (!h->d_query_stack) {
       const hipError_t e = h->d_query_stack.alloc(static_cast<size_t>(max_blocks) * 256u * (AMBER_BVH_STACK - AMBER_QUERY_LDS_LEVELS));
       if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string("hipMalloc(query traversal stacks): ") + hipGetErrorString(e));
       h->query_stack_threads = static_cast<uint64_t>(max_blocks) * 256u;
     }
     if (!h->d_query_next) HIP_TRY(h->d_query_next.alloc(1));
-    const uint32_t n_blocks = by_work < max_blocks ? static_cast<uint32_t>(by_work) : max_blocks;
+    const uint32_t n_blocks = BlocksFor(n, max_blocks);
     if (static_cast<uint64_t>(n_blocks) * 256u > h->query_stack_threads)
       return Fail(AMBER_EINVAL, "ray query: a grid of " + std::to_string(n_blocks) + " workgroups outgrows the traversal stack (" + std::to_string(h->query_stack_threads) + " threads)");
     HIP_TRY(hipMemsetAsync(h->d_query_next, 0, sizeof(unsigned int), h->stream));
     const uint32_t stride = static_cast<uint32_t>(h->query_stack_threads);
     if (any_hit) hipLaunchKernelGGL(bvh_query_kernel<true>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->d_query_next.p, h->d_query_stack.p, stride);
     else hipLaunchKernelGGL(bvh_query_kernel<false>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->d_query_next.p, h->d_query_stack.p, stride);
-  } else {
-    const uint32_t max_blocks = PersistentBlocks(h);
-    const uint32_t n_blocks = by_work < max_blocks ? static_cast<uint32_t>(by_work) : max_blocks;
-    { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
-    WithHitEngine(h->hit_engine, [&](auto engine) -> int {
-      constexpr int kEngine = decltype(engine)::value;
-      if constexpr (kEngine != ENGINE_BVH) {
-        if (any_hit) hipLaunchKernelGGL((ray_query_kernel<kEngine, true>), dim3(n_blocks), dim3(256), 0, h->stream, h->scene, n, d_rays, hits, occluded);
-        else hipLaunchKernelGGL((ray_query_kernel<kEngine, false>), dim3(n_blocks), dim3(256), 0, h->stream, h->scene, n, d_rays, hits, occluded);
-      }
-      return AMBER_OK;
-    });
+    HIP_TRY(hipGetLastError());
+    return AMBER_OK;
   }
-  HIP_TRY(hipGetLastError());
-  return AMBER_OK;
+  return LaunchPerItem(h, n, [&](auto engine, uint32_t n_blocks) {
+    constexpr int kEngine = decltype(engine)::value;
+    if constexpr (kEngine != ENGINE_BVH) {                    // (engine BVH has the kernel above: no ray_query_kernel<ENGINE_BVH, ..>)
+      if (any_hit) hipLaunchKernelGGL((ray_query_kernel<kEngine, true>), dim3(n_blocks), dim3(256), 0, h->stream, h->scene, n, d_rays, hits, occluded);
+      else hipLaunchKernelGGL((ray_query_kernel<kEngine, false>), dim3(n_blocks), dim3(256), 0, h->stream, h->scene, n, d_rays, hits, occluded);
+    }
+  });
 }
 
 int RayQuery(amber_hip_pt* h, uint64_t n, const AmberRay* rays, void* out, uint32_t flags, bool any_hit, const char* name) {

@@ -79,10 +79,7 @@ __global__ void __launch_bounds__(256) wf_generate_kernel(const WfArgs a) {
 template <int kEngine>
 __global__ void __launch_bounds__(256) wf_bounce_kernel(const WfArgs a) {
   const DevScene& sc = a.scene;
-  constexpr bool kTwoPhase = kEngine == ENGINE_TWO_PHASE;
-  __shared__ DevObject lds_objects[kTwoPhase ? AMBER_MAX_LDS_OBJECTS : 1];
-  __shared__ int32_t lds_stack[kEngine == ENGINE_BVH ? AMBER_BVH_STACK * 256 : 1];
-  if (kTwoPhase) StageObjects(sc, lds_objects);
+  const EngineLds lds = StageEngineLds<kEngine, AMBER_BVH_STACK>(sc);
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;          // global wave id
   const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;                       // multiple of AMBER_WF_SHARDS
@@ -108,7 +105,7 @@ __global__ void __launch_bounds__(256) wf_bounce_kernel(const WfArgs a) {
 #ifdef AMBER_STAMPS
       StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-      alive = PathStep<false, kEngine>(sc, lds_objects, lds_stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG);
+      alive = PathStep<false, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG);
       ++rays;
       // measurement += weight * Le : non-zero only when a light was hit; x + (+-0) == x, so skipping zeros is exact
       if (__float_as_uint(meas.x) << 1 || __float_as_uint(meas.y) << 1 || __float_as_uint(meas.z) << 1) {
