@@ -51,6 +51,7 @@ from .api import (  # noqa: F401
     MATH_GLIBC,
     MATH_PORTABLE,
     kat_math,
+    kat_division,
     math_mode,
     library_path,
     load_library,

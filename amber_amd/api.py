@@ -130,7 +130,7 @@ ABI_SYMBOLS = [
 # what include/amber_hip_lab.h declares: libamber_hip_lab.so (the same sources with -DAMBER_LAB) exports these as well
 LAB_SYMBOLS = [
     "amber_hip_kat_cast", "amber_hip_kat_sample", "amber_hip_kat_eye", "amber_hip_kat_trace", "amber_hip_kat_math", "amber_hip_kat_signatures", "amber_hip_pt_signatures",
-    "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump",
+    "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump", "amber_hip_kat_division",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -208,6 +208,8 @@ def load_library() -> C.CDLL:
         lib.amber_hip_kat_traversal_rate.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, vp, C.POINTER(C.c_double), vp]
         lib.amber_hip_pt_signatures.argtypes = [vp, u32, u32, vp]
         lib.amber_hip_kat_bvh_dump.argtypes = [vp, vp, u32, vp, u32, C.POINTER(BvhDumpInfo)]
+        if hasattr(lib, "amber_hip_kat_division"):     # absent only in older builds loaded by tools/ab_lib.py
+            lib.amber_hip_kat_division.argtypes = [i32, i32, u32, vp, vp]
     lib.amber_host_cornell_box.restype = vp
     lib.amber_host_cornell_box.argtypes = [C.c_float, C.c_float, u32]
     lib.amber_host_scene_import.restype = vp
@@ -738,6 +740,16 @@ def kat_math(mode: int, x, device: int = 0) -> np.ndarray:
     out = np.empty((n,) if mode == 1 else (n, 2), np.float32)
     _check(load_library().amber_hip_kat_math(device, mode, n, x.ctypes.data, out.ctypes.data))
     return out.view(np.float64).reshape(n) if mode >= 2 else out
+
+
+def kat_division(mode: int, x, device: int = 0) -> np.ndarray:
+    """The engine's shared-denominator division on device, x = (n, 4) groups {a, b, c, d} -> (n, 3): mode 0 a/d, b/d, c/d through one
+    reciprocal (shared_div.h, with its fallback); mode 1 the plain operators; mode 2 / 3 Normalize({a, b, c}) in the shared / the plain form."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 4)
+    n = len(x)
+    out = np.empty((n, 3), np.float32)
+    _check(load_library().amber_hip_kat_division(device, mode, n, x.ctypes.data, out.ctypes.data))
+    return out
 
 
 MATH_PORTABLE, MATH_GLIBC = 1, 2

@@ -131,7 +131,7 @@ __device__ __forceinline__ void ClosestHit(const DevScene& sc, const DevObject* 
 }
 
 // position / normal of the winning hit, evaluated exactly as the reference's Intersect() does
-template <uint32_t kKindMask = 0xffu>
+template <uint32_t kKindMask = 0xffu, bool kSharedDiv = false>
 __device__ __forceinline__ void ResolveHit(const DevObject* objects, const HitRec& h, V3 o, V3 d, V3& pos, V3& normal, uint32_t& material) {
   const DevObject* ob = objects + h.slot;
   const uint32_t kind = ob->kind & kKindMask;         // the LDS image of the two-phase engine tags kind with index << 8; the grouped engine's also with bit 7 (a filtered triangle)
@@ -142,14 +142,14 @@ __device__ __forceinline__ void ResolveHit(const DevObject* objects, const HitRe
     normal = ld3(ob->n);
   } else if (kind == PRIM_SPHERE) {
     pos = o + h.t * d;                                   // primitive_sphere.cc:91-95
-    normal = Normalize(o + h.t * d - A);
+    normal = Normalize<kSharedDiv>(o + h.t * d - A);
   } else if (kind == PRIM_DISK) {
     pos = o + h.t * d; normal = ld3(ob->e1);
   } else {
     const V3 N = ld3(ob->e1);
     const float hh = Dot(h.t * d - (A - o), N);
     pos = o + h.t * d;
-    normal = Normalize(o + h.t * d - A - hh * N);
+    normal = Normalize<kSharedDiv>(o + h.t * d - A - hh * N);
   }
 }
 
@@ -177,9 +177,9 @@ template <int kEngine>
 __device__ __forceinline__ const DevObject* HitObjects(const DevScene& sc, const DevObject* lds_objects) {
   return EngineTraits<kEngine>::kTwoPhase ? lds_objects : ((kEngine == ENGINE_BVH || kEngine == ENGINE_REF_BVH) ? sc.bvh_objects : sc.objects);
 }
-template <int kEngine>
+template <int kEngine, bool kSharedDiv = false>
 __device__ __forceinline__ void ResolveHit(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3 o, V3 d, V3& pos, V3& normal, uint32_t& material) {
-  ResolveHit<EngineTraits<kEngine>::kKindMask>(HitObjects<kEngine>(sc, lds_objects), h, o, d, pos, normal, material);
+  ResolveHit<EngineTraits<kEngine>::kKindMask, kSharedDiv>(HitObjects<kEngine>(sc, lds_objects), h, o, d, pos, normal, material);
 }
 
 // The LDS of a kernel that casts through ClosestHit<kEngine>, declared and staged (the two-phase image; ends with a barrier: every thread calls it, once, before anything

@@ -28,17 +28,29 @@ __device__ __forceinline__ float Dot(V3 u, V3 v) { return u.x * v.x + u.y * v.y 
 __device__ __forceinline__ float SquaredLength(V3 v) { return Dot(v, v); }
 // __builtin_sqrtf lowers to the correctly rounded sequence (v_sqrt_f32 + one-ulp fix-up); __fsqrt_rn does NOT on ROCm 7.2
 __device__ __forceinline__ float Sqrt(float x) { return __builtin_sqrtf(x); }
-__device__ __forceinline__ V3 Normalize(V3 v) { const float l = Sqrt(SquaredLength(v)); return V3{v.x / l, v.y / l, v.z / l}; }
+// kSharedDiv: the three quotients by l through ONE reciprocal (shared_div.h: the same IEEE quotients; the wave falls back to the plain form when
+// a lane is out of range).  The kernels that measured a gain ask for it (pt_megakernel.inc, AMBER_SHARED_DIV_NORMALIZE); everything else, the
+// lab's one-thread-per-path restatement included, keeps the plain divisions.
+#ifndef AMBER_SHARED_DIV_NORMALIZE
+#define AMBER_SHARED_DIV_NORMALIZE 5   /* 1: the lobe's basis (SampleLight), 2: sphere and cylinder normals (ResolveHit; off: it did not measure), 4: the eye ray */
+#endif
+template <bool kSharedDiv = false>
+__device__ __forceinline__ V3 Normalize(V3 v) {
+  const float l = Sqrt(SquaredLength(v));
+  if (kSharedDiv) { V3 n; shared_div::DivByLength(v.x, v.y, v.z, l, n.x, n.y, n.z); return n; }
+  return V3{v.x / l, v.y / l, v.z / l};
+}
 __device__ __forceinline__ V3 Cross(V3 u, V3 v) {
   return V3{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
 }
 // std::max({x,y,z}) (vector3.h:276-281): first element wins unless a later one is strictly greater
 __device__ __forceinline__ float Max3(V3 v) { float m = v.x; if (m < v.y) m = v.y; if (m < v.z) m = v.z; return m; }
 __device__ __forceinline__ float Abs(float x) { return __builtin_fabsf(x); }
+template <bool kSharedDiv = false>
 __device__ __forceinline__ void OrthonormalBasis(V3 w, V3& u, V3& v) {      // vector3.h:330-342
   const bool xs = Abs(w.x) < Abs(w.y);
-  u = Normalize(Cross(w, xs ? v3(1.f, 0.f, 0.f) : v3(0.f, 1.f, 0.f)));
-  v = Normalize(Cross(w, u));
+  u = Normalize<kSharedDiv>(Cross(w, xs ? v3(1.f, 0.f, 0.f) : v3(0.f, 1.f, 0.f)));
+  v = Normalize<kSharedDiv>(Cross(w, u));
 }
 __device__ __forceinline__ V3 MatMul(const float* e, V3 v) {               // matrix3.h:101-109
   return v3(e[0] * v.x + e[1] * v.y + e[2] * v.z, e[3] * v.x + e[4] * v.y + e[5] * v.z, e[6] * v.x + e[7] * v.y + e[8] * v.z);

@@ -38,6 +38,7 @@ __device__ __forceinline__ V3 Radiance(const DevMaterial& m, V3 normal, V3 dir_o
 }
 
 // Scene::SampleLight -> Material::SampleLight (+ rho forwarders, material_basic.h:233-245, 327-338)
+template <bool kSharedDiv = false>
 __device__ __forceinline__ void SampleLight(const DevMaterial& m, V3 normal, V3 dir_out, uint64_t& rng, V3& dir_in, V3& weight) {
   const V3 rho = ld3(m.rho);
   const uint32_t kind = m.kind;
@@ -52,7 +53,7 @@ __device__ __forceinline__ void SampleLight(const DevMaterial& m, V3 normal, V3 
     const bool phong = kind == MAT_PHONG;
     const float signed_cos_o = AMBER_COS_O();
     const V3 w = phong ? AMBER_MIRROR(signed_cos_o) : (signed_cos_o > 0.0f ? normal : -normal);
-    V3 u, v; OrthonormalBasis(w, u, v);                  // CosinePower rebuilds the same basis on every attempt
+    V3 u, v; OrthonormalBasis<kSharedDiv>(w, u, v);      // CosinePower rebuilds the same basis on every attempt
     // The reference's Phong loop re-samples forever when no direction of the lobe lies on dir_out's side (possible with a
     // normal that is not of unit length); a kernel must terminate, so attempt AMBER_PHONG_MAX_TRIES is accepted as it
     // is (the oracle does the same; with a proper normal at least half of the lobe is acceptable: probability 2^-1024).
@@ -222,7 +223,7 @@ __device__ __forceinline__ bool LensResponse(const DevScene& sc, V3 position, V3
 // near_edge (optional): the aperture sample lies within DevLens.edge_tol (barycentric) of its blade's boundary -- only then can the exact
 // test of ANOTHER blade accept the ray's own origin (pt_megakernel's primary rounds: which blades are candidates).
 struct EyeRayScene { const DevLens* lens; const DevBlade* blades; DevSensor sensor; };
-template <typename Scene>
+template <bool kSharedDiv = false, typename Scene>
 __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uint32_t py, uint64_t& rng,
                                                V3& origin, V3& dir, float& weight, int& origin_slot, bool* near_edge = nullptr) {
   const DevLens L = LoadLens(sc.lens);
@@ -232,7 +233,7 @@ __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uin
     const float uvx = (static_cast<float>(px) + jx) / sc.sensor.wf;
     const float uvy = (static_cast<float>(py) + jy) / sc.sensor.hf;
     const V3 sensor_point = v3((uvx - 0.5f) * sc.sensor.sw, (uvy - 0.5f) * sc.sensor.sh, L.sensor_distance);
-    const V3 ray_dir = Normalize(MatMul(L.global_, -sensor_point));
+    const V3 ray_dir = Normalize<kSharedDiv>(MatMul(L.global_, -sensor_point));
     // PDFDirection lens_pinhole.cc:93-106 (binary32 throughout; no sensor.Size() factor, unlike the thin lens)
     const V3 dl = MatMul(L.local_, ray_dir);
     const V3 point = (L.sensor_distance / dl.z) * dl;
@@ -259,9 +260,9 @@ __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uin
   const float uvx = (static_cast<float>(px) + jx) / sc.sensor.wf;
   const float uvy = (static_cast<float>(py) + jy) / sc.sensor.hf;
   const V3 sensor_point = v3((uvx - 0.5f) * sc.sensor.sw, (uvy - 0.5f) * sc.sensor.sh, L.sensor_distance);
-  const V3 direction = Normalize(L.neg_fd_over_sd * sensor_point - aperture_point);
-  const double factor = Pow4(Normalize(sensor_point - aperture_point).z / direction.z);
-  const V3 ray_dir = Normalize(MatMul(L.global_, direction));
+  const V3 direction = Normalize<kSharedDiv>(L.neg_fd_over_sd * sensor_point - aperture_point);
+  const double factor = Pow4(Normalize(sensor_point - aperture_point).z / direction.z);      // one component: the plain form divides once
+  const V3 ray_dir = Normalize<kSharedDiv>(MatMul(L.global_, direction));
   const V3 dloc = MatMul(L.local_, ray_dir);
   const float pdf_dir = static_cast<float>(static_cast<double>(L.size_over_area) * L.sd2 / Pow4(dloc.z));
   origin = ap_origin; dir = ray_dir;
@@ -280,21 +281,21 @@ struct Bounce { int object; float t; V3 pos; V3 weight_before; };
 // emitted radiance, and the material is sampled with SampleImportance.
 struct SplatSink { DevSplat* records; unsigned int* count; uint32_t capacity; uint32_t path, sample; float size_f; };
 
-template <bool kTrace, int kEngine, bool kLight>
+template <bool kTrace, int kEngine, bool kLight, bool kDivBasis = false, bool kDivHit = false>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
                                           uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink);
 
-template <bool kTrace, int kEngine, bool kLight = false>
+template <bool kTrace, int kEngine, bool kLight = false, bool kDivBasis = false, bool kDivHit = false>
 __device__ __forceinline__ bool PathStep(const DevScene& sc, const DevObject* lds_objects, int32_t* lds_stack, V3& o, V3& d, V3& weight, V3& measurement,
                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink = nullptr,
                                          const bool use_premask = false, const uint32_t premask = 0u, const int bvh_stack_cap = AMBER_BVH_STACK) {
   HitRec h;
   ClosestHit<kEngine>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG, use_premask, premask, bvh_stack_cap);
-  return PathShade<kTrace, kEngine, kLight>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink);
+  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink);
 }
 
 // Everything of a bounce after the closest-hit query (algorithm_pt.cc:140-157): h is the result of Scene::Cast.
-template <bool kTrace, int kEngine, bool kLight>
+template <bool kTrace, int kEngine, bool kLight, bool kDivBasis, bool kDivHit>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
                                           uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink) {
   casts++;
@@ -303,7 +304,7 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
     return false;
   }
   V3 pos, normal; uint32_t mat;
-  ResolveHit<kEngine>(sc, lds_objects, h, o, d, pos, normal, mat);
+  ResolveHit<kEngine, kDivHit>(sc, lds_objects, h, o, d, pos, normal, mat);
   const DevMaterial m = sc.materials[mat];
   const V3 dir_out = -d;
   if (kTrace) { trace->object = h.idx; trace->t = h.t; trace->pos = pos; trace->weight_before = weight; }
@@ -326,7 +327,7 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
   } else {
     measurement = measurement + weight * Radiance(m, normal, dir_out);      // algorithm_pt.cc:144
     AMBER_STAMP(4);
-    SampleLight(m, normal, dir_out, rng, dir_in, sw);                        // :145-146
+    SampleLight<kDivBasis>(m, normal, dir_out, rng, dir_in, sw);             // :145-146
   }
   AMBER_STAMP(5);
   float p_rr = 0.9375f;                                                      // std::min<real_type>(kRussianRoulette, Max(w)) :148-149

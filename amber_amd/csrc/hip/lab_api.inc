@@ -320,5 +320,21 @@ int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* 
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_division(int device, int mode, uint32_t n, const float* x, float* out) { return Guarded("amber_hip_kat_division", [&]() -> int {
+  if (!x || !out || mode < 0 || mode > 3) return Fail(AMBER_EINVAL, "bad argument");
+  if (n == 0) return AMBER_OK;
+  if (n > 0x3fffffffu) return Fail(AMBER_EINVAL, "too many groups for one call");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return Fail(AMBER_ENODEVICE, "no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  DevBuf<float> d_x, d_o;
+  HIP_TRY(d_x.alloc(4ull * n)); HIP_TRY(d_o.alloc(3ull * n));
+  HIP_TRY(hipMemcpy(d_x.p, x, 16ull * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kat_division_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, mode, n, d_x.p, d_o.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_o.p, 12ull * n, hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
 
 }  // extern "C"

@@ -132,3 +132,19 @@ __global__ void kat_math_kernel(int mode, uint32_t n, const float* x, float* out
   }
 }
 
+// Groups {a, b, c, d} of four floats.  0: a / d, b / d, c / d through shared_div.h's Div3 (one reciprocal; the wave falls back when a lane is
+// out of range); 1: the plain-operator expressions; 2 / 3: Normalize({a, b, c}) through the shared and the plain form (d is not read).
+// Whole waves run to the end (the last item stands in for the lanes past n): Div3's guard is a wave vote.
+__global__ void kat_division_kernel(int mode, uint32_t n, const float* x, float* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t k = ClampToLastItem(i, n);
+  const float a = x[4ull * k], b = x[4ull * k + 1], c = x[4ull * k + 2], d = x[4ull * k + 3];
+  V3 q;
+  if (mode == 0) shared_div::Div3(a, b, c, d, q.x, q.y, q.z);
+  else if (mode == 1) q = v3(a / d, b / d, c / d);
+  else if (mode == 2) q = Normalize<true>(v3(a, b, c));
+  else q = Normalize<false>(v3(a, b, c));
+  if (i >= n) return;
+  out[3ull * i] = q.x; out[3ull * i + 1] = q.y; out[3ull * i + 2] = q.z;
+}
+

@@ -16,8 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// The device functions live in seven parts, included here in the order they build on each other (one translation unit: pt_host.hip):
+// The device functions live in eight parts, included here in the order they build on each other (one translation unit: pt_host.hip):
 //   dev_scene.h        diagnostic macros of the stamped builds; the scene layout in HBM (DevObject ... DevScene)
+//   shared_div.h       three quotients by one denominator at one reciprocal (host and device)
 //   dev_math.h         Vector3, the XorShift sampler, glibc's sincosf / powf kernels restated
 //   dev_primitives.h   the reference's primitive tests and hit rule; engine LIST
 //   dev_two_phase.h    engine TWO_PHASE: Phase-A filter, Phase-B exact tests, groups of 32 objects
@@ -25,6 +26,7 @@
 //   dev_closest_hit.h  engine REFERENCE_BVH; ClosestHit<kEngine>; ResolveHit
 //   dev_shading.h      materials, eye ray, light-path start, PathStep / PathShade
 #include "dev_scene.h"
+#include "shared_div.h"
 #include "dev_math.h"
 #include "dev_primitives.h"
 #include "dev_two_phase.h"

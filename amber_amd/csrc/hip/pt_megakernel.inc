@@ -59,6 +59,9 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
   // a cold argument, read next to its use (pt_args.h).  Two families keep the plain form: the light tracer (its bounces read n_samples and
   // first_sample themselves, and with these reads the kernel reserved scratch) and engine BVH's one-shot traversal (measured: Cornell through
   // ENGINE_BVH 118.6 -> 120.0 ms, the room mesh 52.7 -> 53.6 ms with cold reads, EXPERIMENTS.md).
+  // Normalize's three quotients through one reciprocal (shared_div.h): the same family, for the same kind of reason (the light tracers and
+  // <ENGINE_BVH> were not measured with it and keep the plain divisions)
+  constexpr bool kDivBasis = kCold && (AMBER_SHARED_DIV_NORMALIZE & 1), kDivHit = kCold && (AMBER_SHARED_DIV_NORMALIZE & 2), kDivEye = kCold && (AMBER_SHARED_DIV_NORMALIZE & 4);
 #define AMBER_ARG(cold, field) (kCold ? AMBER_COLD(cold, field) : a.field)
 #define AMBER_COLD_OPEN() (kCold ? ColdArgs::Open() : ColdArgs{nullptr})
   __shared__ uint4 lds_pool[4][64 * kChunks];                 // [wave][slot * kChunks + chunk]
@@ -81,15 +84,19 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
   bool carries = false;
   // (its address is formed where it is used, from a thread index the optimiser cannot see through: hoisted out of the
   //  persistent loop, the pointer is the one value the register cap pushes into scratch)
+  // (kCold: the block index goes through an empty asm per use.  blockIdx.x * 256 as a 64-bit pair is loop-invariant, and held across the loop
+  //  it is a scalar register pair that the loop does not have: with the eye ray's shared division the allocator parked it in lanes and
+  //  fetched it back at each of the four uses -- tests/test_headline_kernel_spills.py.  The other two families keep the plain expression.)
+  auto block_index = []() -> size_t { uint32_t b = blockIdx.x; if (kCold) asm volatile("" : "+s"(b)); return b; };
   auto carried_slot = [&]() -> float* {
     const uint32_t t = wave_in_block * 64u + BvhStackHybrid::LaneId();     // = threadIdx.x, from an SGPR and two v_mbcnt
-    return AMBER_ARG(AMBER_COLD_OPEN(), carried) + (static_cast<size_t>(blockIdx.x) * 256u + t) * 3u;
+    return AMBER_ARG(AMBER_COLD_OPEN(), carried) + (block_index() * 256u + t) * 3u;
   };
 #define AMBER_CARRIED() carried_slot()
   // a carried measurement travels with its ray: parked with it (a second block of slots, one per pool slot of the wave) and handed to
   // the lane that pops the ray -- rays change lanes since the primary rounds
   auto carried_parked = [&](uint32_t pool_slot) -> float* {
-    return AMBER_ARG(AMBER_COLD_OPEN(), carried) + (static_cast<size_t>(gridDim.x) * 256u + (static_cast<size_t>(blockIdx.x) * 4u + wave_in_block) * 64u + pool_slot) * 3u;
+    return AMBER_ARG(AMBER_COLD_OPEN(), carried) + (static_cast<size_t>(gridDim.x) * 256u + (block_index() * 4u + wave_in_block) * 64u + pool_slot) * 3u;
   };
   V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f), w = v3(0.f, 0.f, 0.f);
   uint64_t rng = 1;
@@ -188,7 +195,7 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
               rng = XorShiftSeed(AMBER_ARG(cold, hashed_seed), px + py * eye.sensor.w, sample);   // Image index x + y*W (image.h:116-124)
               float ew;
               bool near_edge = false;
-              GenerateEyeRay(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
+              GenerateEyeRay<kDivEye>(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
               w = v3(ew, ew, ew);                             // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
               // (the pointer is read here and once more below, not held across the bookkeeping above: the two scalar registers it would occupy
               //  there are what the dividers need, and the loop has none to spare -- tests/test_headline_kernel_spills.py)
@@ -222,12 +229,12 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
         alive = PathStep<false, kEngine, true>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
       } else if (kSig) {
         Bounce b;
-        alive = PathStep<true, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
+        alive = PathStep<true, kEngine, false, kDivBasis, kDivHit>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
         sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
         if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
         if (!alive) AMBER_ARG(AMBER_COLD_OPEN(), sig)[q] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
       } else {
-        alive = PathStep<false, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
+        alive = PathStep<false, kEngine, false, kDivBasis, kDivHit>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
       }
       if (!kLight) {
         const bool nz = (__float_as_uint(meas.x) | __float_as_uint(meas.y) | __float_as_uint(meas.z)) != 0u;   // anything but +0 (RGB)

@@ -65,6 +65,10 @@ int amber_hip_kat_bvh_dump(amber_hip_pt*, uint32_t* nodes, uint32_t node_capacit
 /* the engine's sin/cos/pow on device: mode 0 = sincos(x[i]) -> out[2i], out[2i+1] ; mode 1 = pow(x[2i], x[2i+1]) -> out[i] ;
  * mode 2 / 3 = x[i]^4 / x[i]^5 in binary64 -> out[2i], out[2i+1] = low, high word of the double */
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out);
+/* the engine's shared-denominator division on device (csrc/hip/shared_div.h): x = n groups {a, b, c, d}, out = n groups of three.
+ * mode 0 = a / d, b / d, c / d through one reciprocal (the wave falls back to mode 1's code when a lane is out of range) ; mode 1 = the plain
+ * operator expressions ; mode 2 / 3 = Normalize({a, b, c}) through the shared and the plain form (d is not read) */
+int amber_hip_kat_division(int device, int mode, uint32_t n, const float* x, float* out);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
