@@ -92,6 +92,12 @@ class AovPixel(C.Structure):
     _fields_ = [("albedo", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("coverage", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """AmberDenoiseParams: levels (1..8) and the four edge-stopping constants of amber_hip_pt_denoise -- 32 bytes."""
+    _fields_ = [("levels", C.c_uint32), ("k_normal", C.c_float), ("k_albedo", C.c_float), ("k_depth", C.c_float), ("k_color", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
 class BvhDumpInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_prims", C.c_uint32), ("root", C.c_int32), ("depth", C.c_uint32),
                 ("gmin", C.c_float * 3), ("step", C.c_float * 3), ("reach", C.c_float * 3)]
@@ -122,7 +128,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
     "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_update_lens",
     "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_resolve", "amber_hip_pt_destroy",
-    "amber_hip_pt_aov_pass", "amber_hip_pt_aov_clear", "amber_hip_pt_aov_download", "amber_hip_pt_device_aov",
+    "amber_hip_pt_aov_pass", "amber_hip_pt_aov_clear", "amber_hip_pt_aov_download", "amber_hip_pt_device_aov", "amber_hip_pt_denoise",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -193,6 +199,8 @@ def load_library() -> C.CDLL:
         lib.amber_hip_pt_aov_clear.argtypes = [vp]
         lib.amber_hip_pt_aov_download.argtypes = [vp, vp]
         lib.amber_hip_pt_device_aov.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    if hasattr(lib, "amber_hip_pt_denoise"):
+        lib.amber_hip_pt_denoise.argtypes = [vp, u32, C.POINTER(DenoiseParams), u32, vp, u64, u32]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -615,6 +623,40 @@ class PathTracer:
         p, n = C.c_void_p(), C.c_uint64()
         _check(load_library().amber_hip_pt_device_aov(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def denoise(self, n_samples: int, levels: int = 5, k_normal: float = 4.0, k_albedo: float = 100.0, k_depth: float = 10.0, k_color: float = 0.25,
+                format: int = RESOLVE_RGB8, mirror: bool = False, out=None):
+        """amber_hip_pt_denoise: the band's mean image (sums / n_samples) through `levels` levels of the edge-avoiding a-trous filter, guided by the
+        AOV buffer (aov_pass the same samples first; a buffer never filled gives all-zero guides and only the colour stop acts), then through
+        resolve's output stage: RESOLVE_MEAN_F32 is the filtered image itself, RESOLVE_RGB8 / RESOLVE_RGBA8 its Filmic + Gamma bytes.  The filter is a
+        fixed sequence of binary32 operations (include/amber_hip.h states it; tests/denoise_reference.py restates it in numpy).  A tap's weight falls
+        to zero where the squared distance of the normals reaches 1 / k_normal, of the albedos 1 / k_albedo, of the colours 1 / k_color (a quarter of
+        that at every further level), and where the depths differ by 1 / k_depth of the pixel's depth.  The defaults -- normals about 30 degrees apart,
+        albedo 0.1 apart, depth 10 % apart, colour 2.0 apart at level 0 -- are starting points: nobody has measured their quality on this renderer's
+        frames.  A band filters within itself (no halo across ranks); a striped handle is refused.  Leaves the framebuffer, the AOV buffer, the ray
+        counter and kernel_time() alone.
+
+        out, torch handling and ORDERING exactly as resolve()."""
+        if format not in (RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8):
+            raise AmberError(f"denoise: unknown format {format}")
+        rows, width, _ = self.band_shape
+        channels, flags = (4 if format == RESOLVE_RGBA8 else 3), (RESOLVE_MIRROR_X if mirror else 0)
+        params = DenoiseParams(levels=levels, k_normal=k_normal, k_albedo=k_albedo, k_depth=k_depth, k_color=k_color)
+        lib = load_library()
+        if out is None:
+            res = np.empty((rows, width, channels), np.float32 if format == RESOLVE_MEAN_F32 else np.uint8)
+            _check(lib.amber_hip_pt_denoise(self._h, n_samples, C.byref(params), format, res.ctypes.data, res.nbytes, flags | RESOLVE_HOST))
+            return res
+        if not self._is_torch(out):
+            raise AmberError("denoise: out must be None or a torch tensor on the handle's device")
+        import torch
+        dtype = torch.float32 if format == RESOLVE_MEAN_F32 else torch.uint8
+        if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or out.numel() != rows * width * channels:
+            raise AmberError(f"denoise: out must be a contiguous {dtype} tensor of {rows} x {width} x {channels} elements on the handle's device")
+        same = self._torch_enter(torch, out.device)
+        _check(lib.amber_hip_pt_denoise(self._h, n_samples, C.byref(params), format, out.data_ptr(), out.numel() * out.element_size(), flags))
+        self._torch_leave(same)
+        return out
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

@@ -22,6 +22,8 @@
 //                          a streaming kernel, four output pixels per thread, bytes equal to the host's output stage.
 //   aov.inc                amber_hip_pt_aov_pass and its three companions: the first-hit guide images (albedo, depth, normal, coverage) of the band --
 //                          one thread per band pixel looping over the samples, the eight sums in registers, every engine's own closest hit.
+//   denoise.inc            amber_hip_pt_denoise: the edge-avoiding a-trous filter of the mean image guided by the AOV buffer -- a prepare kernel (mean and
+//                          guide records), one kernel per level (a thread per pixel, 25 taps, polynomial edge stops), then resolve.inc's kernel.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -178,6 +180,8 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<uint8_t> d_query_out;
   DevBuf<uint8_t> d_resolve_out;            // amber_hip_pt_resolve with AMBER_RESOLVE_HOST (resolve.inc): staging of the output, grown on first use and reused
   DevBuf<float4> d_aov;                     // amber_hip_pt_aov_* (aov.inc): two float4 per band pixel, allocated and zeroed by the first of those calls
+  DevBuf<float> d_denoise_color[2];         // amber_hip_pt_denoise (denoise.inc): the levels' input and output, 3 floats per band pixel each, grown on first use
+  DevBuf<float4> d_denoise_guide;           // ... and the guide records {a.xyz, z} {n.xyz, rz}, two float4 per band pixel
   DevBuf<float> d_fb;
   DevBuf<unsigned long long> d_rays;
   DevBuf<unsigned int> d_next;
@@ -766,6 +770,7 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 #include "ray_query.inc"
 #include "resolve.inc"
 #include "aov.inc"
+#include "denoise.inc"
 
 extern "C" {
 
@@ -1007,6 +1012,10 @@ int amber_hip_pt_aov_download(amber_hip_pt* h, AmberAovPixel* out) {
 
 int amber_hip_pt_device_aov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
   return Guarded("amber_hip_pt_device_aov", [&] { return DeviceAov(h, dptr, n_pixels); });
+}
+
+int amber_hip_pt_denoise(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
+  return Guarded("amber_hip_pt_denoise", [&] { return Denoise(h, n_samples, params, format, out, out_bytes, flags); });
 }
 
 int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) { return Guarded("amber_hip_pt_build_info", [&]() -> int {

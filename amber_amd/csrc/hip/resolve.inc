@@ -106,11 +106,11 @@ __global__ void __launch_bounds__(256) resolve_kernel(const float* __restrict__ 
 constexpr uint64_t kResolveBytesPerPixel[3] = {12u, 3u, 4u};                  // MEAN_F32, RGB8, RGBA8
 
 template <int kFormat>
-void LaunchResolve(amber_hip_pt* h, bool mirror, void* d_out, uint64_t n_pixels, float n) {
+void LaunchResolve(amber_hip_pt* h, const float* src, bool mirror, void* d_out, uint64_t n_pixels, float n) {   // src: sums of the band's layout (the framebuffer; denoise.inc: a filtered mean with n = 1)
   const uint64_t n_vector = reinterpret_cast<uintptr_t>(d_out) % 16u == 0u ? n_pixels / 4u * 4u : 0u;
   const uint32_t n_blocks = static_cast<uint32_t>(((n_pixels + 3u) / 4u + 255u) / 256u);      // n_pixels < 2^32: at most 2^22 workgroups
-  if (mirror) hipLaunchKernelGGL((resolve_kernel<kFormat, true>), dim3(n_blocks), dim3(256), 0, h->stream, h->d_fb.p, d_out, n_pixels, n_vector, h->scene.sensor.w, n);
-  else hipLaunchKernelGGL((resolve_kernel<kFormat, false>), dim3(n_blocks), dim3(256), 0, h->stream, h->d_fb.p, d_out, n_pixels, n_vector, h->scene.sensor.w, n);
+  if (mirror) hipLaunchKernelGGL((resolve_kernel<kFormat, true>), dim3(n_blocks), dim3(256), 0, h->stream, src, d_out, n_pixels, n_vector, h->scene.sensor.w, n);
+  else hipLaunchKernelGGL((resolve_kernel<kFormat, false>), dim3(n_blocks), dim3(256), 0, h->stream, src, d_out, n_pixels, n_vector, h->scene.sensor.w, n);
 }
 
 int Resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
@@ -140,9 +140,9 @@ int Resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uin
   }
   const float n = static_cast<float>(n_samples);
   const bool mirror = (flags & AMBER_RESOLVE_MIRROR_X) != 0u;
-  if (format == AMBER_RESOLVE_MEAN_F32) LaunchResolve<AMBER_RESOLVE_MEAN_F32>(h, mirror, d_out, n_pixels, n);
-  else if (format == AMBER_RESOLVE_RGB8) LaunchResolve<AMBER_RESOLVE_RGB8>(h, mirror, d_out, n_pixels, n);
-  else LaunchResolve<AMBER_RESOLVE_RGBA8>(h, mirror, d_out, n_pixels, n);
+  if (format == AMBER_RESOLVE_MEAN_F32) LaunchResolve<AMBER_RESOLVE_MEAN_F32>(h, h->d_fb.p, mirror, d_out, n_pixels, n);
+  else if (format == AMBER_RESOLVE_RGB8) LaunchResolve<AMBER_RESOLVE_RGB8>(h, h->d_fb.p, mirror, d_out, n_pixels, n);
+  else LaunchResolve<AMBER_RESOLVE_RGBA8>(h, h->d_fb.p, mirror, d_out, n_pixels, n);
   HIP_TRY(hipGetLastError());
   if (host) {
     HIP_TRY(hipMemcpyAsync(out, d_out, want, hipMemcpyDeviceToHost, h->stream));

@@ -368,6 +368,41 @@ int  amber_hip_pt_aov_pass(amber_hip_pt*, uint32_t first_sample, uint32_t n_samp
 int  amber_hip_pt_aov_clear(amber_hip_pt*);
 int  amber_hip_pt_aov_download(amber_hip_pt*, AmberAovPixel* out);      /* band layout of amber_hip_pt_download: local rows in increasing y, width pixels each; synchronises */
 int  amber_hip_pt_device_aov(amber_hip_pt*, void** dptr, uint64_t* n_pixels);
+/* A device filter between accumulation and the output stage: the edge-avoiding a-trous wavelet transform (Dammertz, Sewtz, Hanika, Lensch, HPG 2010)
+ * of the band's mean image, guided by the AOV buffer, with compactly supported polynomial edge-stopping weights instead of exponentials: a fixed
+ * sequence of binary32 operations, no transcendental function.  Still ABI version 3: a new function and one struct.
+ * Every operation is binary32 and rounded alone.  Band pixel p = (x, y) uses local row y; fb is the framebuffer's sums, A the AOV sums.
+ *   1. input colour   c0(p) = fb(p) / (float)n_samples, per channel (amber_hip_pt_resolve's mean)
+ *   2. guide          cov = A.coverage.  If cov > 0: a = A.albedo / cov, n = A.normal / cov (not renormalised), z = A.depth / cov; otherwise
+ *                     a = n = 0 and z = 0.  rz = (z > 0) ? 1 / z : 0.
+ *   3. level step     level i = 0 .. levels-1 has step s = 2^i, input c_i and output c_{i+1}.  The taps are q = (x + dx*s, y + dy*s), dy = -2..2 the
+ *                     outer loop and dx = -2..2 the inner loop, both ascending.  A tap outside the band is skipped: nothing is added for it.
+ *                     hw = H[dy] * H[dx] with H = {1/16, 1/4, 3/8, 1/4, 1/16} (these products are exact).
+ *   4. tap weight     the centre tap: w = hw (not computed, so sum_w >= 9/64 always).  Every other tap, with
+ *                     sq(u, v) = ((u0-v0)*(u0-v0) + (u1-v1)*(u1-v1)) + (u2-v2)*(u2-v2) and clamp0(t) = (t > 0) ? t : 0 (so NaN gives 0):
+ *                       tn = clamp0(1 - sq(n_p, n_q) * k_normal)
+ *                       ta = clamp0(1 - sq(a_p, a_q) * k_albedo)
+ *                       tz = clamp0(1 - (|z_p - z_q| * rz_p) * k_depth)
+ *                       tc = clamp0(1 - sq(c_i(p), c_i(q)) * kc_i),  kc_0 = k_color, kc_{i+1} = kc_i * 4
+ *                       e  = ((tn * ta) * tz) * tc
+ *                       w  = hw * (e * e)
+ *   5. accumulation   S_r, S_g, S_b and S_w start at 0; each tap adds w * c_i(q) per channel and w, in tap order; c_{i+1}(p) = S / S_w.
+ *   6. output stage   c_levels goes through amber_hip_pt_resolve's output stage unchanged: AMBER_RESOLVE_MEAN_F32 is c_levels itself, RGB8 / RGBA8
+ *                     its Filmic + Gamma bytes.
+ * format, out, out_bytes and flags mean exactly what they mean for amber_hip_pt_resolve (formats MEAN_F32 / RGB8 / RGBA8, flags AMBER_RESOLVE_HOST
+ * and AMBER_RESOLVE_MIRROR_X, the same size and alignment checks); the call is stream-ordered on the handle's stream unless HOST, and first waits
+ * for a pass whose record buffer was sized from an estimate, as resolve does.  It reads the framebuffer and the AOV buffer (allocated and zeroed here
+ * if no amber_hip_pt_aov_* call has: all-zero guides, only the colour stop acts) and writes only out and buffers of its own (two colour buffers
+ * and a guide buffer, 56 bytes per band pixel, grown on first use, released by destroy): the framebuffer, the AOV buffer, the ray counter and
+ * amber_hip_pt_kernel_time are untouched.  Every engine, both builds.
+ * Not part of it: albedo demodulation (materials are per object, so albedo edges are object edges), temporal accumulation, variance guidance, a halo
+ * across ranks (a band filters within itself: a tap outside the band is a tap outside the image), the command line and the C++ adapter.
+ * AMBER_EINVAL, with a message and the handle left working: a NULL handle or params, n_samples == 0, levels outside 1..8, a negative, NaN or infinite
+ * k_*, non-zero reserved, an unknown format or flag, any other out_bytes, out == NULL with a non-empty band, a misaligned device pointer, a striped
+ * handle (stripe_period != 0: its local rows are not neighbours in the frame).  An empty band: AMBER_OK. */
+typedef struct { uint32_t levels; float k_normal; float k_albedo; float k_depth; float k_color; uint32_t reserved[3]; } AmberDenoiseParams;  /* 32 bytes */
+int  amber_hip_pt_denoise(amber_hip_pt*, uint32_t n_samples, const AmberDenoiseParams* params,
+                          uint32_t format, void* out, uint64_t out_bytes, uint32_t flags);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);
