@@ -98,6 +98,17 @@ class DenoiseParams(C.Structure):
                 ("reserved", C.c_uint32 * 3)]
 
 
+class MomentsPixel(C.Structure):
+    """AmberMomentsPixel: the sums of the batches' luminance and of its square, and the number of batches -- 16 bytes (amber_hip_pt_render_batch)."""
+    _fields_ = [("m1", C.c_float), ("m2", C.c_float), ("batches", C.c_float), ("pad", C.c_float)]
+
+
+class DenoiseVarianceParams(C.Structure):
+    """AmberDenoiseVarianceParams: levels (1..8), the three guide stops' constants, k_lum and var_radius (0..3) of amber_hip_pt_denoise_variance -- 32 bytes."""
+    _fields_ = [("levels", C.c_uint32), ("k_normal", C.c_float), ("k_albedo", C.c_float), ("k_depth", C.c_float), ("k_lum", C.c_float),
+                ("var_radius", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class BvhDumpInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_prims", C.c_uint32), ("root", C.c_int32), ("depth", C.c_uint32),
                 ("gmin", C.c_float * 3), ("step", C.c_float * 3), ("reach", C.c_float * 3)]
@@ -129,6 +140,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_update_lens",
     "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_resolve", "amber_hip_pt_destroy",
     "amber_hip_pt_aov_pass", "amber_hip_pt_aov_clear", "amber_hip_pt_aov_download", "amber_hip_pt_device_aov", "amber_hip_pt_denoise",
+    "amber_hip_pt_render_batch", "amber_hip_pt_moments_clear", "amber_hip_pt_moments_download", "amber_hip_pt_device_moments", "amber_hip_pt_denoise_variance",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -201,6 +213,12 @@ def load_library() -> C.CDLL:
         lib.amber_hip_pt_device_aov.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_pt_denoise"):
         lib.amber_hip_pt_denoise.argtypes = [vp, u32, C.POINTER(DenoiseParams), u32, vp, u64, u32]
+    if hasattr(lib, "amber_hip_pt_render_batch"):
+        lib.amber_hip_pt_render_batch.argtypes = [vp, u32, u32]
+        lib.amber_hip_pt_moments_clear.argtypes = [vp]
+        lib.amber_hip_pt_moments_download.argtypes = [vp, vp]
+        lib.amber_hip_pt_device_moments.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+        lib.amber_hip_pt_denoise_variance.argtypes = [vp, u32, C.POINTER(DenoiseVarianceParams), u32, vp, u64, u32]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -637,26 +655,71 @@ class PathTracer:
         counter and kernel_time() alone.
 
         out, torch handling and ORDERING exactly as resolve()."""
+        params = DenoiseParams(levels=levels, k_normal=k_normal, k_albedo=k_albedo, k_depth=k_depth, k_color=k_color)
+        return self._filter("denoise", load_library().amber_hip_pt_denoise, n_samples, params, format, mirror, out)
+
+    def _filter(self, what: str, entry, n_samples: int, params, format: int, mirror: bool, out):
+        """the output handling denoise() and denoise_variance() share: resolve()'s"""
         if format not in (RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8):
-            raise AmberError(f"denoise: unknown format {format}")
+            raise AmberError(f"{what}: unknown format {format}")
         rows, width, _ = self.band_shape
         channels, flags = (4 if format == RESOLVE_RGBA8 else 3), (RESOLVE_MIRROR_X if mirror else 0)
-        params = DenoiseParams(levels=levels, k_normal=k_normal, k_albedo=k_albedo, k_depth=k_depth, k_color=k_color)
-        lib = load_library()
         if out is None:
             res = np.empty((rows, width, channels), np.float32 if format == RESOLVE_MEAN_F32 else np.uint8)
-            _check(lib.amber_hip_pt_denoise(self._h, n_samples, C.byref(params), format, res.ctypes.data, res.nbytes, flags | RESOLVE_HOST))
+            _check(entry(self._h, n_samples, C.byref(params), format, res.ctypes.data, res.nbytes, flags | RESOLVE_HOST))
             return res
         if not self._is_torch(out):
-            raise AmberError("denoise: out must be None or a torch tensor on the handle's device")
+            raise AmberError(f"{what}: out must be None or a torch tensor on the handle's device")
         import torch
         dtype = torch.float32 if format == RESOLVE_MEAN_F32 else torch.uint8
         if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or out.numel() != rows * width * channels:
-            raise AmberError(f"denoise: out must be a contiguous {dtype} tensor of {rows} x {width} x {channels} elements on the handle's device")
+            raise AmberError(f"{what}: out must be a contiguous {dtype} tensor of {rows} x {width} x {channels} elements on the handle's device")
         same = self._torch_enter(torch, out.device)
-        _check(lib.amber_hip_pt_denoise(self._h, n_samples, C.byref(params), format, out.data_ptr(), out.numel() * out.element_size(), flags))
+        _check(entry(self._h, n_samples, C.byref(params), format, out.data_ptr(), out.numel() * out.element_size(), flags))
         self._torch_leave(same)
         return out
+
+    # ---- batch moments and the variance-guided filter ------------------------------------------
+    def render_batch(self, first_sample: int, n_samples: int) -> None:
+        """amber_hip_pt_render_batch: render_pass(first_sample, n_samples) whose sums B land in a zeroed buffer of their own, then fb = fb + B and the
+        luminance Y of B / n_samples into the pixel's moments: m1 += Y, m2 += Y * Y, batches += 1.  Up to one accumulation chunk of samples the
+        framebuffer gets render_pass's very bits; a longer batch is summed first and added once.  Rays and kernel_time() count as for render_pass.
+        The caller chooses the granularity: four calls of one sample give per-sample moments of a 4-spp frame.  Asynchronous and stream-ordered,
+        except that a pass whose record buffer was sized from an estimate is waited for.  n_samples == 0 changes nothing."""
+        _check(load_library().amber_hip_pt_render_batch(self._h, first_sample, n_samples))
+
+    def moments_clear(self) -> None:
+        """amber_hip_pt_moments_clear: zeroes the moments buffer (asynchronous, on the handle's stream).  The framebuffer is not cleared; clear() in
+        turn leaves the moments alone."""
+        _check(load_library().amber_hip_pt_moments_clear(self._h))
+
+    def moments_download(self) -> np.ndarray:
+        """amber_hip_pt_moments_download: a float32 array of shape band_shape[:2] + (4,) in AmberMomentsPixel's order -- m1, m2, batches, pad -- rows
+        as download() lays them out.  Synchronises."""
+        rows, width, _ = self.band_shape
+        out = np.zeros((rows, width, 4), np.float32)
+        _check(load_library().amber_hip_pt_moments_download(self._h, out.ctypes.data))
+        return out
+
+    def device_moments(self):
+        """amber_hip_pt_device_moments: (device pointer, number of band pixels) of the moments buffer, 4 float32 per pixel.  ORDERING as device_aov."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(load_library().amber_hip_pt_device_moments(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def denoise_variance(self, n_samples: int, levels: int = 5, k_normal: float = 4.0, k_albedo: float = 100.0, k_depth: float = 10.0, k_lum: float = 16.0,
+                         var_radius: int = 3, format: int = RESOLVE_RGB8, mirror: bool = False, out=None):
+        """amber_hip_pt_denoise_variance: denoise() with the colour stop replaced by a luminance stop that the variance of the mean scales.  That variance
+        comes from the moments render_batch keeps (render the frame as batches: four render_batch(s, 1) for a 4-spp frame), pooled over the
+        (2 * var_radius + 1)^2 neighbours the guide stops let through, blurred 3 x 3 and filtered along with the colour.  A tap's weight falls to zero
+        where the luminances differ by sqrt(k_lum) standard deviations of the estimate -- four with k_lum = 16; the guide stops are denoise()'s.  A
+        fixed sequence of binary32 operations (include/amber_hip.h states it; tests/denoise_variance_reference.py restates it in numpy).  The defaults
+        are starting points: nobody has tuned them on this renderer's frames (EXPERIMENTS.md has what was measured).  A band filters within itself; a
+        striped handle is refused.  Leaves the framebuffer, the AOV buffer, the moments, the ray counter and kernel_time() alone.
+
+        out, torch handling and ORDERING exactly as resolve()."""
+        params = DenoiseVarianceParams(levels=levels, k_normal=k_normal, k_albedo=k_albedo, k_depth=k_depth, k_lum=k_lum, var_radius=var_radius)
+        return self._filter("denoise_variance", load_library().amber_hip_pt_denoise_variance, n_samples, params, format, mirror, out)
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

@@ -51,6 +51,13 @@ __device__ __forceinline__ float DenoiseSq(float u0, float u1, float u2, float v
   return (d0 * d0 + d1 * d1) + d2 * d2;
 }
 __device__ __forceinline__ float DenoiseClamp0(float t) { return t > 0.f ? t : 0.f; }     // 0 for a NaN t
+// (tn * ta) * tz: the three guide stops of a tap q seen from p, guide records {a.xyz, z} {n.xyz, rz} (denoise_variance.inc's kernels use it too)
+__device__ __forceinline__ float DenoiseGuideStop(const float4& pa, const float4& pn, const float4& qa, const float4& qn, float k_normal, float k_albedo, float k_depth) {
+  const float tn = DenoiseClamp0(1.0f - DenoiseSq(pn.x, pn.y, pn.z, qn.x, qn.y, qn.z) * k_normal);
+  const float ta = DenoiseClamp0(1.0f - DenoiseSq(pa.x, pa.y, pa.z, qa.x, qa.y, qa.z) * k_albedo);
+  const float tz = DenoiseClamp0(1.0f - (fabsf(pa.w - qa.w) * pn.w) * k_depth);
+  return (tn * ta) * tz;
+}
 
 // the grid is one-dimensional (a band of one column may have 2^30 tile rows): tile b is tile column b % blocks_x of tile row b / blocks_x
 __global__ void __launch_bounds__(256) denoise_level_kernel(const DenoiseLevelArgs a) {
@@ -81,11 +88,8 @@ __global__ void __launch_bounds__(256) denoise_level_kernel(const DenoiseLevelAr
         const float* cq = a.cin + 3u * q;
         const float qr = cq[0], qg = cq[1], qb = cq[2];
         const float4 qa = a.guide[2u * q], qn = a.guide[2u * q + 1u];
-        const float tn = DenoiseClamp0(1.0f - DenoiseSq(pn.x, pn.y, pn.z, qn.x, qn.y, qn.z) * a.k_normal);
-        const float ta = DenoiseClamp0(1.0f - DenoiseSq(pa.x, pa.y, pa.z, qa.x, qa.y, qa.z) * a.k_albedo);
-        const float tz = DenoiseClamp0(1.0f - (fabsf(pa.w - qa.w) * pn.w) * a.k_depth);
         const float tc = DenoiseClamp0(1.0f - DenoiseSq(pr, pg, pb, qr, qg, qb) * a.k_color);
-        const float e = ((tn * ta) * tz) * tc;
+        const float e = DenoiseGuideStop(pa, pn, qa, qn, a.k_normal, a.k_albedo, a.k_depth) * tc;
         const float w = hw * (e * e);
         // branch-free: an outside tap adds +0 four times, which leaves the sums' bits as they are (a sum is never -0: it starts at +0, and
         // x + y is -0 only when both are).  With a branch per tap the compiler waits for every tap's loads where it uses them (46 VGPR, 76
@@ -102,17 +106,12 @@ __global__ void __launch_bounds__(256) denoise_level_kernel(const DenoiseLevelAr
 
 static_assert(sizeof(AmberDenoiseParams) == 32, "AmberDenoiseParams is 32 bytes");
 
-int Denoise(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
-  const std::string name = "amber_hip_pt_denoise";
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (!params) return Fail(AMBER_EINVAL, name + ": null params");
-  if (n_samples == 0) return Fail(AMBER_EINVAL, name + ": n_samples is 0");
-  if (params->levels < 1u || params->levels > 8u) return Fail(AMBER_EINVAL, name + ": levels is " + std::to_string(params->levels) + ", not 1 .. 8");
-  const float k[4] = {params->k_normal, params->k_albedo, params->k_depth, params->k_color};
-  const char* k_name[4] = {"k_normal", "k_albedo", "k_depth", "k_color"};
-  for (int i = 0; i < 4; i++)
-    if (!(k[i] >= 0.f) || std::isinf(k[i])) return Fail(AMBER_EINVAL, name + ": " + k_name[i] + " is negative, NaN or infinite");
-  if (params->reserved[0] | params->reserved[1] | params->reserved[2]) return Fail(AMBER_EINVAL, name + ": reserved fields must be 0");
+// What the output arguments of amber_hip_pt_denoise and amber_hip_pt_denoise_variance (denoise_variance.inc) must satisfy, checked in this order, and
+// what the launches need of them.  AMBER_OK with n_pixels == 0: an empty band, nothing to do.
+struct DenoiseOutput { uint32_t width, rows, blocks_x; uint64_t n_pixels, want, n_tiles; bool host, mirror; };
+
+int CheckDenoiseOutput(const amber_hip_pt* h, const std::string& name, uint32_t format, const void* out, uint64_t out_bytes, uint32_t flags, DenoiseOutput& o) {
+  o = DenoiseOutput{};
   if (format > AMBER_RESOLVE_RGBA8) return Fail(AMBER_EINVAL, name + ": unknown format " + std::to_string(format));
   if (flags & ~static_cast<uint32_t>(AMBER_RESOLVE_HOST | AMBER_RESOLVE_MIRROR_X)) return Fail(AMBER_EINVAL, name + ": unknown flag bits");
   if (h->stripe_period != 0u) return Fail(AMBER_EINVAL, name + ": a striped handle's local rows are not neighbours in the frame; filter a contiguous band");
@@ -130,6 +129,27 @@ int Denoise(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseParams* param
   const uint32_t blocks_x = (width + 63u) / 64u;
   const uint64_t n_tiles = static_cast<uint64_t>(blocks_x) * ((rows + 3u) / 4u);
   if (n_tiles > 0x7fffffffull) return Fail(AMBER_EINVAL, name + ": band too large for one launch");
+  o.width = width; o.rows = rows; o.blocks_x = blocks_x; o.n_pixels = n_pixels; o.want = want; o.n_tiles = n_tiles;
+  o.host = host; o.mirror = (flags & AMBER_RESOLVE_MIRROR_X) != 0u;
+  return AMBER_OK;
+}
+
+int Denoise(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
+  const std::string name = "amber_hip_pt_denoise";
+  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
+  if (!params) return Fail(AMBER_EINVAL, name + ": null params");
+  if (n_samples == 0) return Fail(AMBER_EINVAL, name + ": n_samples is 0");
+  if (params->levels < 1u || params->levels > 8u) return Fail(AMBER_EINVAL, name + ": levels is " + std::to_string(params->levels) + ", not 1 .. 8");
+  const float k[4] = {params->k_normal, params->k_albedo, params->k_depth, params->k_color};
+  const char* k_name[4] = {"k_normal", "k_albedo", "k_depth", "k_color"};
+  for (int i = 0; i < 4; i++)
+    if (!(k[i] >= 0.f) || std::isinf(k[i])) return Fail(AMBER_EINVAL, name + ": " + k_name[i] + " is negative, NaN or infinite");
+  if (params->reserved[0] | params->reserved[1] | params->reserved[2]) return Fail(AMBER_EINVAL, name + ": reserved fields must be 0");
+  DenoiseOutput o{};
+  { const int rc = CheckDenoiseOutput(h, name, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
+  const uint32_t width = o.width, rows = o.rows, blocks_x = o.blocks_x;
+  const uint64_t n_pixels = o.n_pixels, want = o.want, n_tiles = o.n_tiles;
+  const bool host = o.host;
   HIP_TRY(hipSetDevice(h->device));
   if (h->pending && !h->pending_checked) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }      // as resolve: the sums must stand
   { const int rc = EnsureAov(h, name.c_str()); if (rc != AMBER_OK) return rc; }

@@ -24,6 +24,8 @@
 //                          one thread per band pixel looping over the samples, the eight sums in registers, every engine's own closest hit.
 //   denoise.inc            amber_hip_pt_denoise: the edge-avoiding a-trous filter of the mean image guided by the AOV buffer -- a prepare kernel (mean and
 //                          guide records), one kernel per level (a thread per pixel, 25 taps, polynomial edge stops), then resolve.inc's kernel.
+//   denoise_variance.inc   amber_hip_pt_render_batch's fold and the moments buffer's three companions, and amber_hip_pt_denoise_variance: the same filter with a
+//                          luminance stop scaled by the per-pixel variance of the mean, colour and variance in one 16-byte record per pixel.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -182,7 +184,11 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<float4> d_aov;                     // amber_hip_pt_aov_* (aov.inc): two float4 per band pixel, allocated and zeroed by the first of those calls
   DevBuf<float> d_denoise_color[2];         // amber_hip_pt_denoise (denoise.inc): the levels' input and output, 3 floats per band pixel each, grown on first use
   DevBuf<float4> d_denoise_guide;           // ... and the guide records {a.xyz, z} {n.xyz, rz}, two float4 per band pixel
+  DevBuf<float4> d_dv_record[2];            // amber_hip_pt_denoise_variance (denoise_variance.inc): {c.rgb, var} per band pixel, the levels' input and output, grown on first use
+  DevBuf<float4> d_moments;                 // amber_hip_pt_render_batch / _moments_*: {m1, m2, batches, pad} per band pixel, allocated and zeroed by the first call that needs it
+  DevBuf<float> d_batch;                    // amber_hip_pt_render_batch: the sums of the batch in flight, 3 floats per band pixel, grown on first use
   DevBuf<float> d_fb;
+  float* accum_target = nullptr;            // where reduce_flagged_kernel and reduce_partials_kernel add a pass: d_fb, except inside amber_hip_pt_render_batch (d_batch)
   DevBuf<unsigned long long> d_rays;
   DevBuf<unsigned int> d_next;
   DevBuf<unsigned long long> d_stamps;
@@ -202,6 +208,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   Event pending_event;
   bool pending = false, pending_checked = true;   // a launch whose record counter has not been looked at yet; checked = it cannot have run out of slots
   uint32_t pending_first = 0, pending_n = 0;
+  float* pending_target = nullptr;          // the accumulation target of that launch: a repeat adds to the same buffer
   bool density_known = false;
   double rec_density = 0;                   // record slots used per path, as the last launch measured it
   DevBuf<int32_t> d_bvh_stack;              // pt_bvh_pool_kernel: deep traversal-stack levels
@@ -401,6 +408,7 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
   HIP_TRY(Upload(h.get(), std::vector<DevLens>{p.lens}, 0, sc.lens));
   const size_t fb_floats = static_cast<size_t>(local_rows) * sensor->width * 3;
   HIP_TRY(h->d_fb.alloc(fb_floats));
+  h->accum_target = h->d_fb;
   HIP_TRY(h->d_rays.alloc(1));
   HIP_TRY(h->d_next.alloc(1));
 #ifdef AMBER_STAMPS
@@ -692,12 +700,12 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
   hipLaunchKernelGGL(rec_scan_blocks_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_block_sum, n_rank_blocks, h->d_rec_count, h->rec_capacity, h->d_rays, h->d_rays_launch);
   hipLaunchKernelGGL(rec_place_kernel, dim3(static_cast<uint32_t>(h->n_cus) * 8u), dim3(256), 0, h->stream, h->d_records, h->d_rec_count, h->rec_capacity, h->d_flags,
                      h->d_excl, h->d_block_sum, n, MakeExactDiv(n), h->d_sorted);
-  hipLaunchKernelGGL(reduce_flagged_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, h->d_fb, h->d_flags, h->d_touched, h->d_sorted, h->d_excl, h->d_block_sum,
+  hipLaunchKernelGGL(reduce_flagged_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, h->accum_target, h->d_flags, h->d_touched, h->d_sorted, h->d_excl, h->d_block_sum,
                      h->d_rec_count, h->rec_capacity, n_pixels, n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h->h_rec_count.v, h->d_rec_count, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipEventRecord(h->pending_event.v, h->stream));
-  h->pending = true; h->pending_first = first; h->pending_n = n;
+  h->pending = true; h->pending_first = first; h->pending_n = n; h->pending_target = h->accum_target;
   h->pending_checked = n_paths + RecordSlack(h) <= h->rec_capacity;      // a slot for every path: cannot run out
   return AMBER_OK;
 }
@@ -717,7 +725,10 @@ int ResolvePending(amber_hip_pt* h) {
     h->flags_dirty = true;
     const int rc = EnsureRecordCapacity(h, used + used / 4u + RecordSlack(h));
     if (rc != AMBER_OK) return rc;
+    float* const target = h->accum_target;
+    h->accum_target = h->pending_target;
     const int rl = LaunchPaths(h, h->pending_first, h->pending_n, h->local_rows * h->scene.sensor.w, nullptr);
+    h->accum_target = target;
     if (rl != AMBER_OK) return rl;
   }
   return AMBER_OK;
@@ -771,6 +782,7 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 #include "resolve.inc"
 #include "aov.inc"
 #include "denoise.inc"
+#include "denoise_variance.inc"
 
 extern "C" {
 
@@ -791,6 +803,39 @@ int amber_hip_pt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
 #endif
   if (h->hit_engine != AMBER_ENGINE_BVH || h->bvh_pool || h->bvh_paths) return RenderPassPaths(h, first_sample, n_samples, n_pixels);
   return RenderPassBvhItems(h, first_sample, n_samples, n_pixels, nullptr);
+}); }
+
+// render_pass into the handle's batch buffer (zeroed) instead of the framebuffer, then moments_fold_kernel: fb = fb + B and the batch's luminance into
+// the moments.  The accumulation target points at the batch buffer only inside this call: every way out restores it.
+int amber_hip_pt_render_batch(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) { return Guarded("amber_hip_pt_render_batch", [&]() -> int {
+  const std::string name = "amber_hip_pt_render_batch";
+  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
+  if (n_samples == 0) return AMBER_OK;
+  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, name + ": sample index overflow");
+  HIP_TRY(hipSetDevice(h->device));
+  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  if (n_pixels == 0) return AMBER_OK;                    // empty band
+  if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, name + ": not part of the lab engine WAVEFRONT");
+  // a pass in flight whose record buffer was sized from an estimate may have to be repeated: it must stand before the target moves
+  if (h->pending && !h->pending_checked) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  { const int rc = EnsureMoments(h, name.c_str()); if (rc != AMBER_OK) return rc; }
+  { const int rc = Grow(h, h->d_batch, static_cast<size_t>(n_pixels) * 3u, "batch sums"); if (rc != AMBER_OK) return rc; }
+  HIP_TRY(hipMemsetAsync(h->d_batch, 0, static_cast<size_t>(n_pixels) * 3u * sizeof(float), h->stream));
+  {
+    struct Target {
+      amber_hip_pt* h;
+      explicit Target(amber_hip_pt* handle) : h(handle) { h->accum_target = h->d_batch; }
+      ~Target() { h->accum_target = h->d_fb; }
+    } target(h);
+    int rc = (h->hit_engine != AMBER_ENGINE_BVH || h->bvh_pool || h->bvh_paths) ? RenderPassPaths(h, first_sample, n_samples, n_pixels)
+                                                                                 : RenderPassBvhItems(h, first_sample, n_samples, n_pixels, nullptr);
+    // ... and so must the batch's own last launch before the fold reads its sums (as amber_hip_pt_resolve waits)
+    if (rc == AMBER_OK && h->pending && !h->pending_checked) rc = ResolvePending(h);
+    // (after a failure here a launch may stay pending with the batch buffer for its target: a repeat of it then adds to a buffer nobody reads -- the
+    // next batch zeroes it behind that repeat on the stream -- so nothing of a failed batch reaches the framebuffer or the moments)
+    if (rc != AMBER_OK) return rc;
+  }
+  return FoldBatch(h, n_samples);
 }); }
 
 // sig != null (amber_hip_pt_signatures): one launch of the signature instantiation; nothing reaches the framebuffer or the ray total
@@ -834,7 +879,7 @@ static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n
     HIP_TRY(hipEventRecord(ev.second.v, h->stream));
     if (sig) return AMBER_OK;                                  // the signature launch: nothing reaches the framebuffer
     const uint32_t n_elems = n_pixels * 3u;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((n_elems + 255u) / 256u), dim3(256), 0, h->stream, h->d_fb, h->d_partial, n_elems, n_chunks);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((n_elems + 255u) / 256u), dim3(256), 0, h->stream, h->accum_target, h->d_partial, n_elems, n_chunks);
     HIP_TRY(hipGetLastError());
     done += n;
   }
@@ -1016,6 +1061,22 @@ int amber_hip_pt_device_aov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
 
 int amber_hip_pt_denoise(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
   return Guarded("amber_hip_pt_denoise", [&] { return Denoise(h, n_samples, params, format, out, out_bytes, flags); });
+}
+
+int amber_hip_pt_moments_clear(amber_hip_pt* h) {
+  return Guarded("amber_hip_pt_moments_clear", [&] { return MomentsClear(h); });
+}
+
+int amber_hip_pt_moments_download(amber_hip_pt* h, AmberMomentsPixel* out) {
+  return Guarded("amber_hip_pt_moments_download", [&] { return MomentsDownload(h, out); });
+}
+
+int amber_hip_pt_device_moments(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
+  return Guarded("amber_hip_pt_device_moments", [&] { return DeviceMoments(h, dptr, n_pixels); });
+}
+
+int amber_hip_pt_denoise_variance(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseVarianceParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
+  return Guarded("amber_hip_pt_denoise_variance", [&] { return DenoiseVariance(h, n_samples, params, format, out, out_bytes, flags); });
 }
 
 int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) { return Guarded("amber_hip_pt_build_info", [&]() -> int {

@@ -403,6 +403,68 @@ int  amber_hip_pt_device_aov(amber_hip_pt*, void** dptr, uint64_t* n_pixels);
 typedef struct { uint32_t levels; float k_normal; float k_albedo; float k_depth; float k_color; uint32_t reserved[3]; } AmberDenoiseParams;  /* 32 bytes */
 int  amber_hip_pt_denoise(amber_hip_pt*, uint32_t n_samples, const AmberDenoiseParams* params,
                           uint32_t format, void* out, uint64_t out_bytes, uint32_t flags);
+/* Batch moments: a per-pixel record of how much the batches of a frame disagree, the input a variance-guided filter needs and nothing else in the
+ * handle keeps (the render kernels keep only the paths that reach a light or chunk sums, the framebuffer only the total).  Still ABI version 3: four new
+ * functions and one struct.  No render kernel changes: a batch is a render_pass whose sums land in a buffer of their own first.
+ * Definition.  Every operation is binary32 and rounded alone.  B(p) is what amber_hip_pt_render_pass(first_sample, n_samples) leaves in a framebuffer
+ * that held +0.  amber_hip_pt_render_batch(h, first_sample, n_samples) does, per band pixel and channel, fb = fb + B, adds the batch's rays to the ray
+ * counter and its launches to amber_hip_pt_kernel_time exactly as render_pass does, and then, with b = B / (float)n_samples per channel:
+ *   Y = (0.2126f * b_r + 0.7152f * b_g) + 0.0722f * b_b;   m1 = m1 + Y;   m2 = m2 + Y * Y;   batches = batches + 1.0f;   pad stays 0.
+ * Consequences.  For n_samples <= AMBER_ACCUM_CHUNK the batch is one chunk, and the framebuffer gets the very bits render_pass gives it (fb + (0 + chunk)
+ * is fb + chunk; the one exception is a pixel whose sum somebody uploaded as -0, which a batch without light turns into +0).  A longer batch is summed
+ * first, chunk by chunk from +0, and added once: its own, stated, order, not render_pass's.  The caller chooses the granularity: four calls of one
+ * sample give per-sample moments of a 4-spp frame, eight calls of eight batch moments of a 64-spp frame.  m2 / batches - (m1 / batches)^2 estimates the
+ * variance of ONE batch's luminance; the variance of the frame's mean is that over `batches`, which assumes batches of equal size.
+ * Buffers and order.  The rules of the AOV functions: the first of these calls (or amber_hip_pt_denoise_variance) allocates the moments buffer
+ * (rows * width * 16 bytes) and zeroes it; amber_hip_pt_clear does not clear the moments and moments_clear does not clear the framebuffer;
+ * amber_hip_pt_update_objects / _update_lens leave the moments alone; destroy releases everything; a handle that never calls these pays nothing.
+ * render_batch also owns a batch buffer (12 bytes per band pixel, grown on first use).  render_batch and moments_clear are asynchronous and
+ * stream-ordered on the handle's stream like render_pass, with render_pass's exception: where a pass's record buffer was sized from an estimate (see
+ * AMBER_HIP_ABI_VERSION, 2) the call waits for that pass -- an earlier one before the batch starts, the batch's own before its sums are folded.
+ *   moments_download  copies the band's pixels to the host in amber_hip_pt_download's layout; synchronises.
+ *   device_moments    the device pointer of the buffer and the band's pixel count, as amber_hip_pt_device_aov.  n_pixels may be NULL.
+ * Engines: every product engine in both builds, AMBER_PT_FLAG_BVH_ITEMS and AMBER_PT_FLAG_DEVICE_BUILD included; a handle of the lab engine WAVEFRONT
+ * answers AMBER_EINVAL to render_batch.
+ * n_samples == 0: AMBER_OK, nothing changes, not even batches.  An empty band: AMBER_OK.  AMBER_EINVAL as render_pass gives it: a NULL handle (or out,
+ * or dptr), first_sample + n_samples > 2^32 - 1.  After any other error of render_batch nothing of the batch has reached the framebuffer or the moments. */
+typedef struct { float m1, m2, batches, pad; } AmberMomentsPixel;   /* 16 bytes: one float4 */
+int  amber_hip_pt_render_batch(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples);
+int  amber_hip_pt_moments_clear(amber_hip_pt*);
+int  amber_hip_pt_moments_download(amber_hip_pt*, AmberMomentsPixel* out);      /* band layout of amber_hip_pt_download; synchronises */
+int  amber_hip_pt_device_moments(amber_hip_pt*, void** dptr, uint64_t* n_pixels);
+/* amber_hip_pt_denoise with the colour stop replaced by a luminance stop that the variance of the mean scales, and that variance filtered along with
+ * the colour (after Schied et al., HPG 2017, without its temporal part): what a frame of a few very bright pixels in black needs, which the colour stop
+ * of amber_hip_pt_denoise returns unchanged.  Still ABI version 3: a new function and one struct.
+ * Every operation is binary32 and rounded alone.  fb, A, the band, sq, clamp0, H, hw and the order of the taps are amber_hip_pt_denoise's; M is the
+ * moments buffer; lum(c) = (0.2126f * c_r + 0.7152f * c_g) + 0.0722f * c_b.
+ *   1. input          c0 = fb / (float)n_samples.  The guide (a, n, z, rz) is exactly steps 1 and 2 of amber_hip_pt_denoise.
+ *   2. moments        if M.batches > 0: u1 = M.m1 / M.batches, u2 = M.m2 / M.batches, e = 1; otherwise u1 = u2 = e = 0.
+ *   3. variance of the mean   R = var_radius.  The taps are q = (x + dx, y + dy), dy = -R..R the outer loop and dx the inner, both ascending; a tap outside
+ *                     the band is skipped.  The centre tap has g = e_p; every other tap g = ((tn * ta) * tz) * e_q with tn, ta, tz the three guide stops
+ *                     of amber_hip_pt_denoise's step 4 and this call's k_*.  A1, A2 and G start at 0; each tap adds g * u1_q, g * u2_q and g.
+ *                     If G > 0: mu = A1 / G, v = clamp0(A2 / G - mu * mu); otherwise v = 0.  var_0(p) = (batches_p > 0) ? v / batches_p : v.
+ *                     R = 0 is the pixel's own batch variance; R > 0 pools the neighbours on the same surface, which is what a pixel whose samples
+ *                     are all zero next to a firefly needs.
+ *   4. level i        step 2^i, taps, hw and the centre tap (w = hw, not computed) as amber_hip_pt_denoise.
+ *                     gv(p) = the 3 x 3 binomial blur of var_i at unit spacing at every level, coordinates clamped to the band (so the weights
+ *                     {1,2,1} x {1,2,1} / 16 always sum to 1), summed from 0 in row-major order, each term weight * var_i.
+ *                     r_p = 1 / (k_lum * gv(p) + 1e-10f).
+ *                     A non-centre tap: d = lum(c_i(p)) - lum(c_i(q)), tl = clamp0(1 - (d * d) * r_p), e = ((tn * ta) * tz) * tl, w = hw * (e * e).
+ *                     S_r, S_g, S_b, S_v and S_w start at 0; each tap adds w * c_i(q) per channel, (w * w) * var_i(q) and w, in tap order.
+ *                     c_{i+1} = S / S_w, var_{i+1} = S_v / (S_w * S_w).  No per-level scaling of k_lum: the variance shrinks by itself.
+ *   5. output stage   c_levels goes through amber_hip_pt_resolve's output stage, as in amber_hip_pt_denoise.
+ * k_lum = 16 cuts a tap off where the luminances differ by four standard deviations of the (blurred) estimate.  A NaN colour reaches every pixel that
+ * has it for a tap at some level, as in amber_hip_pt_denoise, and no further; a pixel without batches takes part with e = 0.
+ * format, out, out_bytes and flags mean exactly what they mean for amber_hip_pt_denoise, and so do the stream order and the wait for an estimated
+ * pass, the striped-handle and empty-band rules and the size and alignment checks.  The call reads the framebuffer, the AOV buffer and the moments
+ * buffer (each of the latter two allocated and zeroed here if nobody has touched it) and never writes them, the ray counter or
+ * amber_hip_pt_kernel_time.  It writes out and buffers of its own: two record buffers of 16 bytes per band pixel, and amber_hip_pt_denoise's first
+ * colour buffer and guide buffer (a later amber_hip_pt_denoise fills them again: its bytes do not change).  Every engine, both builds.
+ * Not part of it: firefly clamping, temporal reprojection, albedo demodulation, a halo across ranks, the command line and the C++ adapter.
+ * AMBER_EINVAL as amber_hip_pt_denoise gives it (k_lum in k_color's place), plus var_radius > 3 and non-zero reserved.  An empty band: AMBER_OK. */
+typedef struct { uint32_t levels; float k_normal; float k_albedo; float k_depth; float k_lum; uint32_t var_radius; uint32_t reserved[2]; } AmberDenoiseVarianceParams;  /* 32 bytes */
+int  amber_hip_pt_denoise_variance(amber_hip_pt*, uint32_t n_samples, const AmberDenoiseVarianceParams* params,
+                                   uint32_t format, void* out, uint64_t out_bytes, uint32_t flags);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);
