@@ -149,6 +149,7 @@ ABI_SYMBOLS = [
 LAB_SYMBOLS = [
     "amber_hip_kat_cast", "amber_hip_kat_sample", "amber_hip_kat_eye", "amber_hip_kat_trace", "amber_hip_kat_math", "amber_hip_kat_signatures", "amber_hip_pt_signatures",
     "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump", "amber_hip_kat_division",
+    "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -236,6 +237,9 @@ def load_library() -> C.CDLL:
         lib.amber_hip_kat_bvh_dump.argtypes = [vp, vp, u32, vp, u32, C.POINTER(BvhDumpInfo)]
         if hasattr(lib, "amber_hip_kat_division"):     # absent only in older builds loaded by tools/ab_lib.py
             lib.amber_hip_kat_division.argtypes = [i32, i32, u32, vp, vp]
+        if hasattr(lib, "amber_hip_kat_sqrt"):         # the same
+            lib.amber_hip_kat_sqrt.argtypes = [i32, i32, u32, vp, vp]
+            lib.amber_hip_kat_sqrt_sweep.argtypes = [i32, u32, u64, C.POINTER(SqrtSweep)]
     lib.amber_host_cornell_box.restype = vp
     lib.amber_host_cornell_box.argtypes = [C.c_float, C.c_float, u32]
     lib.amber_host_scene_import.restype = vp
@@ -855,6 +859,31 @@ def kat_division(mode: int, x, device: int = 0) -> np.ndarray:
     out = np.empty((n, 3), np.float32)
     _check(load_library().amber_hip_kat_division(device, mode, n, x.ctypes.data, out.ctypes.data))
     return out
+
+
+class SqrtSweep(C.Structure):
+    """AmberSqrtSweep (include/amber_hip_lab.h)."""
+    _fields_ = [("mismatches", C.c_uint64), ("in_range", C.c_uint64), ("n_offenders", C.c_uint32), ("offenders", C.c_uint32 * 8),
+                ("seed_low", C.c_int32), ("seed_high", C.c_int32)]
+
+
+def kat_sqrt(mode: int, x, device: int = 0) -> np.ndarray:
+    """The engine's square root from one v_rsq_f32 seed on device (exact_sqrt.h): mode 0 the guarded fast form, mode 1 __builtin_sqrtf, x (n,) -> (n,);
+    mode 2 / 3 Normalize in the fused / the plain form, x (n, 3) -> (n, 3); mode 4 two roots under one guard, x (n, 2) -> (n, 2)."""
+    width = 1 if mode <= 1 else (3 if mode <= 3 else 2)
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, width)
+    out = np.empty_like(x)
+    _check(load_library().amber_hip_kat_sqrt(device, mode, len(x), x.ctypes.data, out.ctypes.data))
+    return out.reshape(-1) if width == 1 else out
+
+
+def kat_sqrt_sweep(first_bits: int, count: int, device: int = 0) -> dict:
+    """Mode 0 against mode 1 of kat_sqrt over the bit patterns [first_bits, first_bits + count), generated on the device: the number of
+    mismatches, the first offending patterns, the patterns in the fast form's range and v_rsq_f32's extreme distances (ulp) from the nearest float."""
+    r = SqrtSweep()
+    _check(load_library().amber_hip_kat_sqrt_sweep(device, first_bits, count, C.byref(r)))
+    return {"mismatches": int(r.mismatches), "in_range": int(r.in_range), "offenders": [int(b) for b in r.offenders[:min(int(r.n_offenders), 8)]],
+            "seed_low": int(r.seed_low), "seed_high": int(r.seed_high)}
 
 
 MATH_PORTABLE, MATH_GLIBC = 1, 2

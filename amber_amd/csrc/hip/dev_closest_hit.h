@@ -35,6 +35,7 @@ __device__ __forceinline__ bool ReferenceSlab(const float* mn, const float* mx, 
   t_in = t_min;
   return t_min <= t_max;
 }
+template <int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void ClosestHitReferenceBvh(const DevScene& sc, V3 o, V3 d, HitRec& best) {
   best.t = 3.402823466e+38f; best.u = 0.f; best.v = 0.f; best.idx = -1; best.slot = -1;   // Acceleration::Cast(ray, max()), acceleration.h:46-51
   const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
@@ -95,7 +96,7 @@ __device__ __forceinline__ void ClosestHitReferenceBvh(const DevScene& sc, V3 o,
       if (lf.count & 0x80000000u) {                      // spheres only: the 16-byte records of engine BVH's sphere leaves, same operands
         for (uint32_t k = lf.first; k < last; ++k) {
           const float4 sp4 = sc.bvh_spheres[k];
-          IntersectSphere<false>(v3(sp4.x, sp4.y, sp4.z), sp4.w, static_cast<int>(k), static_cast<int>(k), o, d, best);
+          IntersectSphere<false, kSqrt>(v3(sp4.x, sp4.y, sp4.z), sp4.w, static_cast<int>(k), static_cast<int>(k), o, d, best);
         }
       } else if (lf.count & 0x40000000u) {               // triangles only: {A.xyz E1.x} {E1.yz E2.xy} {E2.z ..}
         for (uint32_t k = lf.first; k < last; ++k) {
@@ -107,7 +108,7 @@ __device__ __forceinline__ void ClosestHitReferenceBvh(const DevScene& sc, V3 o,
       } else {
         for (uint32_t k = lf.first; k < last; ++k) {
           const DevObject& ob = sc.bvh_objects[k];
-          IntersectObject<false>(ob, ob.kind, static_cast<int>(k), static_cast<int>(k), o, d, best);
+          IntersectObject<false, kSqrt>(ob, ob.kind, static_cast<int>(k), static_cast<int>(k), o, d, best);
         }
       }
       next_subtree();
@@ -119,14 +120,15 @@ __device__ __forceinline__ void ClosestHitReferenceBvh(const DevScene& sc, V3 o,
 
 enum { ENGINE_LIST = 1, ENGINE_TWO_PHASE = 2, ENGINE_BVH = 3, ENGINE_TWO_PHASE_N = 5, ENGINE_REF_BVH = 6 };   // (4 is the public WAVEFRONT; 5 = two-phase over groups of 32 objects)
 
-template <int kEngine>
+// kSqrt: SolveQuadratic's root (AMBER_EXACT_SQRT bit 8, dev_math.h); engine BVH keeps __builtin_sqrtf
+template <int kEngine, int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void ClosestHit(const DevScene& sc, const DevObject* lds_objects, int32_t* lds_stack, V3 o, V3 d, int origin_slot, HitRec& best AMBER_STAMP_PARAM,
                                            const bool use_premask = false, const uint32_t premask = 0u, const int bvh_stack_cap = AMBER_BVH_STACK) {
-  if (kEngine == ENGINE_TWO_PHASE) ClosestHitTwoPhase(sc, lds_objects, o, d, origin_slot, best AMBER_STAMP_ARG, use_premask, premask);
-  else if (kEngine == ENGINE_TWO_PHASE_N) ClosestHitTwoPhaseGroups(sc, lds_objects, o, d, origin_slot, best AMBER_STAMP_ARG, use_premask, premask);
+  if (kEngine == ENGINE_TWO_PHASE) ClosestHitTwoPhase<kSqrt>(sc, lds_objects, o, d, origin_slot, best AMBER_STAMP_ARG, use_premask, premask);
+  else if (kEngine == ENGINE_TWO_PHASE_N) ClosestHitTwoPhaseGroups<kSqrt>(sc, lds_objects, o, d, origin_slot, best AMBER_STAMP_ARG, use_premask, premask);
   else if (kEngine == ENGINE_BVH) ClosestHitBvh(sc, lds_stack, o, d, best, bvh_stack_cap);
-  else if (kEngine == ENGINE_REF_BVH) ClosestHitReferenceBvh(sc, o, d, best);
-  else ClosestHitList(sc, o, d, best);
+  else if (kEngine == ENGINE_REF_BVH) ClosestHitReferenceBvh<kSqrt>(sc, o, d, best);
+  else ClosestHitList<kSqrt>(sc, o, d, best);
   AMBER_STAMP(3);
 }
 

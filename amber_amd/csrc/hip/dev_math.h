@@ -27,16 +27,29 @@ __device__ __forceinline__ V3 operator-(V3 a) { return V3{-a.x, -a.y, -a.z}; }
 __device__ __forceinline__ float Dot(V3 u, V3 v) { return u.x * v.x + u.y * v.y + u.z * v.z; }
 __device__ __forceinline__ float SquaredLength(V3 v) { return Dot(v, v); }
 // __builtin_sqrtf lowers to the correctly rounded sequence (v_sqrt_f32 + one-ulp fix-up); __fsqrt_rn does NOT on ROCm 7.2
-__device__ __forceinline__ float Sqrt(float x) { return __builtin_sqrtf(x); }
 // kSharedDiv: the three quotients by l through ONE reciprocal (shared_div.h: the same IEEE quotients; the wave falls back to the plain form when
 // a lane is out of range).  The kernels that measured a gain ask for it (pt_megakernel.inc, AMBER_SHARED_DIV_NORMALIZE); everything else, the
 // lab's one-thread-per-path restatement included, keeps the plain divisions.
 #ifndef AMBER_SHARED_DIV_NORMALIZE
 #define AMBER_SHARED_DIV_NORMALIZE 5   /* 1: the lobe's basis (SampleLight), 2: sphere and cylinder normals (ResolveHit; off: it did not measure), 4: the eye ray */
 #endif
-template <bool kSharedDiv = false>
+// kSqrt: how the length is formed.  SQRT_PLAIN: __builtin_sqrtf.  SQRT_EXACT: the same bits from one v_rsq_f32 seed (exact_sqrt.h; the wave
+// falls back to __builtin_sqrtf when a lane is out of range).  SQRT_FUSED (with kSharedDiv): that seed's refined half-reciprocal also starts
+// the division's reciprocal, one guard for the root and the quotients.  Asked for by the same kernels (AMBER_EXACT_SQRT); the switch bits:
+//   1: the lengths of the lobe's two basis vectors   2: the lobe's sqrt(r0), sqrt(1 - r0) and Phong's sin(theta)   4: the eye ray's three lengths
+//   8: SolveQuadratic and refraction's cos(beta)      16: the fused form at the sites of bits 1 and 4
+#ifndef AMBER_EXACT_SQRT
+#define AMBER_EXACT_SQRT 31   /* every site measured a gain in the combination (EXPERIMENTS.md) */
+#endif
+enum { SQRT_PLAIN = 0, SQRT_EXACT = 1, SQRT_FUSED = 2 };
+constexpr int SqrtModeOf(uint32_t mask, uint32_t site_bit) { return (mask & site_bit) ? ((mask & 16u) ? SQRT_FUSED : SQRT_EXACT) : SQRT_PLAIN; }
+template <int kSqrt = SQRT_PLAIN>
+__device__ __forceinline__ float Sqrt(float x) { return kSqrt == SQRT_PLAIN ? __builtin_sqrtf(x) : exact_sqrt::Sqrt1(x); }
+template <bool kSharedDiv = false, int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ V3 Normalize(V3 v) {
-  const float l = Sqrt(SquaredLength(v));
+  const float s = SquaredLength(v);
+  if (kSharedDiv && kSqrt == SQRT_FUSED) { V3 n; exact_sqrt::NormalizeFused(v.x, v.y, v.z, s, n.x, n.y, n.z); return n; }
+  const float l = Sqrt<kSqrt>(s);
   if (kSharedDiv) { V3 n; shared_div::DivByLength(v.x, v.y, v.z, l, n.x, n.y, n.z); return n; }
   return V3{v.x / l, v.y / l, v.z / l};
 }
@@ -46,11 +59,11 @@ __device__ __forceinline__ V3 Cross(V3 u, V3 v) {
 // std::max({x,y,z}) (vector3.h:276-281): first element wins unless a later one is strictly greater
 __device__ __forceinline__ float Max3(V3 v) { float m = v.x; if (m < v.y) m = v.y; if (m < v.z) m = v.z; return m; }
 __device__ __forceinline__ float Abs(float x) { return __builtin_fabsf(x); }
-template <bool kSharedDiv = false>
+template <bool kSharedDiv = false, int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void OrthonormalBasis(V3 w, V3& u, V3& v) {      // vector3.h:330-342
   const bool xs = Abs(w.x) < Abs(w.y);
-  u = Normalize<kSharedDiv>(Cross(w, xs ? v3(1.f, 0.f, 0.f) : v3(0.f, 1.f, 0.f)));
-  v = Normalize<kSharedDiv>(Cross(w, u));
+  u = Normalize<kSharedDiv, kSqrt>(Cross(w, xs ? v3(1.f, 0.f, 0.f) : v3(0.f, 1.f, 0.f)));
+  v = Normalize<kSharedDiv, kSqrt>(Cross(w, u));
 }
 __device__ __forceinline__ V3 MatMul(const float* e, V3 v) {               // matrix3.h:101-109
   return v3(e[0] * v.x + e[1] * v.y + e[2] * v.z, e[3] * v.x + e[4] * v.y + e[5] * v.z, e[6] * v.x + e[7] * v.y + e[8] * v.z);

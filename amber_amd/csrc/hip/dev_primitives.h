@@ -13,10 +13,11 @@ namespace amber_dev {
 struct HitRec { float t, u, v; int idx; int slot; };   // idx: object index (scene order); slot: index into the array the engine scans
 
 // algebra.h:31-52
+template <int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ bool SolveQuadratic(float a, float b, float c, float& alpha, float& beta) {
   const float d = b * b - 4.0f * a * c;
   if (d < 0.0f) return false;
-  const float sqrt_d = Sqrt(d);
+  const float sqrt_d = Sqrt<kSqrt>(d);
   alpha = -b - sqrt_d;
   beta = -b + sqrt_d;
   if (Abs(alpha) < Abs(beta)) { alpha = c / beta * 2.0f; beta = beta / (2.0f * a); }
@@ -49,13 +50,13 @@ __device__ __forceinline__ void IntersectTriangle(V3 A, V3 E1, V3 E2, int i, int
     }
   }
 }
-template <bool kTie>
+template <bool kTie, int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void IntersectSphere(V3 A, float radius, int i, int slot, V3 o, V3 d, HitRec& best) {      // primitive_sphere.cc:75-107
   const V3 co = A - o;
   const float b = -2.0f * Dot(co, d);
   const float c = SquaredLength(co) - radius * radius;
   float alpha, beta;
-  if (SolveQuadratic(1.0f, b, c, alpha, beta)) {
+  if (SolveQuadratic<kSqrt>(1.0f, b, c, alpha, beta)) {
     float t;
     bool ok = true;
     if (alpha > AMBER_KEPS) t = alpha; else if (beta > AMBER_KEPS) t = beta; else { ok = false; t = 0.f; }
@@ -73,7 +74,7 @@ __device__ __forceinline__ void IntersectDisk(V3 A, V3 N, float radius, int i, i
     }
   }
 }
-template <bool kTie>
+template <bool kTie, int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void IntersectCylinder(V3 A, V3 N, float radius, float height, int i, int slot, V3 o, V3 d, HitRec& best) {   // primitive_cylinder.cc:100-142
   const V3 OC = A - o;
   const V3 uu = d - Dot(d, N) * N;
@@ -82,7 +83,7 @@ __device__ __forceinline__ void IntersectCylinder(V3 A, V3 N, float radius, floa
   const float b = -2.0f * Dot(uu, vv);
   const float c = SquaredLength(vv) - radius * radius;
   float alpha, beta;
-  if (SolveQuadratic(a, b, c, alpha, beta)) {
+  if (SolveQuadratic<kSqrt>(a, b, c, alpha, beta)) {
     bool ok = false; float t = 0.f;
     if (alpha > AMBER_KEPS) {
       const float h = Dot(alpha * d - OC, N);
@@ -96,16 +97,17 @@ __device__ __forceinline__ void IntersectCylinder(V3 A, V3 N, float radius, floa
   }
 }
 
-template <bool kTie>
+template <bool kTie, int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void IntersectObject(const DevObject& ob, uint32_t kind, int i, int slot, V3 o, V3 d, HitRec& best) {
   const V3 A = ld3(ob.a);
   if (kind == PRIM_TRIANGLE) IntersectTriangle<kTie>(A, ld3(ob.e1), ld3(ob.e2), i, slot, o, d, best);
-  else if (kind == PRIM_SPHERE) IntersectSphere<kTie>(A, ob.radius, i, slot, o, d, best);
+  else if (kind == PRIM_SPHERE) IntersectSphere<kTie, kSqrt>(A, ob.radius, i, slot, o, d, best);
   else if (kind == PRIM_DISK) IntersectDisk<kTie>(A, ld3(ob.e1), ob.radius, i, slot, o, d, best);
-  else IntersectCylinder<kTie>(A, ld3(ob.e1), ob.radius, ob.height, i, slot, o, d, best);
+  else IntersectCylinder<kTie, kSqrt>(A, ld3(ob.e1), ob.radius, ob.height, i, slot, o, d, best);
 }
 
 // Engine LIST: every object, exact test, wave-uniform index (object data in SGPRs).
+template <int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void ClosestHitList(const DevScene& sc, V3 o, V3 d, HitRec& best) {
   best.t = 3.402823466e+38f; best.u = 0.f; best.v = 0.f; best.idx = -1; best.slot = -1;   // Acceleration::Cast(ray, FLT_MAX)
   const int n = static_cast<int>(sc.n_objects);
@@ -115,9 +117,9 @@ __device__ __forceinline__ void ClosestHitList(const DevScene& sc, V3 o, V3 d, H
     const uint32_t kind = w[3];
     const V3 A = cw_v3(w, 0);
     if (kind == PRIM_TRIANGLE) IntersectTriangle<false>(A, cw_v3(w, 4), cw_v3(w, 8), i, i, o, d, best);
-    else if (kind == PRIM_SPHERE) IntersectSphere<false>(A, cw_f(w, 7), i, i, o, d, best);
+    else if (kind == PRIM_SPHERE) IntersectSphere<false, kSqrt>(A, cw_f(w, 7), i, i, o, d, best);
     else if (kind == PRIM_DISK) IntersectDisk<false>(A, cw_v3(w, 4), cw_f(w, 7), i, i, o, d, best);
-    else IntersectCylinder<false>(A, cw_v3(w, 4), cw_f(w, 7), cw_f(w, 11), i, i, o, d, best);
+    else IntersectCylinder<false, kSqrt>(A, cw_v3(w, 4), cw_f(w, 7), cw_f(w, 11), i, i, o, d, best);
   }
 }
 

@@ -38,7 +38,8 @@ __device__ __forceinline__ V3 Radiance(const DevMaterial& m, V3 normal, V3 dir_o
 }
 
 // Scene::SampleLight -> Material::SampleLight (+ rho forwarders, material_basic.h:233-245, 327-338)
-template <bool kSharedDiv = false>
+// kSqrtMask: the switch bits of AMBER_EXACT_SQRT (dev_math.h) that the calling kernel asks for; 0: every root is __builtin_sqrtf
+template <bool kSharedDiv = false, uint32_t kSqrtMask = 0u>
 __device__ __forceinline__ void SampleLight(const DevMaterial& m, V3 normal, V3 dir_out, uint64_t& rng, V3& dir_in, V3& weight) {
   const V3 rho = ld3(m.rho);
   const uint32_t kind = m.kind;
@@ -53,7 +54,7 @@ __device__ __forceinline__ void SampleLight(const DevMaterial& m, V3 normal, V3 
     const bool phong = kind == MAT_PHONG;
     const float signed_cos_o = AMBER_COS_O();
     const V3 w = phong ? AMBER_MIRROR(signed_cos_o) : (signed_cos_o > 0.0f ? normal : -normal);
-    V3 u, v; OrthonormalBasis<kSharedDiv>(w, u, v);      // CosinePower rebuilds the same basis on every attempt
+    V3 u, v; OrthonormalBasis<kSharedDiv, SqrtModeOf(kSqrtMask, 1u)>(w, u, v);      // CosinePower rebuilds the same basis on every attempt
     // The reference's Phong loop re-samples forever when no direction of the lobe lies on dir_out's side (possible with a
     // normal that is not of unit length); a kernel must terminate, so attempt AMBER_PHONG_MAX_TRIES is accepted as it
     // is (the oracle does the same; with a proper normal at least half of the lobe is acceptable: probability 2^-1024).
@@ -63,7 +64,9 @@ __device__ __forceinline__ void SampleLight(const DevMaterial& m, V3 normal, V3 
       float cos_theta, sin_theta;
       if (phong) {
         cos_theta = Pow(r0, m.aux0);                     // r0 ^ (1 / (e + 1))
-        sin_theta = Sqrt(1.0f - cos_theta * cos_theta);
+        sin_theta = Sqrt<(kSqrtMask & 2u) ? SQRT_EXACT : SQRT_PLAIN>(1.0f - cos_theta * cos_theta);
+      } else if (kSqrtMask & 2u) {
+        exact_sqrt::Sqrt2(r0, 1.0f - r0, cos_theta, sin_theta);      // one guard, one vote (r0 = 0: the whole wave takes __builtin_sqrtf)
       } else {
         cos_theta = Sqrt(r0);
         sin_theta = Sqrt(1.0f - r0);
@@ -90,7 +93,7 @@ __device__ __forceinline__ void SampleLight(const DevMaterial& m, V3 normal, V3 
       dir_in = dir_r; weight = 1.0f * rho;
     } else {
       const float cos_alpha = Abs(signed_cos_alpha);
-      const float cos_beta = Sqrt(squared_cos_beta);
+      const float cos_beta = Sqrt<(kSqrtMask & 8u) ? SQRT_EXACT : SQRT_PLAIN>(squared_cos_beta);
       const V3 dir_t = (-ior) * dir_out + ((signed_cos_alpha < 0.0f ? 1.0f : -1.0f) * cos_beta + ior * signed_cos_alpha) * normal;
       // Schlick (material_refraction.cc:271-275): r0 + (1 - r0) * pow(1 - cos, 5) evaluated in double
       const float rho_r = static_cast<float>(static_cast<double>(m.r0) + static_cast<double>(1.0f - m.r0) * Pow5(1.0f - cos_alpha));
@@ -223,7 +226,7 @@ __device__ __forceinline__ bool LensResponse(const DevScene& sc, V3 position, V3
 // near_edge (optional): the aperture sample lies within DevLens.edge_tol (barycentric) of its blade's boundary -- only then can the exact
 // test of ANOTHER blade accept the ray's own origin (pt_megakernel's primary rounds: which blades are candidates).
 struct EyeRayScene { const DevLens* lens; const DevBlade* blades; DevSensor sensor; };
-template <bool kSharedDiv = false, typename Scene>
+template <bool kSharedDiv = false, int kSqrt = SQRT_PLAIN, typename Scene>
 __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uint32_t py, uint64_t& rng,
                                                V3& origin, V3& dir, float& weight, int& origin_slot, bool* near_edge = nullptr) {
   const DevLens L = LoadLens(sc.lens);
@@ -233,7 +236,7 @@ __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uin
     const float uvx = (static_cast<float>(px) + jx) / sc.sensor.wf;
     const float uvy = (static_cast<float>(py) + jy) / sc.sensor.hf;
     const V3 sensor_point = v3((uvx - 0.5f) * sc.sensor.sw, (uvy - 0.5f) * sc.sensor.sh, L.sensor_distance);
-    const V3 ray_dir = Normalize<kSharedDiv>(MatMul(L.global_, -sensor_point));
+    const V3 ray_dir = Normalize<kSharedDiv, kSqrt>(MatMul(L.global_, -sensor_point));
     // PDFDirection lens_pinhole.cc:93-106 (binary32 throughout; no sensor.Size() factor, unlike the thin lens)
     const V3 dl = MatMul(L.local_, ray_dir);
     const V3 point = (L.sensor_distance / dl.z) * dl;
@@ -260,9 +263,9 @@ __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uin
   const float uvx = (static_cast<float>(px) + jx) / sc.sensor.wf;
   const float uvy = (static_cast<float>(py) + jy) / sc.sensor.hf;
   const V3 sensor_point = v3((uvx - 0.5f) * sc.sensor.sw, (uvy - 0.5f) * sc.sensor.sh, L.sensor_distance);
-  const V3 direction = Normalize<kSharedDiv>(L.neg_fd_over_sd * sensor_point - aperture_point);
-  const double factor = Pow4(Normalize(sensor_point - aperture_point).z / direction.z);      // one component: the plain form divides once
-  const V3 ray_dir = Normalize<kSharedDiv>(MatMul(L.global_, direction));
+  const V3 direction = Normalize<kSharedDiv, kSqrt>(L.neg_fd_over_sd * sensor_point - aperture_point);
+  const double factor = Pow4(Normalize<false, kSqrt>(sensor_point - aperture_point).z / direction.z);      // one component: the plain form divides once
+  const V3 ray_dir = Normalize<kSharedDiv, kSqrt>(MatMul(L.global_, direction));
   const V3 dloc = MatMul(L.local_, ray_dir);
   const float pdf_dir = static_cast<float>(static_cast<double>(L.size_over_area) * L.sd2 / Pow4(dloc.z));
   origin = ap_origin; dir = ray_dir;
@@ -281,21 +284,21 @@ struct Bounce { int object; float t; V3 pos; V3 weight_before; };
 // emitted radiance, and the material is sampled with SampleImportance.
 struct SplatSink { DevSplat* records; unsigned int* count; uint32_t capacity; uint32_t path, sample; float size_f; };
 
-template <bool kTrace, int kEngine, bool kLight, bool kDivBasis = false, bool kDivHit = false>
+template <bool kTrace, int kEngine, bool kLight, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
                                           uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink);
 
-template <bool kTrace, int kEngine, bool kLight = false, bool kDivBasis = false, bool kDivHit = false>
+template <bool kTrace, int kEngine, bool kLight = false, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u>
 __device__ __forceinline__ bool PathStep(const DevScene& sc, const DevObject* lds_objects, int32_t* lds_stack, V3& o, V3& d, V3& weight, V3& measurement,
                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink = nullptr,
                                          const bool use_premask = false, const uint32_t premask = 0u, const int bvh_stack_cap = AMBER_BVH_STACK) {
   HitRec h;
-  ClosestHit<kEngine>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG, use_premask, premask, bvh_stack_cap);
-  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink);
+  ClosestHit<kEngine, (kSqrtMask & 8u) ? SQRT_EXACT : SQRT_PLAIN>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG, use_premask, premask, bvh_stack_cap);
+  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit, kSqrtMask>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink);
 }
 
 // Everything of a bounce after the closest-hit query (algorithm_pt.cc:140-157): h is the result of Scene::Cast.
-template <bool kTrace, int kEngine, bool kLight, bool kDivBasis, bool kDivHit>
+template <bool kTrace, int kEngine, bool kLight, bool kDivBasis, bool kDivHit, uint32_t kSqrtMask>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
                                           uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink) {
   casts++;
@@ -327,7 +330,7 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
   } else {
     measurement = measurement + weight * Radiance(m, normal, dir_out);      // algorithm_pt.cc:144
     AMBER_STAMP(4);
-    SampleLight<kDivBasis>(m, normal, dir_out, rng, dir_in, sw);             // :145-146
+    SampleLight<kDivBasis, kSqrtMask>(m, normal, dir_out, rng, dir_in, sw);             // :145-146
   }
   AMBER_STAMP(5);
   float p_rr = 0.9375f;                                                      // std::min<real_type>(kRussianRoulette, Max(w)) :148-149

@@ -27,31 +27,33 @@ __device__ __forceinline__ FilterView SceneView(const DevScene& sc) {
   return FilterView{(ConstWords)(sc.planes), (ConstWords)(sc.tri_filters), (ConstWords)(sc.sphere_filters), static_cast<int>(sc.n_planes), static_cast<int>(sc.n_simple_planes),
                     static_cast<int>(sc.n_sphere_filters), sc.always_mask, sc.n_prog_tris, sc.n_objects, 0};
 }
-template <bool kMulti, bool kFirst>
+template <bool kMulti, bool kFirst, int kSqrt = SQRT_PLAIN>     // kSqrt: SolveQuadratic's root in the exact tests (AMBER_EXACT_SQRT bit 8, dev_math.h)
 __device__ __forceinline__ void ClosestHitTwoPhaseView(const DevScene& sc, const FilterView fv, const DevObject* lds_objects, V3 o_world, V3 d, int origin_slot, HitRec& best AMBER_STAMP_PARAM,
                                                        const bool use_premask, const uint32_t premask);
+template <int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void ClosestHitTwoPhase(const DevScene& sc, const DevObject* lds_objects, V3 o_world, V3 d, int origin_slot, HitRec& best AMBER_STAMP_PARAM,
                                                    const bool use_premask = false, const uint32_t premask = 0u) {
-  ClosestHitTwoPhaseView<false, true>(sc, SceneView(sc), lds_objects, o_world, d, origin_slot, best AMBER_STAMP_ARG, use_premask, premask);
+  ClosestHitTwoPhaseView<false, true, kSqrt>(sc, SceneView(sc), lds_objects, o_world, d, origin_slot, best AMBER_STAMP_ARG, use_premask, premask);
 }
 // Engine TWO_PHASE_N: every group in turn; the primary rounds' pixel masks describe group 0 only (the other groups run Phase A for eye rays too).
+template <int kSqrt = SQRT_PLAIN>
 __device__ __forceinline__ void ClosestHitTwoPhaseGroups(const DevScene& sc, const DevObject* lds_objects, V3 o_world, V3 d, int origin_slot, HitRec& best AMBER_STAMP_PARAM,
                                                          const bool use_premask = false, const uint32_t premask = 0u) {
-  ClosestHitTwoPhaseView<true, true>(sc, SceneView(sc), lds_objects, o_world, d, origin_slot < 32 ? origin_slot : -1, best AMBER_STAMP_ARG, use_premask, premask);
+  ClosestHitTwoPhaseView<true, true, kSqrt>(sc, SceneView(sc), lds_objects, o_world, d, origin_slot < 32 ? origin_slot : -1, best AMBER_STAMP_ARG, use_premask, premask);
   const int n_groups = static_cast<int>(sc.n_groups);
   ConstWords gw = (ConstWords)(sc.groups);
   for (int g = 1; g < n_groups; ++g) {
     ConstWords w = gw + g * 12;                               // DevFilterGroup = 12 dwords
     const FilterView fv{(ConstWords)(sc.planes) + w[0] * 8u, (ConstWords)(sc.tri_filters) + w[3] * 8u, (ConstWords)(sc.sphere_filters) + w[4] * 8u,
                         static_cast<int>(w[1]), static_cast<int>(w[2]), static_cast<int>(w[5]), w[6], w[7], w[8], g * 32};
-    ClosestHitTwoPhaseView<true, false>(sc, fv, lds_objects, o_world, d, origin_slot, best AMBER_STAMP_ARG, false, 0u);
+    ClosestHitTwoPhaseView<true, false, kSqrt>(sc, fv, lds_objects, o_world, d, origin_slot, best AMBER_STAMP_ARG, false, 0u);
   }
 }
 // The primitive kind in a record of the LDS image: the two-phase engines tag `kind` with index << 8; the grouped engine's records also flag filtered triangles in bit 7.
 template <bool kGrouped> constexpr uint32_t kLdsKindMask = kGrouped ? 0x7fu : 0xffu;
 // kMulti = false: the 32-object engine -- the code of rounds 2-4, operand for operand (slot base 0, the kind byte unmasked: a 1.2 % slower config-2 kernel was
 // the price of sharing ONE instantiation with the grouped engine, tools/ab_lib.py across the round's commits).
-template <bool kMulti, bool kFirst>
+template <bool kMulti, bool kFirst, int kSqrt>
 __device__ __forceinline__ void ClosestHitTwoPhaseView(const DevScene& sc, const FilterView fv, const DevObject* lds_objects_all, V3 o_world, V3 d, int origin_slot_all, HitRec& best AMBER_STAMP_PARAM,
                                                        const bool use_premask, const uint32_t premask) {
   if (kFirst) { best.t = 3.402823466e+38f; best.u = 0.f; best.v = 0.f; best.idx = -1; best.slot = -1; }
@@ -209,7 +211,7 @@ __device__ __forceinline__ void ClosestHitTwoPhaseView(const DevScene& sc, const
     const int slot = __builtin_ctz(mo);
     mo &= mo - 1u;
     const DevObject& ob = lds_objects[slot];
-    IntersectObject<true>(ob, ob.kind & kKindMask, static_cast<int>(ob.kind >> 8), slot_base + slot, o_world, d, best);
+    IntersectObject<true, kSqrt>(ob, ob.kind & kKindMask, static_cast<int>(ob.kind >> 8), slot_base + slot, o_world, d, best);
   }
 }
 

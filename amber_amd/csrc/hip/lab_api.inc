@@ -337,4 +337,39 @@ int amber_hip_kat_division(int device, int mode, uint32_t n, const float* x, flo
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_sqrt(int device, int mode, uint32_t n, const float* x, float* out) { return Guarded("amber_hip_kat_sqrt", [&]() -> int {
+  if (!x || !out || mode < 0 || mode > 4) return Fail(AMBER_EINVAL, "bad argument");
+  if (n == 0) return AMBER_OK;
+  if (n > 0x3fffffffu) return Fail(AMBER_EINVAL, "too many items for one call");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return Fail(AMBER_ENODEVICE, "no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  const size_t width = mode <= 1 ? 1u : (mode <= 3 ? 3u : 2u);           // floats per item, in and out
+  DevBuf<float> d_x, d_o;
+  HIP_TRY(d_x.alloc(width * n)); HIP_TRY(d_o.alloc(width * n));
+  HIP_TRY(hipMemcpy(d_x.p, x, width * n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kat_sqrt_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, mode, n, d_x.p, d_o.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_o.p, width * n * 4, hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
+
+int amber_hip_kat_sqrt_sweep(int device, uint32_t first_bits, uint64_t count, AmberSqrtSweep* out) { return Guarded("amber_hip_kat_sqrt_sweep", [&]() -> int {
+  if (!out || count == 0 || static_cast<uint64_t>(first_bits) + count > (1ull << 32)) return Fail(AMBER_EINVAL, "bad argument");
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return Fail(AMBER_ENODEVICE, "no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  static_assert(sizeof(SqrtSweepCounters) == sizeof(AmberSqrtSweep), "the kernel's counters are the C record");
+  DevBuf<SqrtSweepCounters> d_c;
+  HIP_TRY(d_c.alloc(1));
+  HIP_TRY(hipMemset(d_c.p, 0, sizeof(SqrtSweepCounters)));
+  const uint64_t blocks = (count + 255u) / 256u;
+  hipLaunchKernelGGL(kat_sqrt_sweep_kernel, dim3(static_cast<uint32_t>(blocks < 8192u ? blocks : 8192u)), dim3(256), 0, 0, first_bits, static_cast<unsigned long long>(count), d_c.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_c.p, sizeof(SqrtSweepCounters), hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
+
 }  // extern "C"

@@ -148,3 +148,64 @@ __global__ void kat_division_kernel(int mode, uint32_t n, const float* x, float*
   out[3ull * i] = q.x; out[3ull * i + 1] = q.y; out[3ull * i + 2] = q.z;
 }
 
+// exact_sqrt.h on the device.  0: x[i] -> sqrt through Sqrt1 (one v_rsq_f32 seed; the wave falls back when a lane is out of range); 1: __builtin_sqrtf;
+// 2 / 3: groups {a, b, c} -> Normalize through the fused form (the root's half-reciprocal seeds the division) and through the plain form;
+// 4: pairs {a, b} -> their roots through Sqrt2 (one guard, one vote).  Whole waves run to the end, as above: the guards are wave votes.
+__global__ void kat_sqrt_kernel(int mode, uint32_t n, const float* x, float* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t k = ClampToLastItem(i, n);
+  if (mode <= 1) {
+    const float v = x[k];
+    const float s = mode == 0 ? exact_sqrt::Sqrt1(v) : __builtin_sqrtf(v);
+    if (i < n) out[i] = s;
+  } else if (mode <= 3) {
+    const V3 v = v3(x[3 * k], x[3 * k + 1], x[3 * k + 2]);
+    const V3 q = mode == 2 ? Normalize<true, SQRT_FUSED>(v) : Normalize<false>(v);
+    if (i < n) { out[3ull * i] = q.x; out[3ull * i + 1] = q.y; out[3ull * i + 2] = q.z; }
+  } else {
+    float sa, sb;
+    exact_sqrt::Sqrt2(x[2 * k], x[2 * k + 1], sa, sb);
+    if (i < n) { out[2ull * i] = sa; out[2ull * i + 1] = sb; }
+  }
+}
+
+// Every bit pattern of [first_bits, first_bits + count): Sqrt1 against __builtin_sqrtf, bit for bit (64 consecutive patterns per wave trip: the
+// bounds of the range are multiples of 64, so a wave is inside or outside as a whole).  For the patterns inside the range also how far
+// v_rsq_f32 lies, in ulp, from the float nearest to 1 / sqrt(x) formed in binary64: the window that the host check of exact_sqrt.h has to cover.
+struct SqrtSweepCounters { unsigned long long mismatches, in_range; uint32_t n_offenders, offenders[8]; int32_t seed_low, seed_high; };
+__global__ void kat_sqrt_sweep_kernel(uint32_t first_bits, unsigned long long count, SqrtSweepCounters* counters) {
+  const unsigned long long stride = static_cast<unsigned long long>(gridDim.x) * blockDim.x;
+  uint32_t mismatches = 0, in_range = 0;
+  int32_t low = 0, high = 0;
+  for (unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const uint32_t bits = first_bits + static_cast<uint32_t>(i);
+    const float x = __uint_as_float(bits);
+    const float fast = exact_sqrt::Sqrt1(x), plain = __builtin_sqrtf(x);
+    if (__float_as_uint(fast) != __float_as_uint(plain)) {
+      ++mismatches;
+      const uint32_t slot = atomicAdd(&counters->n_offenders, 1u);
+      if (slot < 8u) counters->offenders[slot] = bits;
+    }
+    if (exact_sqrt::ExactSqrtSafe(x)) {
+      ++in_range;
+      const float nearest = static_cast<float>(1.0 / __builtin_sqrt(static_cast<double>(x)));
+      const int32_t distance = static_cast<int32_t>(__float_as_uint(__builtin_amdgcn_rsqf(x))) - static_cast<int32_t>(__float_as_uint(nearest));
+      low = distance < low ? distance : low;
+      high = distance > high ? distance : high;
+    }
+  }
+  for (int step = 32; step > 0; step >>= 1) {                          // the wave's extremes and sums in its first lane
+    const int32_t other_low = __shfl_xor(low, step), other_high = __shfl_xor(high, step);
+    low = other_low < low ? other_low : low;
+    high = other_high > high ? other_high : high;
+    mismatches += __shfl_xor(mismatches, step);
+    in_range += __shfl_xor(in_range, step);
+  }
+  if ((threadIdx.x & 63u) == 0u) {
+    if (mismatches) atomicAdd(&counters->mismatches, static_cast<unsigned long long>(mismatches));
+    if (in_range) atomicAdd(&counters->in_range, static_cast<unsigned long long>(in_range));
+    if (low < 0) atomicMin(&counters->seed_low, low);
+    if (high > 0) atomicMax(&counters->seed_high, high);
+  }
+}
+

@@ -16,9 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// The device functions live in eight parts, included here in the order they build on each other (one translation unit: pt_host.hip):
+// The device functions live in nine parts, included here in the order they build on each other (one translation unit: pt_host.hip):
 //   dev_scene.h        diagnostic macros of the stamped builds; the scene layout in HBM (DevObject ... DevScene)
 //   shared_div.h       three quotients by one denominator at one reciprocal (host and device)
+//   exact_sqrt.h       the correctly rounded square root from one v_rsq_f32 seed; Normalize from that seed (host and device)
 //   dev_math.h         Vector3, the XorShift sampler, glibc's sincosf / powf kernels restated
 //   dev_primitives.h   the reference's primitive tests and hit rule; engine LIST
 //   dev_two_phase.h    engine TWO_PHASE: Phase-A filter, Phase-B exact tests, groups of 32 objects
@@ -27,6 +28,7 @@
 //   dev_shading.h      materials, eye ray, light-path start, PathStep / PathShade
 #include "dev_scene.h"
 #include "shared_div.h"
+#include "exact_sqrt.h"
 #include "dev_math.h"
 #include "dev_primitives.h"
 #include "dev_two_phase.h"

@@ -62,6 +62,8 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
   // Normalize's three quotients through one reciprocal (shared_div.h): the same family, for the same kind of reason (the light tracers and
   // <ENGINE_BVH> were not measured with it and keep the plain divisions)
   constexpr bool kDivBasis = kCold && (AMBER_SHARED_DIV_NORMALIZE & 1), kDivHit = kCold && (AMBER_SHARED_DIV_NORMALIZE & 2), kDivEye = kCold && (AMBER_SHARED_DIV_NORMALIZE & 4);
+  // the square roots of the bounce and the eye ray from one v_rsq_f32 seed (exact_sqrt.h; the switch bits: dev_math.h): the same family again
+  constexpr uint32_t kSqrtMask = kCold ? static_cast<uint32_t>(AMBER_EXACT_SQRT) : 0u;
 #define AMBER_ARG(cold, field) (kCold ? AMBER_COLD(cold, field) : a.field)
 #define AMBER_COLD_OPEN() (kCold ? ColdArgs::Open() : ColdArgs{nullptr})
   __shared__ uint4 lds_pool[4][64 * kChunks];                 // [wave][slot * kChunks + chunk]
@@ -195,7 +197,7 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
               rng = XorShiftSeed(AMBER_ARG(cold, hashed_seed), px + py * eye.sensor.w, sample);   // Image index x + y*W (image.h:116-124)
               float ew;
               bool near_edge = false;
-              GenerateEyeRay<kDivEye>(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
+              GenerateEyeRay<kDivEye, SqrtModeOf(kSqrtMask, 4u)>(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
               w = v3(ew, ew, ew);                             // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
               // (the pointer is read here and once more below, not held across the bookkeeping above: the two scalar registers it would occupy
               //  there are what the dividers need, and the loop has none to spare -- tests/test_headline_kernel_spills.py)
@@ -229,12 +231,12 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
         alive = PathStep<false, kEngine, true>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
       } else if (kSig) {
         Bounce b;
-        alive = PathStep<true, kEngine, false, kDivBasis, kDivHit>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
+        alive = PathStep<true, kEngine, false, kDivBasis, kDivHit, kSqrtMask>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
         sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
         if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
         if (!alive) AMBER_ARG(AMBER_COLD_OPEN(), sig)[q] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
       } else {
-        alive = PathStep<false, kEngine, false, kDivBasis, kDivHit>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
+        alive = PathStep<false, kEngine, false, kDivBasis, kDivHit, kSqrtMask>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
       }
       if (!kLight) {
         const bool nz = (__float_as_uint(meas.x) | __float_as_uint(meas.y) | __float_as_uint(meas.z)) != 0u;   // anything but +0 (RGB)

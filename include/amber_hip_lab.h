@@ -69,6 +69,15 @@ int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* 
  * mode 0 = a / d, b / d, c / d through one reciprocal (the wave falls back to mode 1's code when a lane is out of range) ; mode 1 = the plain
  * operator expressions ; mode 2 / 3 = Normalize({a, b, c}) through the shared and the plain form (d is not read) */
 int amber_hip_kat_division(int device, int mode, uint32_t n, const float* x, float* out);
+/* the engine's square root from one v_rsq_f32 seed on device (csrc/hip/exact_sqrt.h).  mode 0 = sqrt(x[i]) in the guarded fast form (the wave
+ * falls back to mode 1's code when a lane is out of range) ; mode 1 = __builtin_sqrtf ; mode 2 / 3 = n groups {a, b, c} -> Normalize through the
+ * fused form (root and quotients from the one seed) and through the plain form ; mode 4 = n pairs {a, b} -> their two roots under one guard */
+int amber_hip_kat_sqrt(int device, int mode, uint32_t n, const float* x, float* out);
+/* mode 0 against mode 1 over the bit patterns [first_bits, first_bits + count), generated on the device (first_bits + count <= 2^32):
+ * how many differ, the first few that do (n_offenders counts them all), how many lie in the fast form's range, and for those the extreme
+ * signed distances in ulp of v_rsq_f32(x) from the float nearest to 1 / sqrt(x) (formed in binary64 on the device) */
+typedef struct { uint64_t mismatches, in_range; uint32_t n_offenders, offenders[8]; int32_t seed_low, seed_high; } AmberSqrtSweep;
+int amber_hip_kat_sqrt_sweep(int device, uint32_t first_bits, uint64_t count, AmberSqrtSweep* out);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

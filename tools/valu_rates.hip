@@ -1,8 +1,10 @@
 // valu_rates.hip -- issue cost (SIMD cycles per wave64 instruction) of the VALU operations the path tracer leans on,
 // measured on the device: every wave runs ITER iterations of UNROLL independent dependency chains of one operation,
 // the grid fills every SIMD with 8 waves, cost = elapsed cycles * SIMDs / wave-instructions.
-//   hipcc --offload-arch=gfx950 -O3 -o /tmp/valu_rates tools/valu_rates.hip && /tmp/valu_rates
+//   hipcc --offload-arch=gfx950 -O3 -I amber_amd/csrc/hip -o /tmp/valu_rates tools/valu_rates.hip && /tmp/valu_rates
 #include <hip/hip_runtime.h>
+
+#include "exact_sqrt.h"      // amber_amd/csrc/hip: the square root from one v_rsq_f32 seed, as the render kernels run it
 
 #include <cstdint>
 #include <cstdio>
@@ -12,12 +14,13 @@
 #define CHAINS 8
 
 enum Op { FMA32, MUL32, ADD32, RCP32, SQRT32, RSQ32, DIV32_IEEE, SQRT32_IEEE, FMA64, ADD64F, MUL64F, DIV64_IEEE, SHL64, XORSHIFT64, XORSHIFT64_32,
-          MULLO32, MULHI32, MAD64_32, CVT_F32_U32, MIN3, CNDMASK, LDS_READ, PK_FMA32, EXP32, LOG32, SIN32, N_OPS };
+          MULLO32, MULHI32, MAD64_32, CVT_F32_U32, MIN3, CNDMASK, LDS_READ, PK_FMA32, EXP32, LOG32, SIN32, SQRT32_SEED, SQRT32_SEED_GUARDED, SQRT32_SEED_PAIR, SQRT32_IEEE_PAIR, N_OPS };
 static const char* kNames[N_OPS] = {"v_fma_f32", "v_mul_f32", "v_add_f32", "v_rcp_f32", "v_sqrt_f32 (approx)", "v_rsq_f32", "a / b (IEEE f32 sequence)",
                                     "sqrtf (IEEE f32 sequence)", "v_fma_f64", "v_add_f64", "v_mul_f64", "a / b (IEEE f64 sequence)", "v_lshlrev_b64",
                                     "xorshift64 step (u64 code)", "xorshift64 step (u32 halves, alignbit)", "v_mul_lo_u32", "v_mul_hi_u32", "v_mad_u64_u32",
                                     "v_cvt_f32_u32", "v_min3_f32", "v_cndmask_b32 (+v_cmp)", "ds_read_b32 (broadcast)", "v_pk_fma_f32 (2 flops/lane)",
-                                    "v_exp_f32", "v_log_f32", "v_sin_f32"};
+                                    "v_exp_f32", "v_log_f32", "v_sin_f32", "sqrt from v_rsq_f32 (exact_sqrt.h, no guard)", "sqrt from v_rsq_f32, guard + wave vote",
+                                    "two such roots, one guard (+ v_add_f32)", "two sqrtf sequences (+ v_add_f32)"};
 
 template <int kOp>
 __global__ void __launch_bounds__(256) rate_kernel(float* out, const float* in, int iters) {
@@ -64,6 +67,10 @@ __global__ void __launch_bounds__(256) rate_kernel(float* out, const float* in, 
       else if (kOp == EXP32) f[c] = __builtin_amdgcn_exp2f(f[c]);
       else if (kOp == LOG32) f[c] = __builtin_amdgcn_logf(f[c]);
       else if (kOp == SIN32) f[c] = __builtin_amdgcn_sinf(f[c]);
+      else if (kOp == SQRT32_SEED) f[c] = exact_sqrt::ExactSqrt(f[c], __builtin_amdgcn_rsqf(f[c]));
+      else if (kOp == SQRT32_SEED_GUARDED) f[c] = exact_sqrt::Sqrt1(f[c]);
+      else if (kOp == SQRT32_SEED_PAIR) { float sa, sb; exact_sqrt::Sqrt2(f[c], f[c] + a, sa, sb); f[c] = sa + sb; }   // (the chain stays between 1 and 6: in range)
+      else if (kOp == SQRT32_IEEE_PAIR) f[c] = __builtin_sqrtf(f[c]) + __builtin_sqrtf(f[c] + a);
     }
   }
   float acc = 0;
@@ -104,7 +111,7 @@ int main() {
 #define RUN(op) ms[op] = Run<op>(d_out, d_in, blocks);
   RUN(FMA32) RUN(MUL32) RUN(ADD32) RUN(RCP32) RUN(SQRT32) RUN(RSQ32) RUN(DIV32_IEEE) RUN(SQRT32_IEEE) RUN(FMA64) RUN(ADD64F) RUN(MUL64F) RUN(DIV64_IEEE)
   RUN(SHL64) RUN(XORSHIFT64) RUN(XORSHIFT64_32) RUN(MULLO32) RUN(MULHI32) RUN(MAD64_32) RUN(CVT_F32_U32) RUN(MIN3) RUN(CNDMASK) RUN(LDS_READ) RUN(PK_FMA32)
-  RUN(EXP32) RUN(LOG32) RUN(SIN32)
+  RUN(EXP32) RUN(LOG32) RUN(SIN32) RUN(SQRT32_SEED) RUN(SQRT32_SEED_GUARDED) RUN(SQRT32_SEED_PAIR) RUN(SQRT32_IEEE_PAIR)
   std::printf("%s: %d CUs, %.2f GHz (nominal); %d waves/SIMD, %d chains x %d iterations per wave\n", prop.gcnArchName, cus, ghz, 8, CHAINS, ITER);
   std::printf("%-44s %10s %26s\n", "operation (one per chain step)", "ms", "SIMD cycles per wave-step");
   for (int op = 0; op < N_OPS; op++) {
