@@ -77,6 +77,16 @@ class UpdateInfo(C.Structure):
                 ("area_before", C.c_float), ("area_after", C.c_float), ("update_ms", C.c_double)]
 
 
+class LtPassInfo(C.Structure):
+    """AmberLtPassInfo: the totals of one amber_hip_lt_render_pass call -- 32 bytes."""
+    _fields_ = [("n_splats", C.c_uint64), ("n_rays", C.c_uint64), ("n_launches", C.c_uint32), ("n_repeats", C.c_uint32),
+                ("longest_run", C.c_uint32), ("pad", C.c_uint32)]
+
+
+LT_SPLAT_CAPACITY0 = 65536   # AMBER_LT_SPLAT_CAPACITY0: records the handle's splat buffer holds before the first growth
+SPLAT_DTYPE = np.dtype([("path", np.uint32), ("sample", np.uint32), ("bounce", np.uint32), ("pixel", np.uint32), ("rgb", np.float32, (3,)), ("pad", np.uint32)])   # AmberSplat
+
+
 class Ray(C.Structure):
     """AmberRay: origin, t_max, dir, pad -- 32 bytes (amber_hip_pt_cast_rays / amber_hip_pt_occluded)."""
     _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("dir", C.c_float * 3), ("pad", C.c_uint32)]
@@ -141,7 +151,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_resolve", "amber_hip_pt_destroy",
     "amber_hip_pt_aov_pass", "amber_hip_pt_aov_clear", "amber_hip_pt_aov_download", "amber_hip_pt_device_aov", "amber_hip_pt_denoise",
     "amber_hip_pt_render_batch", "amber_hip_pt_moments_clear", "amber_hip_pt_moments_download", "amber_hip_pt_device_moments", "amber_hip_pt_denoise_variance",
-    "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range",
+    "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range", "amber_hip_lt_render_pass",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
 ]
@@ -149,7 +159,7 @@ ABI_SYMBOLS = [
 LAB_SYMBOLS = [
     "amber_hip_kat_cast", "amber_hip_kat_sample", "amber_hip_kat_eye", "amber_hip_kat_trace", "amber_hip_kat_math", "amber_hip_kat_signatures", "amber_hip_pt_signatures",
     "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump", "amber_hip_kat_division",
-    "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep",
+    "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep", "amber_hip_kat_lt_accumulate", "amber_hip_kat_lt_stage_ms",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -224,6 +234,8 @@ def load_library() -> C.CDLL:
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
         lib.amber_hip_lt_trace_range.argtypes = [vp, u32, u32, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
+    if hasattr(lib, "amber_hip_lt_render_pass"):
+        lib.amber_hip_lt_render_pass.argtypes = [vp, u32, u32, C.POINTER(LtPassInfo)]
     if hasattr(lib, "amber_hip_kat_cast"):         # the lab build (include/amber_hip_lab.h); the product exports none of these
         lib.amber_hip_kat_cast.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         lib.amber_hip_kat_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
@@ -240,6 +252,9 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "amber_hip_kat_sqrt"):         # the same
             lib.amber_hip_kat_sqrt.argtypes = [i32, i32, u32, vp, vp]
             lib.amber_hip_kat_sqrt_sweep.argtypes = [i32, u32, u64, C.POINTER(SqrtSweep)]
+        if hasattr(lib, "amber_hip_kat_lt_accumulate"):    # the same
+            lib.amber_hip_kat_lt_accumulate.argtypes = [vp, vp, u32]
+            lib.amber_hip_kat_lt_stage_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.amber_host_cornell_box.restype = vp
     lib.amber_host_cornell_box.argtypes = [C.c_float, C.c_float, u32]
     lib.amber_host_scene_import.restype = vp
@@ -728,7 +743,7 @@ class PathTracer:
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),
         sorted (pass, path, bounce).  Returns (structured numpy array of records, ray count)."""
-        dt = np.dtype([("path", np.uint32), ("sample", np.uint32), ("bounce", np.uint32), ("pixel", np.uint32), ("rgb", np.float32, (3,)), ("pad", np.uint32)])
+        dt = SPLAT_DTYPE
         while True:
             out = np.zeros(capacity, dt)
             n, rays = C.c_uint32(), C.c_uint64()
@@ -743,7 +758,32 @@ class PathTracer:
             _check(rc)
             return out[: n.value], rays.value
 
+    def lt_render_pass(self, first_sample: int, n_samples: int) -> dict:
+        """amber_hip_lt_render_pass: the light-tracing passes [first_sample, first_sample + n_samples) into the handle's framebuffer on the device, in the
+        reference's order -- per pass a pass image summed from +0 in (path, bounce) order, pass images added to the framebuffer in pass order, bit for
+        bit what adding lt_trace's records on the host gives (include/amber_hip.h states it; tests/lt_accumulate_reference.py restates it in numpy).
+        The framebuffer is render_pass's and is not cleared; download / resolve / denoise / device_framebuffer work on it as they are, and
+        resolve(n) after n passes is the mean `algorithm="lt"` returns.  Any split of the passes over calls leaves the same bits.  The ray counter
+        grows by lt_trace's ray count and kernel_time() counts the trace launches.  Waits for the stream.  Whole-frame handles only.  Returns
+        AmberLtPassInfo as a dict: n_splats, n_rays, n_launches, n_repeats (launches repeated after the handle's splat buffer,
+        LT_SPLAT_CAPACITY0 records at first, had to grow), longest_run (most records of one pixel in one pass)."""
+        info = LtPassInfo()
+        _check(load_library().amber_hip_lt_render_pass(self._h, first_sample, n_samples, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in LtPassInfo._fields_ if k != "pad"}
+
     # ---- known-answer entry points -----------------------------------------------------------
+    def kat_lt_accumulate(self, records) -> None:
+        """Lab build: lt_render_pass's device path (order by (pixel, pass, path, bounce), ordered sum) on the caller's records -- a structured array of
+        lt_trace's dtype, in any order -- into the framebuffer."""
+        rec = np.ascontiguousarray(records, SPLAT_DTYPE)
+        _check(load_library().amber_hip_kat_lt_accumulate(self._h, rec.ctypes.data if len(rec) else None, len(rec)))
+
+    def kat_lt_stage_ms(self):
+        """Lab build: (sort ms, sum ms) of lt_render_pass's device path since the previous call; the first call switches the timing on."""
+        a, b = C.c_double(), C.c_double()
+        _check(load_library().amber_hip_kat_lt_stage_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def kat_cast(self, origins, dirs):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
         n = len(o)

@@ -489,8 +489,9 @@ const Image<RGB> HipPathTracing::Render(const Scene<RGB>& scene, const Sensor& s
   return image;
 }
 
-// rendering::LightTracing (algorithm_lt.cc:82-163) on the HIP engine: per claimed pass W*H light paths; their splats come
-// back sorted in the reference's accumulation order and are added to a pass image, pass images to the running sum.
+// rendering::LightTracing (algorithm_lt.cc:82-163) on the HIP engine: per claimed pass W*H light paths; their splats are
+// added to a pass image in the reference's accumulation order, pass images to the running sum -- on the device with one
+// device (amber_hip_lt_render_pass), on the host from the sorted record lists with several.
 const Image<RGB> HipLightTracing::Render(const Scene<RGB>& scene, const Sensor& sensor, Context& context) {
   stats_ = HipPathTracingStats();
   const scene::FlatScene fs = scene.Flatten();
@@ -511,6 +512,32 @@ const Image<RGB> HipLightTracing::Render(const Scene<RGB>& scene, const Sensor& 
     Check(amber_hip_pt_create(&fs.flat, &s, &p, &handles[r].h), "amber_hip_pt_create");
   }
   auto sum = sensor.CreateImage<RGB>();
+  if (n_dev == 1) {
+    // One device: amber_hip_lt_render_pass orders and adds the splats on the device -- the loop at the end of this function, operation for operation --
+    // and the sum comes back once.  (Several devices: a light path of any device lands anywhere in the frame, so their lists are merged below.)
+    const uint32_t batch = options_.samples_per_launch ? options_.samples_per_launch : 64;
+    uint32_t first = 0;
+    for (;;) {
+      uint32_t n = 0;
+      while (n < batch && context.Iterate()) n++;
+      if (n == 0) break;
+      Check(amber_hip_lt_render_pass(handles[0].h, first, n, nullptr), "amber_hip_lt_render_pass");
+      stats_.launches++;
+      first += n; stats_.passes += n;
+      if (n < batch) break;
+    }
+    std::vector<float> fb(static_cast<std::size_t>(n_paths) * 3);
+    uint64_t rays = 0;
+    Check(amber_hip_pt_download(handles[0].h, fb.data(), &rays), "amber_hip_pt_download");
+    stats_.rays += rays;
+    for (uint32_t y = 0; y < s.height; y++)
+      for (uint32_t x = 0; x < s.width; x++) {
+        const float* v = &fb[(static_cast<std::size_t>(y) * s.width + x) * 3];
+        sum[Pixel(x, y)] = RGB(v[0], v[1], v[2]);
+      }
+    if (stats_.passes) sum /= RGB(static_cast<real_type>(stats_.passes));
+    return sum;
+  }
   std::vector<std::vector<AmberSplat>> lists(n_dev, std::vector<AmberSplat>(1u << 16));
   std::vector<uint32_t> counts(n_dev, 0);
   std::vector<uint64_t> rays(n_dev, 0);

@@ -303,6 +303,33 @@ int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_s
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_lt_accumulate(amber_hip_pt* h, const AmberSplat* records, uint32_t n) { return Guarded("amber_hip_kat_lt_accumulate", [&]() -> int {
+  if (!h || (n && !records)) return Fail(AMBER_EINVAL, "null argument");
+  if (!WholeFrame(h)) return Fail(AMBER_EINVAL, "amber_hip_kat_lt_accumulate: the handle renders a band or stripes of the frame");
+  if (n > 0x7fffffffu) return Fail(AMBER_EINVAL, "too many records for one call");
+  const uint32_t npx = h->scene.sensor.w * h->scene.sensor.h;
+  for (uint32_t i = 0; i < n; i++) if (records[i].pixel >= npx) return Fail(AMBER_EINVAL, "pixel index out of range");
+  if (n == 0) return AMBER_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  { const int rc = EnsureLtSplats(h, n); if (rc != AMBER_OK) return rc; }
+  static_assert(sizeof(AmberSplat) == sizeof(DevSplat), "splat layouts must agree");
+  HIP_TRY(hipMemcpyAsync(h->d_splats, records, static_cast<size_t>(n) * sizeof(DevSplat), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemsetAsync(h->lt.longest.p, 0, sizeof(unsigned int), h->stream));
+  { const int rc = LtAccumulate(h, n, 32u); if (rc != AMBER_OK) return rc; }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return AMBER_OK;
+}); }
+
+int amber_hip_kat_lt_stage_ms(amber_hip_pt* h, double* sort_ms, double* sum_ms) { return Guarded("amber_hip_kat_lt_stage_ms", [&]() -> int {
+  if (!h) return Fail(AMBER_EINVAL, "null handle");
+  h->lt.stage_timing = true;
+  if (sort_ms) *sort_ms = h->lt.sort_ms;
+  if (sum_ms) *sum_ms = h->lt.sum_ms;
+  h->lt.sort_ms = h->lt.sum_ms = 0;
+  return AMBER_OK;
+}); }
+
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out) { return Guarded("amber_hip_kat_math", [&]() -> int {
   if (!x || !out || mode < 0 || mode > 3) return Fail(AMBER_EINVAL, "bad argument");
   if (n == 0) return AMBER_OK;

@@ -26,6 +26,8 @@
 //                          guide records), one kernel per level (a thread per pixel, 25 taps, polynomial edge stops), then resolve.inc's kernel.
 //   denoise_variance.inc   amber_hip_pt_render_batch's fold and the moments buffer's three companions, and amber_hip_pt_denoise_variance: the same filter with a
 //                          luminance stop scaled by the per-pixel variance of the mean, colour and variance in one 16-byte record per pixel.
+//   lt_accumulate.inc      amber_hip_lt_render_pass: the splat records of a light-tracing launch into the framebuffer in the reference's order -- an index
+//                          permutation sorted by (pixel, pass, path, bounce) with two stable radix sorts, then one thread per pixel run.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -139,6 +141,20 @@ struct BvhBuildScratch {
   DevBuf<double> area;                      // update: {sum of the child boxes' areas, the root's area} of the tree before and after
   DevBuf<uint8_t> retired_nodes;            // a node array a rebuild has outgrown: passes enqueued earlier may still read it, released once the stream has been waited for
 };
+// amber_hip_lt_render_pass (lt_accumulate.inc): the scratch of the two sorts and of the ordered sum, grown on first use, kept, released with the handle
+struct LtAccumBufs {
+  DevBuf<unsigned long long> key[2];        // sort keys, in and out
+  DevBuf<uint32_t> index[2];                // the permutation, in and out
+  DevBuf<float4> value;                     // {rgb, pad} of the records in sorted order
+  DevBuf<uint8_t> temp;                     // rocPRIM's temporary storage
+  DevBuf<unsigned int> longest;             // AmberLtPassInfo.longest_run of the call in flight
+  uint32_t capacity = 0;                    // records d_splats holds for that call: AMBER_LT_SPLAT_CAPACITY0, or what a launch made it grow to
+#ifdef AMBER_LAB
+  bool stage_timing = false;                // amber_hip_kat_lt_stage_ms: sort and sum timed with events (waits for the stream after every accumulation)
+  double sort_ms = 0, sum_ms = 0;
+  Event ev[3];
+#endif
+};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -195,6 +211,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<DevSplat> d_splats;
   DevBuf<unsigned int> d_splat_count;
   uint64_t hashed_seed_lt = 0;
+  LtAccumBufs lt;                           // amber_hip_lt_render_pass
   DevBuf<float> d_partial;                  // pt_bvh_megakernel: per-item sums
   // path-granular accumulation (RenderPassPaths): bitmap, records in arrival order, measurements in path order, ranks
   DevBuf<uint32_t> d_flags;  bool flags_dirty = true;   // dirty: must be cleared before the next launch
@@ -776,6 +793,62 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
   }
   return AMBER_OK;
 }
+
+// The launches of light tracing over the passes [first_sample, first_sample + n_samples) of the light paths [path_begin, path_begin + n_paths): what
+// amber_hip_lt_trace_range and amber_hip_lt_render_pass share.  Each launch leaves its splat records at h->d_splats in arrival order (at most
+// `capacity` of them, read again before every launch: the callback may have grown the buffer) and is waited for; then
+//   after_launch(first, n, produced, rays_before, rays_now, &again)
+// sees the passes of the launch, the records it produced (also beyond the capacity) and the handle's ray counter before the first launch and now.
+// It returns a status other than AMBER_OK to stop, or sets `again` to have exactly this launch repeated.  `timed`: amber_hip_pt_kernel_time counts
+// the launches.  n_samples and n_paths are not zero.
+template <typename F>
+int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t n_paths, bool timed, const uint32_t& capacity, F&& after_launch) {
+  const bool bvh = h->hit_engine == AMBER_ENGINE_BVH;
+  // One launch numbers its work units with 31 bits -- pt_megakernel: (light path, pass) pairs; pt_bvh_megakernel: (light
+  // path, chunk of passes) items -- so a long range of passes is traced in several launches, each a whole number of chunks.
+  // Launches run in pass order and each one's splats are sorted, so the concatenation is in (pass, path, bounce) order.
+  const uint64_t max_units = 0x7fffffffull / n_paths;
+  if (max_units == 0) return Fail(AMBER_EINVAL, "too many light paths for one launch");
+  uint64_t max_samples = bvh ? max_units * AMBER_ACCUM_CHUNK : max_units / AMBER_ACCUM_CHUNK * AMBER_ACCUM_CHUNK;
+  if (max_samples == 0) max_samples = max_units;               // fewer than a chunk fits: any split is valid for light tracing (nothing is summed across launches)
+  unsigned long long rays_before = 0, rays_now = 0;
+  HIP_TRY(hipMemcpyAsync(&rays_before, h->d_rays, sizeof rays_before, hipMemcpyDeviceToHost, h->stream));
+  uint32_t done = 0;
+  while (done < n_samples) {
+    uint32_t n = n_samples - done;
+    if (n > max_samples) n = static_cast<uint32_t>(max_samples);
+    const uint32_t n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
+    const uint64_t n_work = bvh ? static_cast<uint64_t>(n_paths) * n_chunks : static_cast<uint64_t>(n_paths) * n;
+    RenderArgs a = MakeRenderArgs(h, h->hashed_seed_lt, n_paths, first_sample + done, n);
+    a.SetBand(0u, 0u, 0u);                                    // light paths have no band; every divider of the launch is a valid record all the same
+    a.ray_count = h->d_rays; a.next_item = h->d_next;
+    a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = capacity;
+    a.path_offset = path_begin; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
+    const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
+    { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
+    std::pair<Event, Event>* evp = nullptr;
+    if (timed) { const int rc = AcquireEventPair(h, &evp); if (rc != AMBER_OK) return rc; }
+    HIP_TRY(hipMemsetAsync(h->d_splat_count, 0, sizeof(unsigned int), h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
+    if (evp) HIP_TRY(hipEventRecord(evp->first.v, h->stream));
+    WithHitEngine(h->hit_engine, [&](auto engine) -> int {
+      constexpr int kEngine = decltype(engine)::value;
+      if constexpr (kEngine == ENGINE_BVH) hipLaunchKernelGGL((pt_bvh_megakernel<true, 24>), dim3(n_blocks), dim3(256), 0, h->stream, a);   // light tracing on engine BVH: always the item kernel
+      else hipLaunchKernelGGL((pt_megakernel<kEngine, true>), dim3(n_blocks), dim3(256), 0, h->stream, a);
+      return AMBER_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    if (evp) HIP_TRY(hipEventRecord(evp->second.v, h->stream));
+    unsigned int produced = 0;
+    HIP_TRY(hipMemcpyAsync(&produced, h->d_splat_count, sizeof produced, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&rays_now, h->d_rays, sizeof rays_now, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    bool again = false;
+    { const int rc = after_launch(first_sample + done, n, produced, rays_before, rays_now, &again); if (rc != AMBER_OK) return rc; }
+    if (!again) done += n;
+  }
+  return AMBER_OK;
+}
 }  // namespace
 
 #include "ray_query.inc"
@@ -783,6 +856,7 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 #include "aov.inc"
 #include "denoise.inc"
 #include "denoise_variance.inc"
+#include "lt_accumulate.inc"
 
 extern "C" {
 
@@ -900,45 +974,16 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   if (n_samples == 0 || n_paths == 0 || h->scene.n_lights == 0) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
   { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
-  const bool bvh = h->hit_engine == AMBER_ENGINE_BVH;
   const uint32_t dev_capacity = capacity ? capacity : 1u;
   { const int rc = Grow(h, h->d_splats, dev_capacity, "splats"); if (rc != AMBER_OK) return rc; }
   if (!h->d_splat_count) HIP_TRY(h->d_splat_count.alloc(1));
-  // One launch numbers its work units with 31 bits -- pt_megakernel: (light path, pass) pairs; pt_bvh_megakernel: (light
-  // path, chunk of passes) items -- so a long range of passes is traced in several launches, each a whole number of chunks.
-  // Launches run in pass order and each one's splats are sorted, so the concatenation is in (pass, path, bounce) order.
-  const uint64_t max_units = 0x7fffffffull / n_paths;
-  if (max_units == 0) return Fail(AMBER_EINVAL, "too many light paths for one launch");
-  uint64_t max_samples = bvh ? max_units * AMBER_ACCUM_CHUNK : max_units / AMBER_ACCUM_CHUNK * AMBER_ACCUM_CHUNK;
-  if (max_samples == 0) max_samples = max_units;               // fewer than a chunk fits: any split is valid for light tracing (nothing is summed on the device)
   uint64_t total = 0;                                         // splats produced (also beyond the caller's capacity)
-  unsigned long long rays_before = 0, rays_after = 0;
-  HIP_TRY(hipMemcpyAsync(&rays_before, h->d_rays, sizeof rays_before, hipMemcpyDeviceToHost, h->stream));
-  uint32_t done = 0;
-  while (done < n_samples) {
-    uint32_t n = n_samples - done;
-    if (n > max_samples) n = static_cast<uint32_t>(max_samples);
-    const uint32_t n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
-    const uint64_t n_work = bvh ? static_cast<uint64_t>(n_paths) * n_chunks : static_cast<uint64_t>(n_paths) * n;
-    HIP_TRY(hipMemsetAsync(h->d_splat_count, 0, sizeof(unsigned int), h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
-    RenderArgs a = MakeRenderArgs(h, h->hashed_seed_lt, n_paths, first_sample + done, n);
-    a.SetBand(0u, 0u, 0u);                                    // light paths have no band; every divider of the launch is a valid record all the same
-    a.ray_count = h->d_rays; a.next_item = h->d_next;
-    a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = dev_capacity;
-    a.path_offset = path_begin; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
-    const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
-    { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
-    WithHitEngine(h->hit_engine, [&](auto engine) -> int {
-      constexpr int kEngine = decltype(engine)::value;
-      if constexpr (kEngine == ENGINE_BVH) hipLaunchKernelGGL((pt_bvh_megakernel<true, 24>), dim3(n_blocks), dim3(256), 0, h->stream, a);   // light tracing on engine BVH: always the item kernel
-      else hipLaunchKernelGGL((pt_megakernel<kEngine, true>), dim3(n_blocks), dim3(256), 0, h->stream, a);
-      return AMBER_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    unsigned int produced = 0;
-    HIP_TRY(hipMemcpyAsync(&produced, h->d_splat_count, sizeof produced, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+  unsigned long long rays_first = 0, rays_last = 0;
+  bool any = false;
+  const int rc = LtTraceLaunches(h, first_sample, n_samples, path_begin, n_paths, false, dev_capacity,
+                                 [&](uint32_t, uint32_t, unsigned int produced, unsigned long long rays_before, unsigned long long rays_now, bool*) -> int {
+    if (!any) { rays_first = rays_before; any = true; }
+    rays_last = rays_now;
     const uint64_t room = total < capacity ? capacity - total : 0;
     if (produced <= room && produced <= dev_capacity) {
       if (produced) {
@@ -954,14 +999,18 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
       }
     }
     total += produced;                                        // keeps counting: the caller learns the capacity it needs
-    done += n;
-  }
-  HIP_TRY(hipMemcpy(&rays_after, h->d_rays, sizeof rays_after, hipMemcpyDeviceToHost));
-  if (ray_count) *ray_count = rays_after - rays_before;
+    return AMBER_OK;
+  });
+  if (rc != AMBER_OK) return rc;
+  if (ray_count) *ray_count = rays_last - rays_first;
   *n_out = total > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(total);
   if (total > capacity) return Fail(AMBER_ENOMEM, "splat buffer too small: " + std::to_string(total) + " splats produced");
   return AMBER_OK;
 }); }
+
+int amber_hip_lt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, AmberLtPassInfo* info) {
+  return Guarded("amber_hip_lt_render_pass", [&] { return LtRenderPass(h, first_sample, n_samples, info); });
+}
 
 int amber_hip_lt_trace(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, AmberSplat* out, uint32_t capacity,
                        uint32_t* n_out, uint64_t* ray_count) {

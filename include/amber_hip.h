@@ -484,6 +484,39 @@ int amber_hip_lt_trace(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples,
 int amber_hip_lt_trace_range(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end,
                              AmberSplat* out, uint32_t capacity, uint32_t* n_out, uint64_t* ray_count);
 
+/* ---- light tracing into the device framebuffer -----------------------------------------------------------------------------------------------
+ * amber_hip_lt_render_pass accumulates the light-tracing passes [first_sample, first_sample + n_samples) into the handle's framebuffer on the
+ * device, in the reference's order, bit for bit: no record leaves the GPU, and the frame can go on through amber_hip_pt_resolve,
+ * amber_hip_pt_denoise and amber_hip_pt_device_framebuffer like a path-traced one.
+ * Definition.  Every operation is binary32 and rounded alone.  R is the record list amber_hip_lt_trace(h, first_sample, n_samples, ...) returns; it is
+ * already in (pass, path, bounce) order.  For each pass s ascending, P_s starts at +0 everywhere; each record of pass s, in list order, does
+ * P_s[pixel].c = P_s[pixel].c + rgb[c] for c = 0, 1, 2; then fb[p].c = fb[p].c + P_s[p].c for every pixel p that received at least one record in pass s.
+ * All other pixels are untouched.  This equals the reference's `sum += image` (algorithm_lt.cc:112-123), except for a sum somebody uploaded as -0
+ * (which + 0 would turn into +0), and it is exactly the loop at the end of HipLightTracing::Render.
+ * Splitting.  The sum is pass by pass, with no chunking: one call over [a, a + m + n) and the two calls [a, a + m), [a + m, a + m + n) leave the same
+ * bits, at any boundary.  This differs from amber_hip_pt_render_pass, whose sums are formed per accumulation chunk.
+ * Framebuffer and counters.  The framebuffer is the one amber_hip_pt_render_pass writes; it is not cleared.  amber_hip_pt_clear, _download, _resolve,
+ * _denoise and _device_framebuffer work on it as they are; after n passes resolve(n) gives the mean HipLightTracing returns.  The handle's ray counter
+ * grows by exactly the ray_count amber_hip_lt_trace reports for the same range, once.  amber_hip_pt_kernel_time counts the trace launches.
+ * Running out of record slots.  The handle sizes its own splat buffer: it starts at AMBER_LT_SPLAT_CAPACITY0 records and keeps what it grew to.  When
+ * a launch produces more than fits, nothing of that launch reaches the framebuffer, the ray counter is put back to its value before the launch, the
+ * buffer grows to the count the launch reported and the (deterministic) launch is repeated once.  n_repeats counts these.  A call may also split its
+ * passes into smaller launches.
+ * info (may be NULL) reports the totals of the call: records that reached the framebuffer, rays, trace launches (the repeated ones included), repeats;
+ * longest_run is the largest number of records one pixel received in one pass.  It is zeroed first, whatever the call then answers.
+ * Order.  The call is stream-ordered after everything enqueued on the handle (a pass of amber_hip_pt_render_pass whose record buffer was sized from an
+ * estimate is waited for and stands first).  It waits for the stream before it returns, because it reads the record count per launch, as
+ * amber_hip_lt_trace does.
+ * Whole frame only.  A handle with a band or stripes (row_begin / row_end / stripe_period set) answers AMBER_EINVAL: light paths land anywhere in the
+ * frame.  Several devices stay on amber_hip_lt_trace_range plus the host merge.
+ * AMBER_EINVAL, with no effect: a NULL handle; first_sample + n_samples > 2^32 - 1; stale lights (as amber_hip_lt_trace); the lab engine WAVEFRONT; a
+ * banded or striped handle.  AMBER_OK with nothing changed: n_samples == 0, or a scene without lights.
+ * Every engine on which amber_hip_lt_trace works, AMBER_PT_FLAG_BVH_ITEMS and AMBER_PT_FLAG_DEVICE_BUILD included.  Still ABI version 3: a new
+ * function, a new struct, a new constant. */
+#define AMBER_LT_SPLAT_CAPACITY0 65536u   /* records the handle's splat buffer holds before the first growth */
+typedef struct { uint64_t n_splats, n_rays; uint32_t n_launches, n_repeats, longest_run, pad; } AmberLtPassInfo;  /* 32 bytes */
+int amber_hip_lt_render_pass(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples, AmberLtPassInfo* info /* may be NULL */);
+
 const char* amber_hip_last_error(void);
 int         amber_hip_abi_version(void);
 /* Arithmetic of sin / cos / pow the library was built with: AMBER_MATH_GLIBC (the product) executes glibc 2.35's

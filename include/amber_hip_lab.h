@@ -62,6 +62,14 @@ int amber_hip_kat_pixel_masks(amber_hip_pt*, uint32_t* out_mask, uint32_t* out_s
  * prim_capacity entries of the leaf order (leaf slot -> object index); info always receives the sizes and the scalars.  nodes / prims may be NULL. */
 typedef struct { uint32_t n_nodes, n_prims; int32_t root; uint32_t depth; float gmin[3], step[3], reach[3]; } AmberBvhDump;
 int amber_hip_kat_bvh_dump(amber_hip_pt*, uint32_t* nodes, uint32_t node_capacity, uint32_t* prims, uint32_t prim_capacity, AmberBvhDump* info);
+/* amber_hip_lt_render_pass's device path on the caller's records: uploads the n records (host memory) in the given order into the handle's splat
+ * buffer -- growing it as a launch that ran out of slots would -- and runs exactly the ordering and the ordered sum of lt_accumulate.inc into the
+ * framebuffer; `path` is sorted with all its 32 bits.  Real scenes splat rarely (the aperture catches about 1e-4 of the light paths): only this hook
+ * puts the sort and the sum under load.  Synchronous.  AMBER_EINVAL for a pixel >= width * height or a banded handle; n == 0 changes nothing. */
+int amber_hip_kat_lt_accumulate(amber_hip_pt*, const AmberSplat* records /* host */, uint32_t n);
+/* Measurement: the first call switches on the timing of that device path with events (every accumulation then waits for the stream); every call
+ * returns the milliseconds spent ordering (keys, sorts, gather) and summing since the previous call.  Either pointer may be NULL. */
+int amber_hip_kat_lt_stage_ms(amber_hip_pt*, double* sort_ms, double* sum_ms);
 /* the engine's sin/cos/pow on device: mode 0 = sincos(x[i]) -> out[2i], out[2i+1] ; mode 1 = pow(x[2i], x[2i+1]) -> out[i] ;
  * mode 2 / 3 = x[i]^4 / x[i]^5 in binary64 -> out[2i], out[2i+1] = low, high word of the double */
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out);
