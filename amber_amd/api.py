@@ -119,6 +119,17 @@ class DenoiseVarianceParams(C.Structure):
                 ("var_radius", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class TemporalParams(C.Structure):
+    """AmberTemporalParams: levels (0..8), max_history (1..65535) and the four edge-stopping constants of amber_hip_pt_temporal -- 32 bytes."""
+    _fields_ = [("levels", C.c_uint32), ("max_history", C.c_uint32), ("k_normal", C.c_float), ("k_albedo", C.c_float), ("k_depth", C.c_float),
+                ("k_color", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class HistoryPixel(C.Structure):
+    """AmberHistoryPixel: the accumulated colour, the history length and the two running moments of the luminance -- 32 bytes (amber_hip_pt_temporal)."""
+    _fields_ = [("color", C.c_float * 3), ("length", C.c_float), ("m1", C.c_float), ("m2", C.c_float), ("pad", C.c_float * 2)]
+
+
 class BvhDumpInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_prims", C.c_uint32), ("root", C.c_int32), ("depth", C.c_uint32),
                 ("gmin", C.c_float * 3), ("step", C.c_float * 3), ("reach", C.c_float * 3)]
@@ -151,6 +162,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_resolve", "amber_hip_pt_destroy",
     "amber_hip_pt_aov_pass", "amber_hip_pt_aov_clear", "amber_hip_pt_aov_download", "amber_hip_pt_device_aov", "amber_hip_pt_denoise",
     "amber_hip_pt_render_batch", "amber_hip_pt_moments_clear", "amber_hip_pt_moments_download", "amber_hip_pt_device_moments", "amber_hip_pt_denoise_variance",
+    "amber_hip_pt_temporal", "amber_hip_pt_temporal_reset", "amber_hip_pt_history_download", "amber_hip_pt_device_history",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range", "amber_hip_lt_render_pass",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
@@ -230,6 +242,11 @@ def load_library() -> C.CDLL:
         lib.amber_hip_pt_moments_download.argtypes = [vp, vp]
         lib.amber_hip_pt_device_moments.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
         lib.amber_hip_pt_denoise_variance.argtypes = [vp, u32, C.POINTER(DenoiseVarianceParams), u32, vp, u64, u32]
+    if hasattr(lib, "amber_hip_pt_temporal"):
+        lib.amber_hip_pt_temporal.argtypes = [vp, u32, C.POINTER(TemporalParams), u32, vp, u64, u32]
+        lib.amber_hip_pt_temporal_reset.argtypes = [vp]
+        lib.amber_hip_pt_history_download.argtypes = [vp, vp]
+        lib.amber_hip_pt_device_history.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace"):     # absent only in older builds loaded by tools/ab_lib.py
         lib.amber_hip_lt_trace.argtypes = [vp, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_trace_range"):
@@ -678,7 +695,7 @@ class PathTracer:
         return self._filter("denoise", load_library().amber_hip_pt_denoise, n_samples, params, format, mirror, out)
 
     def _filter(self, what: str, entry, n_samples: int, params, format: int, mirror: bool, out):
-        """the output handling denoise() and denoise_variance() share: resolve()'s"""
+        """the output handling denoise(), denoise_variance() and temporal() share: resolve()'s"""
         if format not in (RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8):
             raise AmberError(f"{what}: unknown format {format}")
         rows, width, _ = self.band_shape
@@ -739,6 +756,43 @@ class PathTracer:
         out, torch handling and ORDERING exactly as resolve()."""
         params = DenoiseVarianceParams(levels=levels, k_normal=k_normal, k_albedo=k_albedo, k_depth=k_depth, k_lum=k_lum, var_radius=var_radius)
         return self._filter("denoise_variance", load_library().amber_hip_pt_denoise_variance, n_samples, params, format, mirror, out)
+
+    # ---- reprojected frame history ---------------------------------------------------------------
+    def temporal(self, n_samples: int, levels: int = 5, max_history: int = 32, k_normal: float = 4.0, k_albedo: float = 100.0, k_depth: float = 10.0,
+                 k_color: float = 0.25, format: int = RESOLVE_RGB8, mirror: bool = False, out=None):
+        """amber_hip_pt_temporal: this frame's mean (sums / n_samples) accumulated into the handle's per-pixel history, then `levels` levels of
+        denoise()'s filter on the accumulated colour (0: none), then resolve's output stage.  The frame loop: update_lens / update_objects, clear(),
+        render_pass or lt_render_pass of this frame's samples (a fresh first_sample per frame), aov_clear(), aov_pass, temporal(n_samples).  The
+        previous history is reprojected through the previous lens (bilinear, four taps; an unchanged lens reprojects every pixel to itself, so a
+        static camera is an exact running mean) and a tap is accepted only where the previous guide passes denoise()'s normal, albedo and depth
+        stops; a pixel without an accepted tap starts again.  The history length is capped at max_history, from where the blend is exponential.  A
+        fixed sequence of binary32 operations (include/amber_hip.h states it; tests/temporal_reference.py restates it in numpy).  The filtered colour
+        is not fed back.  The defaults are starting points nobody has tuned (EXPERIMENTS.md has what was measured).  A band reprojects and filters
+        within itself; a striped handle is refused.  Leaves the framebuffer, the AOV buffer, the moments, the ray counter and kernel_time() alone.
+
+        out, torch handling and ORDERING exactly as resolve()."""
+        params = TemporalParams(levels=levels, max_history=max_history, k_normal=k_normal, k_albedo=k_albedo, k_depth=k_depth, k_color=k_color)
+        return self._filter("temporal", load_library().amber_hip_pt_temporal, n_samples, params, format, mirror, out)
+
+    def temporal_reset(self) -> None:
+        """amber_hip_pt_temporal_reset: empties the history (asynchronous, on the handle's stream): the next temporal() is a first call.  clear(),
+        aov_clear(), update_objects() and update_lens() leave the history alone."""
+        _check(load_library().amber_hip_pt_temporal_reset(self._h))
+
+    def history_download(self) -> np.ndarray:
+        """amber_hip_pt_history_download: a float32 array of shape band_shape[:2] + (8,) in AmberHistoryPixel's order -- colour r g b, length, m1, m2,
+        two pads -- rows as download() lays them out.  A history never used, or emptied, reads as zeros.  Synchronises."""
+        rows, width, _ = self.band_shape
+        out = np.zeros((rows, width, 8), np.float32)
+        _check(load_library().amber_hip_pt_history_download(self._h, out.ctypes.data))
+        return out
+
+    def device_history(self):
+        """amber_hip_pt_device_history: (device pointer, number of band pixels) of the CURRENT history buffer, 8 float32 per pixel; the next temporal()
+        makes the other buffer current, so ask again after every call.  ORDERING as device_aov."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(load_library().amber_hip_pt_device_history(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

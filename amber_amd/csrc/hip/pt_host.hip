@@ -26,6 +26,8 @@
 //                          guide records), one kernel per level (a thread per pixel, 25 taps, polynomial edge stops), then resolve.inc's kernel.
 //   denoise_variance.inc   amber_hip_pt_render_batch's fold and the moments buffer's three companions, and amber_hip_pt_denoise_variance: the same filter with a
 //                          luminance stop scaled by the per-pixel variance of the mean, colour and variance in one 16-byte record per pixel.
+//   temporal.inc           amber_hip_pt_temporal and its three companions: a per-pixel history of the mean image -- one kernel reprojects the previous history
+//                          through the previous lens, validates it against the previous guide records, blends and writes; then denoise.inc's levels.
 //   lt_accumulate.inc      amber_hip_lt_render_pass: the splat records of a light-tracing launch into the framebuffer in the reference's order -- an index
 //                          permutation sorted by (pixel, pass, path, bounce) with two stable radix sorts, then one thread per pixel run.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
@@ -202,6 +204,11 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<float4> d_denoise_guide;           // ... and the guide records {a.xyz, z} {n.xyz, rz}, two float4 per band pixel
   DevBuf<float4> d_dv_record[2];            // amber_hip_pt_denoise_variance (denoise_variance.inc): {c.rgb, var} per band pixel, the levels' input and output, grown on first use
   DevBuf<float4> d_moments;                 // amber_hip_pt_render_batch / _moments_*: {m1, m2, batches, pad} per band pixel, allocated and zeroed by the first call that needs it
+  DevBuf<float4> d_history[2];              // amber_hip_pt_temporal (temporal.inc): {color.rgb, length} {m1, m2, 0, 0} per band pixel, used ping-pong, allocated and zeroed by the first call that needs them
+  DevBuf<float4> d_history_guide[2];        // ... and the guide records of the frame each history was written with
+  uint32_t history_cur = 0;                 // the pair that holds the current history
+  bool history_empty = true;                // nothing to reproject: set at create and by amber_hip_pt_temporal_reset
+  DevLens history_lens{};                   // the handle's lens as the call that wrote the current history saw it
   DevBuf<float> d_batch;                    // amber_hip_pt_render_batch: the sums of the batch in flight, 3 floats per band pixel, grown on first use
   DevBuf<float> d_fb;
   float* accum_target = nullptr;            // where reduce_flagged_kernel and reduce_partials_kernel add a pass: d_fb, except inside amber_hip_pt_render_batch (d_batch)
@@ -856,6 +863,7 @@ int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 #include "aov.inc"
 #include "denoise.inc"
 #include "denoise_variance.inc"
+#include "temporal.inc"
 #include "lt_accumulate.inc"
 
 extern "C" {
@@ -1110,6 +1118,22 @@ int amber_hip_pt_device_aov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
 
 int amber_hip_pt_denoise(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
   return Guarded("amber_hip_pt_denoise", [&] { return Denoise(h, n_samples, params, format, out, out_bytes, flags); });
+}
+
+int amber_hip_pt_temporal(amber_hip_pt* h, uint32_t n_samples, const AmberTemporalParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
+  return Guarded("amber_hip_pt_temporal", [&] { return Temporal(h, n_samples, params, format, out, out_bytes, flags); });
+}
+
+int amber_hip_pt_temporal_reset(amber_hip_pt* h) {
+  return Guarded("amber_hip_pt_temporal_reset", [&] { return TemporalReset(h); });
+}
+
+int amber_hip_pt_history_download(amber_hip_pt* h, AmberHistoryPixel* out) {
+  return Guarded("amber_hip_pt_history_download", [&] { return HistoryDownload(h, out); });
+}
+
+int amber_hip_pt_device_history(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
+  return Guarded("amber_hip_pt_device_history", [&] { return DeviceHistory(h, dptr, n_pixels); });
 }
 
 int amber_hip_pt_moments_clear(amber_hip_pt* h) {

@@ -395,7 +395,7 @@ int  amber_hip_pt_device_aov(amber_hip_pt*, void** dptr, uint64_t* n_pixels);
  * if no amber_hip_pt_aov_* call has: all-zero guides, only the colour stop acts) and writes only out and buffers of its own (two colour buffers
  * and a guide buffer, 56 bytes per band pixel, grown on first use, released by destroy): the framebuffer, the AOV buffer, the ray counter and
  * amber_hip_pt_kernel_time are untouched.  Every engine, both builds.
- * Not part of it: albedo demodulation (materials are per object, so albedo edges are object edges), temporal accumulation, variance guidance, a halo
+ * Not part of it: albedo demodulation (materials are per object, so albedo edges are object edges), temporal accumulation (amber_hip_pt_temporal keeps the frames), variance guidance, a halo
  * across ranks (a band filters within itself: a tap outside the band is a tap outside the image), the command line and the C++ adapter.
  * AMBER_EINVAL, with a message and the handle left working: a NULL handle or params, n_samples == 0, levels outside 1..8, a negative, NaN or infinite
  * k_*, non-zero reserved, an unknown format or flag, any other out_bytes, out == NULL with a non-empty band, a misaligned device pointer, a striped
@@ -460,11 +460,85 @@ int  amber_hip_pt_device_moments(amber_hip_pt*, void** dptr, uint64_t* n_pixels)
  * buffer (each of the latter two allocated and zeroed here if nobody has touched it) and never writes them, the ray counter or
  * amber_hip_pt_kernel_time.  It writes out and buffers of its own: two record buffers of 16 bytes per band pixel, and amber_hip_pt_denoise's first
  * colour buffer and guide buffer (a later amber_hip_pt_denoise fills them again: its bytes do not change).  Every engine, both builds.
- * Not part of it: firefly clamping, temporal reprojection, albedo demodulation, a halo across ranks, the command line and the C++ adapter.
+ * Not part of it: firefly clamping, temporal reprojection (amber_hip_pt_temporal reprojects the frames, with amber_hip_pt_denoise's colour stop), albedo demodulation, a halo across ranks, the command line and the C++ adapter.
  * AMBER_EINVAL as amber_hip_pt_denoise gives it (k_lum in k_color's place), plus var_radius > 3 and non-zero reserved.  An empty band: AMBER_OK. */
 typedef struct { uint32_t levels; float k_normal; float k_albedo; float k_depth; float k_lum; uint32_t var_radius; uint32_t reserved[2]; } AmberDenoiseVarianceParams;  /* 32 bytes */
 int  amber_hip_pt_denoise_variance(amber_hip_pt*, uint32_t n_samples, const AmberDenoiseVarianceParams* params,
                                    uint32_t format, void* out, uint64_t out_bytes, uint32_t flags);
+/* Reprojected frame history: what an interactive caller, who moves the camera with amber_hip_pt_update_lens and renders a few samples per frame, needs
+ * to keep the last dozen frames instead of starting every frame from nothing.  The handle keeps a per-pixel history; amber_hip_pt_temporal does, per
+ * frame, "accumulate into the history, optionally filter, output".  Still ABI version 3: four new functions and two structs.  The call does not read the
+ * scene: every engine, both builds, path-traced and light-traced frames alike.
+ * The frame loop:  update_lens / update_objects;  clear;  render_pass or lt_render_pass of this frame's samples (a fresh first_sample per frame);
+ * aov_clear, aov_pass;  temporal(n_samples, ...).
+ * Every operation is binary32 and rounded alone.  fb, A, the band, sq, clamp0 and the guide stops tn, ta, tz are amber_hip_pt_denoise's; lum is
+ * amber_hip_pt_denoise_variance's.  Band pixel p = (px, ly) has local row ly and global row py = row_begin + ly; W, H, wf = (float)W, hf = (float)H,
+ * sw = scene_width and sh = scene_height are the sensor's.  M . v is the matrix-vector product with each row (m0 * v.x + m1 * v.y) + m2 * v.z; dot(v, v)
+ * is (v.x * v.x + v.y * v.y) + v.z * v.z; sqrt and / are correctly rounded.
+ *   1. this frame     c = fb / (float)n_samples.  cov = A.coverage; the guide record (a, z)(n, rz) is exactly steps 1 and 2 of amber_hip_pt_denoise.
+ *                     Y = lum(c).
+ *   2. state          two history buffers and two guide buffers, used ping-pong (history: AmberHistoryPixel; guide: the record of step 1 as the call
+ *                     that wrote the history formed it), 2 * (32 + 32) bytes per band pixel, allocated and zeroed by the first of these calls that needs them (temporal_reset never does),
+ *                     released by destroy; a snapshot of the lens of the previous call; an "empty" flag, set at create and by temporal_reset.  Primed
+ *                     names (H', guide', lens') are the previous call's.  "guide'(q) had coverage" means rz'(q) > 0: the record keeps no coverage word,
+ *                     and a hit at a mean depth that is not positive counts as none.
+ *   3. reprojection   While the history is empty nothing is reprojected: every pixel is reset (step 4).  Otherwise up to four taps q_k with weights b_k and
+ *                     an expected depth d:
+ *      lens unchanged (every value of AmberFlatThinLens the handle was given last -- origin, both matrices, focus_distance, sensor_distance, p_area,
+ *                     n_blades, kind -- has the bits of the snapshot's): one tap q_0 = p with b_0 = 1, and d = z_p.  (Deliberate: a static camera is an
+ *                     exact running mean, not a bilinear tap with a weight one ulp off 1.)
+ *      lens changed   through the chief ray, which the pinhole and the thin lens share.  A pixel with cov > 0:
+ *                       uvx = ((float)px + 0.5f) / wf,  uvy = ((float)py + 0.5f) / hf
+ *                       s = ((uvx - 0.5f) * sw, (uvy - 0.5f) * sh, sensor_distance)
+ *                       g = global_ . (-s),  dir = g / sqrt(dot(g, g))  per component
+ *                       P = origin + z_p * dir  per component
+ *                       v = P - origin',  dl = local_' . v,  t = sensor_distance' / dl.z,  pt = t * dl
+ *                       fx = (pt.x / sw + 0.5f) * wf - 0.5f,  fy = (pt.y / sh + 0.5f) * hf - 0.5f,  d = sqrt(dot(v, v))
+ *                     valid iff dl.z < 0 and fx > -1 and fx < wf and fy > -1 and fy < hf (each comparison false for a NaN); nothing is converted to an
+ *                     integer before this test.  ix = floor(fx), ax = fx - ix, ux = 1 - ax, and iy, ay, uy alike.  The taps, in this order:
+ *                     (ix, iy) with b = ux * uy, (ix + 1, iy) with ax * uy, (ix, iy + 1) with ux * ay, (ix + 1, iy + 1) with ax * ay; iy counts
+ *                     global rows.  An invalid reprojection has no taps.
+ *      accepting      a tap of a pixel with cov > 0 is accepted iff it lies inside the band (a band reprojects within itself, as it filters within
+ *                     itself), H'(q).length > 0, guide'(q) had coverage, and (tn * ta) * tz > 0 with the stops taken between this pixel's guide and
+ *                     guide'(q), d in place of z_p and 1 / d in place of rz_p, and this call's k_normal, k_albedo, k_depth.  Acceptance is binary: the
+ *                     stops do not scale the weight.
+ *      cov == 0       (background; any cov that is not > 0.)  Lens unchanged: the one tap is accepted iff H'(p).length > 0 and guide'(p) had no coverage
+ *                     either.  Lens changed: no taps.
+ *      sums           S_r, S_g, S_b, S_len, S_m1, S_m2 and B start at 0; each accepted tap, in tap order, adds b * H'(q).field and b.  The history is
+ *                     KEPT iff B > 0.01f; then h.field = S_field / B.  Otherwise the pixel is RESET.
+ *   4. blend          kept:  N = min(h.length + 1, (float)max_history) (the comparison (h.length + 1 < m) ? h.length + 1 : m), alpha = 1 / N, and
+ *                     x = h.x + (x_now - h.x) * alpha for the three channels (x_now = c), for m1 (x_now = Y) and for m2 (x_now = Y * Y).
+ *                     reset: N = 1, color = c, m1 = Y, m2 = Y * Y.
+ *                     {color, N, m1, m2, 0, 0} and this frame's guide record go into the other pair of buffers, which becomes the current one; the
+ *                     lens is snapshot and the empty flag cleared.  m2 - m1 * m1 is then the temporal variance of the luminance; this call only keeps it.
+ *   5. filter, output levels == 0: the accumulated colour goes through amber_hip_pt_resolve's output stage.  levels >= 1: steps 3 to 5 of
+ *                     amber_hip_pt_denoise run `levels` times with c_0 = the accumulated colour, this frame's guide record, k_color and its x 4
+ *                     schedule; c_levels goes through the output stage.
+ * format, out, out_bytes and flags mean exactly what they mean for amber_hip_pt_denoise, with the same checks in the same order, and so do the stream
+ * order, the wait for an estimated pass, the striped-handle and empty-band rules.  The call reads the framebuffer and the AOV buffer (allocated and
+ * zeroed here if nobody has touched it: every pixel is background) and never writes them, the moments, the ray counter or amber_hip_pt_kernel_time; it
+ * writes out, the history and amber_hip_pt_denoise's two colour buffers (a later amber_hip_pt_denoise fills its buffers again: its bytes do not
+ * change).  amber_hip_pt_clear, _aov_clear, _update_objects and _update_lens leave the history alone: a moved object is caught by the depth and normal
+ * stops, not by motion vectors.
+ *   temporal_reset    empties the history: the next call is a first call, and until then the history reads as zeros.  Asynchronous, stream-ordered.
+ *   history_download  copies the current history to the host in amber_hip_pt_download's layout; synchronises.  A history never used reads as zeros.
+ *   device_history    the device pointer of the CURRENT history buffer and the band's pixel count, as amber_hip_pt_device_aov; the next
+ *                     amber_hip_pt_temporal makes the other buffer current, so ask again after every call.  n_pixels may be NULL.
+ * Not part of it: feeding the filtered colour back into the history (the history holds unfiltered means only), variance-guided levels on the temporal
+ * moments, motion of moved objects, a halo across ranks, the command line and the C++ adapter.
+ * AMBER_EINVAL, with the handle and the history left as they were: a NULL handle or params (or out, or dptr, for the companions), n_samples == 0,
+ * levels > 8, max_history outside 1 .. 65535, a negative, NaN or infinite k_*, non-zero reserved, and amber_hip_pt_denoise's checks of format, flags,
+ * out_bytes, out and a striped handle.  An empty band: AMBER_OK.  After any other error nothing of the call has reached the history. */
+typedef struct { uint32_t levels;        /* 0 .. 8: a-trous levels after accumulation, 0 = none */
+                 uint32_t max_history;   /* 1 .. 65535: cap on the history length N */
+                 float k_normal, k_albedo, k_depth, k_color;
+                 uint32_t reserved[2]; } AmberTemporalParams;                    /* 32 bytes */
+typedef struct { float color[3]; float length; float m1, m2; float pad[2]; } AmberHistoryPixel;  /* 32 bytes: two float4 */
+int  amber_hip_pt_temporal(amber_hip_pt*, uint32_t n_samples, const AmberTemporalParams* params,
+                           uint32_t format, void* out, uint64_t out_bytes, uint32_t flags);
+int  amber_hip_pt_temporal_reset(amber_hip_pt*);
+int  amber_hip_pt_history_download(amber_hip_pt*, AmberHistoryPixel* out);      /* band layout of amber_hip_pt_download; synchronises */
+int  amber_hip_pt_device_history(amber_hip_pt*, void** dptr, uint64_t* n_pixels);
 /* Per-launch timing of the dominant kernel, measured with hipEvents on the handle's stream:
  * number of timed launches since create/clear and their total duration. */
 int  amber_hip_pt_kernel_time(amber_hip_pt*, uint32_t* n_launches, double* total_ms);
