@@ -626,25 +626,20 @@ class PathTracer:
         with the answer).  out = a contiguous torch tensor on the handle's device, of that dtype and exactly that many elements: zero-copy and
         asynchronous on the handle's stream, `out` is returned.  ORDERING as cast_rays: under `with torch.cuda.stream(ExternalStream(pt.stream()))`
         nothing is waited for; otherwise torch's current stream is waited for before the call and the handle's stream after it."""
-        if format not in (RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8):
-            raise AmberError(f"resolve: unknown format {format}")
+        return self._filter("resolve", load_library().amber_hip_pt_resolve, n_samples, None, format, mirror, out)
+
+    def _band_download(self, entry, channels: int) -> np.ndarray:
+        """what aov_download(), moments_download() and history_download() share: `channels` float32 per band pixel, rows as download() lays them out"""
         rows, width, _ = self.band_shape
-        channels, flags = (4 if format == RESOLVE_RGBA8 else 3), (RESOLVE_MIRROR_X if mirror else 0)
-        lib = load_library()
-        if out is None:
-            res = np.empty((rows, width, channels), np.float32 if format == RESOLVE_MEAN_F32 else np.uint8)
-            _check(lib.amber_hip_pt_resolve(self._h, n_samples, format, res.ctypes.data, res.nbytes, flags | RESOLVE_HOST))
-            return res
-        if not self._is_torch(out):
-            raise AmberError("resolve: out must be None or a torch tensor on the handle's device")
-        import torch
-        dtype = torch.float32 if format == RESOLVE_MEAN_F32 else torch.uint8
-        if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or out.numel() != rows * width * channels:
-            raise AmberError(f"resolve: out must be a contiguous {dtype} tensor of {rows} x {width} x {channels} elements on the handle's device")
-        same = self._torch_enter(torch, out.device)
-        _check(lib.amber_hip_pt_resolve(self._h, n_samples, format, out.data_ptr(), out.numel() * out.element_size(), flags))
-        self._torch_leave(same)
+        out = np.zeros((rows, width, channels), np.float32)
+        _check(entry(self._h, out.ctypes.data))
         return out
+
+    def _band_pointer(self, entry):
+        """what device_aov(), device_moments() and device_history() share: (device pointer, number of band pixels)"""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(entry(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     # ---- first-hit AOVs -----------------------------------------------------------------------
     def aov_pass(self, first_sample: int, n_samples: int) -> None:
@@ -664,19 +659,14 @@ class PathTracer:
         """amber_hip_pt_aov_download: a float32 array of shape band_shape[:2] + (8,) in AmberAovPixel's order -- albedo r g b, depth, normal x y z,
         coverage -- rows as download() lays them out.  Raw SUMS: divide by the sample count, or by coverage for a mean over the samples that hit.
         Synchronises."""
-        rows, width, _ = self.band_shape
-        out = np.zeros((rows, width, 8), np.float32)
-        _check(load_library().amber_hip_pt_aov_download(self._h, out.ctypes.data))
-        return out
+        return self._band_download(load_library().amber_hip_pt_aov_download, 8)
 
     def device_aov(self):
         """amber_hip_pt_device_aov: (device pointer, number of band pixels) of the AOV buffer, 8 float32 per pixel, for zero-copy consumers
         (torch.from_dlpack / a __cuda_array_interface__ wrapper, a denoiser).  ORDERING: the engine works on the handle's stream, not on torch's
         current stream.  Wrap the handle's stream -- torch.cuda.ExternalStream(pt.stream()) -- and read the buffer under `with torch.cuda.stream(...)`
         of it, so that aov_pass and the reader are ordered on one stream; otherwise call sync() first."""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(load_library().amber_hip_pt_device_aov(self._h, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._band_pointer(load_library().amber_hip_pt_device_aov)
 
     def denoise(self, n_samples: int, levels: int = 5, k_normal: float = 4.0, k_albedo: float = 100.0, k_depth: float = 10.0, k_color: float = 0.25,
                 format: int = RESOLVE_RGB8, mirror: bool = False, out=None):
@@ -695,14 +685,15 @@ class PathTracer:
         return self._filter("denoise", load_library().amber_hip_pt_denoise, n_samples, params, format, mirror, out)
 
     def _filter(self, what: str, entry, n_samples: int, params, format: int, mirror: bool, out):
-        """the output handling denoise(), denoise_variance() and temporal() share: resolve()'s"""
+        """the output handling resolve() (params is None: its entry point takes none), denoise(), denoise_variance() and temporal() share"""
         if format not in (RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8):
             raise AmberError(f"{what}: unknown format {format}")
         rows, width, _ = self.band_shape
         channels, flags = (4 if format == RESOLVE_RGBA8 else 3), (RESOLVE_MIRROR_X if mirror else 0)
+        head = (self._h, n_samples) if params is None else (self._h, n_samples, C.byref(params))
         if out is None:
             res = np.empty((rows, width, channels), np.float32 if format == RESOLVE_MEAN_F32 else np.uint8)
-            _check(entry(self._h, n_samples, C.byref(params), format, res.ctypes.data, res.nbytes, flags | RESOLVE_HOST))
+            _check(entry(*head, format, res.ctypes.data, res.nbytes, flags | RESOLVE_HOST))
             return res
         if not self._is_torch(out):
             raise AmberError(f"{what}: out must be None or a torch tensor on the handle's device")
@@ -711,7 +702,7 @@ class PathTracer:
         if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or out.numel() != rows * width * channels:
             raise AmberError(f"{what}: out must be a contiguous {dtype} tensor of {rows} x {width} x {channels} elements on the handle's device")
         same = self._torch_enter(torch, out.device)
-        _check(entry(self._h, n_samples, C.byref(params), format, out.data_ptr(), out.numel() * out.element_size(), flags))
+        _check(entry(*head, format, out.data_ptr(), out.numel() * out.element_size(), flags))
         self._torch_leave(same)
         return out
 
@@ -732,16 +723,11 @@ class PathTracer:
     def moments_download(self) -> np.ndarray:
         """amber_hip_pt_moments_download: a float32 array of shape band_shape[:2] + (4,) in AmberMomentsPixel's order -- m1, m2, batches, pad -- rows
         as download() lays them out.  Synchronises."""
-        rows, width, _ = self.band_shape
-        out = np.zeros((rows, width, 4), np.float32)
-        _check(load_library().amber_hip_pt_moments_download(self._h, out.ctypes.data))
-        return out
+        return self._band_download(load_library().amber_hip_pt_moments_download, 4)
 
     def device_moments(self):
         """amber_hip_pt_device_moments: (device pointer, number of band pixels) of the moments buffer, 4 float32 per pixel.  ORDERING as device_aov."""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(load_library().amber_hip_pt_device_moments(self._h, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._band_pointer(load_library().amber_hip_pt_device_moments)
 
     def denoise_variance(self, n_samples: int, levels: int = 5, k_normal: float = 4.0, k_albedo: float = 100.0, k_depth: float = 10.0, k_lum: float = 16.0,
                          var_radius: int = 3, format: int = RESOLVE_RGB8, mirror: bool = False, out=None):
@@ -782,17 +768,12 @@ class PathTracer:
     def history_download(self) -> np.ndarray:
         """amber_hip_pt_history_download: a float32 array of shape band_shape[:2] + (8,) in AmberHistoryPixel's order -- colour r g b, length, m1, m2,
         two pads -- rows as download() lays them out.  A history never used, or emptied, reads as zeros.  Synchronises."""
-        rows, width, _ = self.band_shape
-        out = np.zeros((rows, width, 8), np.float32)
-        _check(load_library().amber_hip_pt_history_download(self._h, out.ctypes.data))
-        return out
+        return self._band_download(load_library().amber_hip_pt_history_download, 8)
 
     def device_history(self):
         """amber_hip_pt_device_history: (device pointer, number of band pixels) of the CURRENT history buffer, 8 float32 per pixel; the next temporal()
         makes the other buffer current, so ask again after every call.  ORDERING as device_aov."""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(load_library().amber_hip_pt_device_history(self._h, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._band_pointer(load_library().amber_hip_pt_device_history)
 
     def lt_trace(self, first_sample: int, n_samples: int, capacity: int = 1 << 16, paths=None):
         """Light tracing (algorithm_lt.cc): splats of W*H light paths per pass (or of the light paths [paths[0], paths[1])),

@@ -1,6 +1,7 @@
 // aov.inc -- amber_hip_pt_aov_pass / _aov_clear / _aov_download / amber_hip_pt_device_aov: the first-hit guide images of the band (albedo, depth,
 // shading normal, coverage), summed over samples on the device.  Part of the one translation unit pt_host.hip; the device functions are the render
-// kernels': GenerateEyeRay with the render kernels' seed, draw order and origin_slot, ClosestHit<kEngine>, ResolveHit.
+// kernels': GenerateEyeRay with the render kernels' seed, draw order and origin_slot, ClosestHit<kEngine>, ResolveHit.  The buffer and its clear,
+// download and device pointer are a BandBuf of image_stage.inc; this file holds the kernel and the pass.
 //
 //   aov_kernel<kEngine>   ONE THREAD PER BAND PIXEL, looping over the samples first_sample .. first_sample + n_samples - 1 in this order.  The eight
 //                         sums (AmberAovPixel: two float4) live in registers: read once, one binary32 addition per component and hit, written once.
@@ -68,15 +69,9 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? AMBER_QUERY_WAVES
 
 static_assert(sizeof(AmberAovPixel) == 32, "an AOV pixel is two float4");
 
-// The AOV buffer of the band: allocated and zeroed (on the handle's stream) by the first of the four entry points; nothing for an empty band.
-int EnsureAov(amber_hip_pt* h, const char* name) {
-  const uint64_t n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
-  if (n_pixels == 0 || h->d_aov) return AMBER_OK;
-  const hipError_t e = h->d_aov.alloc(static_cast<size_t>(n_pixels) * 2u);
-  if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string(name) + ": hipMalloc(AOV buffer): " + hipGetErrorString(e));
-  HIP_TRY(hipMemsetAsync(h->d_aov, 0, static_cast<size_t>(n_pixels) * sizeof(AmberAovPixel), h->stream));
-  return AMBER_OK;
-}
+// The AOV buffer of the band, zeroed by the first of the four entry points (and of the filters) that needs it: image_stage.inc's BandBuf
+BandBuf AovBuf(amber_hip_pt* h) { return {{&h->img.aov}, 1, 2u, "AOV buffer"}; }
+int EnsureAov(amber_hip_pt* h, const char* name) { return EnsureBand(h, AovBuf(h), name); }
 
 int AovPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
   const char* name = "amber_hip_pt_aov_pass";
@@ -87,11 +82,11 @@ int AovPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
   return Fail(AMBER_EINVAL, std::string(name) + ": not part of an AMBER_BVH_WIDE measurement build");
 #endif
   HIP_TRY(hipSetDevice(h->device));
-  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   if (n_pixels == 0) return AMBER_OK;                                         // empty band
-  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(EnsureAov(h, name));
   AovArgs a{};
-  a.scene = h->scene; a.aov = h->d_aov; a.hashed_seed = h->hashed_seed;
+  a.scene = h->scene; a.aov = h->img.aov; a.hashed_seed = h->hashed_seed;
   a.n_pixels = n_pixels; a.first_sample = first_sample; a.n_samples = n_samples;
   a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period);
   return LaunchPerItem(h, n_pixels, [&](auto engine, uint32_t n_blocks) {
@@ -99,35 +94,8 @@ int AovPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
   });
 }
 
-int AovClear(amber_hip_pt* h) {
-  const char* name = "amber_hip_pt_aov_clear";
-  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const bool fresh = !h->d_aov;
-  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
-  if (!fresh) HIP_TRY(hipMemsetAsync(h->d_aov, 0, static_cast<size_t>(h->local_rows) * h->scene.sensor.w * sizeof(AmberAovPixel), h->stream));
-  return AMBER_OK;
-}
-
-int AovDownload(amber_hip_pt* h, AmberAovPixel* out) {
-  const char* name = "amber_hip_pt_aov_download";
-  if (!h || !out) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or output pointer");
-  HIP_TRY(hipSetDevice(h->device));
-  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
-  const size_t n_pixels = static_cast<size_t>(h->local_rows) * h->scene.sensor.w;
-  if (n_pixels) HIP_TRY(hipMemcpyAsync(out, h->d_aov, n_pixels * sizeof(AmberAovPixel), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return AMBER_OK;
-}
-
-int DeviceAov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
-  const char* name = "amber_hip_pt_device_aov";
-  if (!h || !dptr) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or pointer");
-  HIP_TRY(hipSetDevice(h->device));
-  { const int rc = EnsureAov(h, name); if (rc != AMBER_OK) return rc; }
-  *dptr = h->d_aov;                                                           // (null for an empty band)
-  if (n_pixels) *n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
-  return AMBER_OK;
-}
+int AovClear(amber_hip_pt* h) { return BandClear(h, AovBuf, "amber_hip_pt_aov_clear"); }
+int AovDownload(amber_hip_pt* h, AmberAovPixel* out) { return BandDownload(h, AovBuf, out, "amber_hip_pt_aov_download"); }
+int DeviceAov(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) { return BandPointer(h, AovBuf, dptr, n_pixels, "amber_hip_pt_device_aov"); }
 
 }  // namespace

@@ -224,7 +224,7 @@ int UpdateScene(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlat
   if (count == 0) {                                            // nothing changes; the figures are those of the tree in use
     if (!h->area_known) {
       HIP_TRY(hipSetDevice(h->device));
-      { const int rc = QueueArea(h, 0); if (rc != AMBER_OK) return rc; }
+      AMBER_TRY(QueueArea(h, 0));
       HIP_TRY(hipStreamSynchronize(h->stream));
       h->tree_area = AreaOf(h, 0); h->area_known = true;
     }
@@ -246,11 +246,11 @@ int UpdateScene(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlat
   }
 
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }   // a pass enqueued before this call renders the old scene, also when the host has to repeat it
+  AMBER_TRY(ResolvePending(h));   // a pass enqueued before this call renders the old scene, also when the host has to repeat it
   const hipStream_t st = h->stream;
   BvhBuildScratch& s = h->update_scratch;
   const bool measure_before = !h->area_known;                  // a handle's first update: the figure comes with the bounds' read-back
-  if (measure_before) { const int rc = QueueArea(h, 0); if (rc != AMBER_OK) return rc; }
+  if (measure_before) AMBER_TRY(QueueArea(h, 0));
   const size_t object_bytes = static_cast<size_t>(n) * sizeof(DevObject);
   HIP_TRY(h->objects_alt.need(object_bytes)); HIP_TRY(s.staged.need(count)); HIP_TRY(s.red.need(1)); HIP_TRY(s.boxes.need(n));
   DevObject* fresh = reinterpret_cast<DevObject*>(h->objects_alt.p);
@@ -330,7 +330,7 @@ int UpdateScene(amber_hip_pt* h, uint32_t first, uint32_t count, const AmberFlat
     std::memcpy(h->aperture_rect, lens_change->aperture_rect, sizeof h->aperture_rect);
     h->blade_records.assign(objects, objects + count);
   }
-  { const int rc = QueueArea(h, 1); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(QueueArea(h, 1));
   HIP_TRY(hipStreamSynchronize(st));                           // the second and last wait: the caller's records have been read, update_ms covers the work
   s.retired_nodes.reset();
   h->tree_area = AreaOf(h, 1); h->area_known = true;

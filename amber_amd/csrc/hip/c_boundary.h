@@ -9,7 +9,7 @@
 //   anything else                       -> AMBER_EHIP,   no message
 // A handler's message is a std::string too: it is formed inside a try of its own, and left empty if that throws.  No handler throws.
 // Needs the error codes only -- no HIP -- so that tests/c_boundary_main.cc checks it as a stand-alone host program; HIP_TRY is a macro and
-// names the HIP runtime only where it is used.
+// names the HIP runtime only where it is used.  AMBER_TRY is its counterpart for the library's own int-returning calls.
 #pragma once
 
 #include <exception>
@@ -29,6 +29,12 @@ int Fail(int code, const std::string& msg) { g_last_error = msg; return code; }
     hipError_t e_ = (expr);                                                                        \
     if (e_ != hipSuccess)                                                                          \
       return Fail(AMBER_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
+  } while (0)
+// The same for a call of the library's own that has set the message: its code, unless it is AMBER_OK, is what the caller returns
+#define AMBER_TRY(expr)                                                                            \
+  do {                                                                                             \
+    const int rc_ = (expr);                                                                        \
+    if (rc_ != AMBER_OK) return rc_;                                                               \
   } while (0)
 
 int FailCaught(int code, const char* name, const char* what) noexcept {   // a handler's message, "<name>: <what>"

@@ -2,7 +2,9 @@
 // image, guided by the AOV buffer, between accumulation and the output stage.  The edge-stopping weights are compactly supported polynomials,
 // clamp0(1 - d * k), not exponentials: the filter is a fixed sequence of binary32 operations, each rounded alone (-ffp-contract=off), and the
 // contract of include/amber_hip.h states it operation by operation (its numpy restatement: tests/denoise_reference.py).  Part of the one translation
-// unit pt_host.hip; the output stage is resolve.inc's kernel on the last colour buffer with n = 1 (x / 1.0f == x).
+// unit pt_host.hip; the output stage is resolve.inc's kernel on the last colour buffer with n = 1 (x / 1.0f == x).  From image_stage.inc: the
+// stops' device helpers and the guide record, the checks of the parameters and of the output arguments, the output tail.  LaunchDenoiseLevels
+// here runs the levels for amber_hip_pt_temporal too.
 //
 //   denoise_prepare_kernel   one thread per band pixel: reads the sums (12 bytes) and the AOV sums (32 bytes), writes c0 = sum / n (12 bytes) and the
 //                            guide record {a.xyz, z}{n.xyz, rz} (32 bytes): the divisions by coverage and the reciprocal of the depth are done once
@@ -16,7 +18,7 @@
 // A level reads every 44-byte pixel record 25 times and writes 12 bytes: a cache-bandwidth problem (L1 / L2), which HBM sees about once per level.
 // No LDS, no scratch, no atomics, no tuning surface: 256 threads per workgroup, registers left to the compiler (129 VGPR: 3 waves per SIMD).
 // Buffers of the handle, grown on first use: two colour buffers used ping-pong (level i reads [i & 1], writes [(i + 1) & 1]) and the guide buffer;
-// AMBER_RESOLVE_HOST stages through resolve's d_resolve_out.
+// AMBER_RESOLVE_HOST stages through the output tail's buffer.
 namespace {
 
 struct DenoiseLevelArgs {
@@ -35,28 +37,9 @@ __global__ void __launch_bounds__(256) denoise_prepare_kernel(const float* __res
   const float* s = fb + 3u * i;
   float* c = c0 + 3u * i;
   c[0] = s[0] / n; c[1] = s[1] / n; c[2] = s[2] / n;
-  const float4 a0 = aov[2u * i], a1 = aov[2u * i + 1u];
-  const float cov = a1.w;
-  float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
-  if (cov > 0.f) {
-    g0.x = a0.x / cov; g0.y = a0.y / cov; g0.z = a0.z / cov; g0.w = a0.w / cov;
-    g1.x = a1.x / cov; g1.y = a1.y / cov; g1.z = a1.z / cov;
-  }
-  g1.w = g0.w > 0.f ? 1.0f / g0.w : 0.f;
+  float4 g0, g1;
+  GuideRecord(aov[2u * i], aov[2u * i + 1u], g0, g1);
   guide[2u * i] = g0; guide[2u * i + 1u] = g1;
-}
-
-__device__ __forceinline__ float DenoiseSq(float u0, float u1, float u2, float v0, float v1, float v2) {
-  const float d0 = u0 - v0, d1 = u1 - v1, d2 = u2 - v2;
-  return (d0 * d0 + d1 * d1) + d2 * d2;
-}
-__device__ __forceinline__ float DenoiseClamp0(float t) { return t > 0.f ? t : 0.f; }     // 0 for a NaN t
-// (tn * ta) * tz: the three guide stops of a tap q seen from p, guide records {a.xyz, z} {n.xyz, rz} (denoise_variance.inc's kernels use it too)
-__device__ __forceinline__ float DenoiseGuideStop(const float4& pa, const float4& pn, const float4& qa, const float4& qn, float k_normal, float k_albedo, float k_depth) {
-  const float tn = DenoiseClamp0(1.0f - DenoiseSq(pn.x, pn.y, pn.z, qn.x, qn.y, qn.z) * k_normal);
-  const float ta = DenoiseClamp0(1.0f - DenoiseSq(pa.x, pa.y, pa.z, qa.x, qa.y, qa.z) * k_albedo);
-  const float tz = DenoiseClamp0(1.0f - (fabsf(pa.w - qa.w) * pn.w) * k_depth);
-  return (tn * ta) * tz;
 }
 
 // the grid is one-dimensional (a band of one column may have 2^30 tile rows): tile b is tile column b % blocks_x of tile row b / blocks_x
@@ -106,81 +89,39 @@ __global__ void __launch_bounds__(256) denoise_level_kernel(const DenoiseLevelAr
 
 static_assert(sizeof(AmberDenoiseParams) == 32, "AmberDenoiseParams is 32 bytes");
 
-// What the output arguments of amber_hip_pt_denoise and amber_hip_pt_denoise_variance (denoise_variance.inc) must satisfy, checked in this order, and
-// what the launches need of them.  AMBER_OK with n_pixels == 0: an empty band, nothing to do.
-struct DenoiseOutput { uint32_t width, rows, blocks_x; uint64_t n_pixels, want, n_tiles; bool host, mirror; };
+// What every filter does once its arguments have passed: the device, the sums (as resolve: a pass that may have to be repeated must stand) and the AOV buffer
+int BeginFilter(amber_hip_pt* h, const std::string& name) {
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->pending && !h->pending_checked) AMBER_TRY(ResolvePending(h));
+  return EnsureAov(h, name.c_str());
+}
 
-int CheckDenoiseOutput(const amber_hip_pt* h, const std::string& name, uint32_t format, const void* out, uint64_t out_bytes, uint32_t flags, DenoiseOutput& o) {
-  o = DenoiseOutput{};
-  if (format > AMBER_RESOLVE_RGBA8) return Fail(AMBER_EINVAL, name + ": unknown format " + std::to_string(format));
-  if (flags & ~static_cast<uint32_t>(AMBER_RESOLVE_HOST | AMBER_RESOLVE_MIRROR_X)) return Fail(AMBER_EINVAL, name + ": unknown flag bits");
-  if (h->stripe_period != 0u) return Fail(AMBER_EINVAL, name + ": a striped handle's local rows are not neighbours in the frame; filter a contiguous band");
-  const uint32_t width = h->scene.sensor.w, rows = h->local_rows;
-  const uint64_t n_pixels = static_cast<uint64_t>(rows) * width;
-  const uint64_t want = n_pixels * kResolveBytesPerPixel[format];
-  if (out_bytes != want)
-    return Fail(AMBER_EINVAL, name + ": out_bytes is " + std::to_string(out_bytes) + ", the band takes exactly " + std::to_string(want) + " (" + std::to_string(rows) +
-                                  " rows of " + std::to_string(width) + " pixels, " + std::to_string(kResolveBytesPerPixel[format]) + " bytes each)");
-  if (n_pixels == 0) return AMBER_OK;                                         // empty band
-  if (!out) return Fail(AMBER_EINVAL, name + ": null output pointer");
-  const bool host = (flags & AMBER_RESOLVE_HOST) != 0u;
-  if (!host && format != AMBER_RESOLVE_RGB8 && reinterpret_cast<uintptr_t>(out) % 4u != 0u)
-    return Fail(AMBER_EINVAL, name + ": a device pointer for MEAN_F32 or RGBA8 must be 4-byte aligned");
-  const uint32_t blocks_x = (width + 63u) / 64u;
-  const uint64_t n_tiles = static_cast<uint64_t>(blocks_x) * ((rows + 3u) / 4u);
-  if (n_tiles > 0x7fffffffull) return Fail(AMBER_EINVAL, name + ": band too large for one launch");
-  o.width = width; o.rows = rows; o.blocks_x = blocks_x; o.n_pixels = n_pixels; o.want = want; o.n_tiles = n_tiles;
-  o.host = host; o.mirror = (flags & AMBER_RESOLVE_MIRROR_X) != 0u;
-  return AMBER_OK;
+// The levels 0 .. levels - 1 over the colour in the first colour buffer (both grown by the caller), ping-pong; the buffer that holds the last level's output
+const float* LaunchDenoiseLevels(amber_hip_pt* h, const BandOutput& o, const float4* guide, uint32_t levels, float k_normal, float k_albedo, float k_depth, float k_color) {
+  DenoiseLevelArgs a{};
+  a.guide = guide; a.width = o.width; a.rows = o.rows; a.blocks_x = o.blocks_x;
+  a.k_normal = k_normal; a.k_albedo = k_albedo; a.k_depth = k_depth; a.k_color = k_color;
+  for (uint32_t i = 0; i < levels; i++) {
+    a.cin = h->img.denoise_color[i & 1u]; a.cout = h->img.denoise_color[(i + 1u) & 1u]; a.step = 1 << i;
+    hipLaunchKernelGGL(denoise_level_kernel, dim3(static_cast<uint32_t>(o.n_tiles)), dim3(256), 0, h->stream, a);
+    a.k_color = a.k_color * 4.0f;                                             // kc_{i+1} = kc_i * 4
+  }
+  return h->img.denoise_color[levels & 1u];
 }
 
 int Denoise(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
   const std::string name = "amber_hip_pt_denoise";
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (!params) return Fail(AMBER_EINVAL, name + ": null params");
-  if (n_samples == 0) return Fail(AMBER_EINVAL, name + ": n_samples is 0");
-  if (params->levels < 1u || params->levels > 8u) return Fail(AMBER_EINVAL, name + ": levels is " + std::to_string(params->levels) + ", not 1 .. 8");
-  const float k[4] = {params->k_normal, params->k_albedo, params->k_depth, params->k_color};
-  const char* k_name[4] = {"k_normal", "k_albedo", "k_depth", "k_color"};
-  for (int i = 0; i < 4; i++)
-    if (!(k[i] >= 0.f) || std::isinf(k[i])) return Fail(AMBER_EINVAL, name + ": " + k_name[i] + " is negative, NaN or infinite");
-  if (params->reserved[0] | params->reserved[1] | params->reserved[2]) return Fail(AMBER_EINVAL, name + ": reserved fields must be 0");
-  DenoiseOutput o{};
-  { const int rc = CheckDenoiseOutput(h, name, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
-  const uint32_t width = o.width, rows = o.rows, blocks_x = o.blocks_x;
-  const uint64_t n_pixels = o.n_pixels, want = o.want, n_tiles = o.n_tiles;
-  const bool host = o.host;
-  HIP_TRY(hipSetDevice(h->device));
-  if (h->pending && !h->pending_checked) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }      // as resolve: the sums must stand
-  { const int rc = EnsureAov(h, name.c_str()); if (rc != AMBER_OK) return rc; }
-  for (DevBuf<float>& c : h->d_denoise_color) { const int rc = Grow(h, c, static_cast<size_t>(n_pixels) * 3u, "denoise colour"); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_denoise_guide, static_cast<size_t>(n_pixels) * 2u, "denoise guide"); if (rc != AMBER_OK) return rc; }
-  void* d_out = out;
-  if (host) {
-    const int rc = Grow(h, h->d_resolve_out, want, "resolve staging"); if (rc != AMBER_OK) return rc;
-    d_out = h->d_resolve_out.p;
-  }
-  hipLaunchKernelGGL(denoise_prepare_kernel, dim3(static_cast<uint32_t>((n_pixels + 255u) / 256u)), dim3(256), 0, h->stream, h->d_fb.p, h->d_aov.p,
-                     h->d_denoise_color[0].p, h->d_denoise_guide.p, n_pixels, static_cast<float>(n_samples));
-  DenoiseLevelArgs a{};
-  a.guide = h->d_denoise_guide; a.width = width; a.rows = rows; a.blocks_x = blocks_x;
-  a.k_normal = params->k_normal; a.k_albedo = params->k_albedo; a.k_depth = params->k_depth; a.k_color = params->k_color;
-  for (uint32_t i = 0; i < params->levels; i++) {
-    a.cin = h->d_denoise_color[i & 1u]; a.cout = h->d_denoise_color[(i + 1u) & 1u]; a.step = 1 << i;
-    hipLaunchKernelGGL(denoise_level_kernel, dim3(static_cast<uint32_t>(n_tiles)), dim3(256), 0, h->stream, a);
-    a.k_color = a.k_color * 4.0f;                                             // kc_{i+1} = kc_i * 4
-  }
-  const float* filtered = h->d_denoise_color[params->levels & 1u];
-  const bool mirror = (flags & AMBER_RESOLVE_MIRROR_X) != 0u;
-  if (format == AMBER_RESOLVE_MEAN_F32) LaunchResolve<AMBER_RESOLVE_MEAN_F32>(h, filtered, mirror, d_out, n_pixels, 1.0f);
-  else if (format == AMBER_RESOLVE_RGB8) LaunchResolve<AMBER_RESOLVE_RGB8>(h, filtered, mirror, d_out, n_pixels, 1.0f);
-  else LaunchResolve<AMBER_RESOLVE_RGBA8>(h, filtered, mirror, d_out, n_pixels, 1.0f);
-  HIP_TRY(hipGetLastError());
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, want, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return AMBER_OK;
+  AMBER_TRY(CheckFilterParams(name, h, params, n_samples, 1u, &AmberDenoiseParams::k_color, "k_color"));
+  BandOutput o{};
+  { const int rc = CheckBandOutput(h, name, true, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
+  AMBER_TRY(BeginFilter(h, name));
+  ImageStageBufs& img = h->img;
+  for (DevBuf<float>& c : img.denoise_color) AMBER_TRY(Grow(h, c, static_cast<size_t>(o.n_pixels) * 3u, "denoise colour"));
+  AMBER_TRY(Grow(h, img.denoise_guide, static_cast<size_t>(o.n_pixels) * 2u, "denoise guide"));
+  hipLaunchKernelGGL(denoise_prepare_kernel, dim3(static_cast<uint32_t>((o.n_pixels + 255u) / 256u)), dim3(256), 0, h->stream, h->d_fb.p, img.aov.p,
+                     img.denoise_color[0].p, img.denoise_guide.p, o.n_pixels, static_cast<float>(n_samples));
+  const float* filtered = LaunchDenoiseLevels(h, o, img.denoise_guide, params->levels, params->k_normal, params->k_albedo, params->k_depth, params->k_color);
+  return WriteBandOutput(h, o, format, filtered, 1.0f, out);
 }
 
 }  // namespace

@@ -2,7 +2,8 @@
 // and amber_hip_pt_denoise_variance: the a-trous filter of denoise.inc with its colour stop replaced by a luminance stop that is scaled by a per-pixel
 // estimate of the variance of the mean, which is filtered along with the colour (Schied et al., HPG 2017, without the temporal part).  A fixed sequence of
 // binary32 operations, each rounded alone; the contract of include/amber_hip.h states it (its numpy restatement: tests/denoise_variance_reference.py).
-// Part of the one translation unit pt_host.hip.  The guide buffer, its prepare kernel and the three guide stops (DenoiseGuideStop) are denoise.inc's own.
+// Part of the one translation unit pt_host.hip.  The guide buffer and its prepare kernel are denoise.inc's own; the three guide stops (DenoiseGuideStop),
+// the luminance, the moments' BandBuf, the checks of the parameters and of the output arguments and the output tail are image_stage.inc's.
 //
 //   moments_fold_kernel     one thread per band pixel, after a batch has been rendered into the handle's batch buffer instead of the framebuffer (the
 //                           accumulation target of pt_host.hip): fb = fb + B, and the luminance of B / n into the pixel's {m1, m2, batches, pad}
@@ -21,8 +22,6 @@ namespace {
 
 static_assert(sizeof(AmberMomentsPixel) == 16, "a moments pixel is one float4");
 static_assert(sizeof(AmberDenoiseVarianceParams) == 32, "AmberDenoiseVarianceParams is 32 bytes");
-
-__device__ __forceinline__ float DvLuminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
 __global__ void __launch_bounds__(256) moments_fold_kernel(float* __restrict__ fb, const float* __restrict__ batch, float4* __restrict__ moments, uint64_t n_pixels,
                                                            float n) {
@@ -142,108 +141,51 @@ __global__ void __launch_bounds__(256) dv_level_kernel(const DvArgs a) {
   else a.out[p] = make_float4(cr, cg, cb, sv / (sw * sw));
 }
 
-// The moments buffer of the band: allocated and zeroed (on the handle's stream) by the first call that needs it; nothing for an empty band.
-int EnsureMoments(amber_hip_pt* h, const char* name) {
-  const uint64_t n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
-  if (n_pixels == 0 || h->d_moments) return AMBER_OK;
-  const hipError_t e = h->d_moments.alloc(static_cast<size_t>(n_pixels));
-  if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string(name) + ": hipMalloc(moments buffer): " + hipGetErrorString(e));
-  HIP_TRY(hipMemsetAsync(h->d_moments, 0, static_cast<size_t>(n_pixels) * sizeof(AmberMomentsPixel), h->stream));
-  return AMBER_OK;
-}
+// The moments buffer of the band, zeroed by the first call that needs it: image_stage.inc's BandBuf
+BandBuf MomentsBuf(amber_hip_pt* h) { return {{&h->img.moments}, 1, 1u, "moments buffer"}; }
+int EnsureMoments(amber_hip_pt* h, const char* name) { return EnsureBand(h, MomentsBuf(h), name); }
+int MomentsClear(amber_hip_pt* h) { return BandClear(h, MomentsBuf, "amber_hip_pt_moments_clear"); }
+int MomentsDownload(amber_hip_pt* h, AmberMomentsPixel* out) { return BandDownload(h, MomentsBuf, out, "amber_hip_pt_moments_download"); }
+int DeviceMoments(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) { return BandPointer(h, MomentsBuf, dptr, n_pixels, "amber_hip_pt_device_moments"); }
 
-// After a batch has been rendered into h->d_batch: the framebuffer and the moments take it.
+// After a batch has been rendered into the handle's batch buffer: the framebuffer and the moments take it.
 int FoldBatch(amber_hip_pt* h, uint32_t n_samples) {
-  const uint64_t n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
-  hipLaunchKernelGGL(moments_fold_kernel, dim3(static_cast<uint32_t>((n_pixels + 255u) / 256u)), dim3(256), 0, h->stream, h->d_fb.p, h->d_batch.p, h->d_moments.p, n_pixels,
+  const uint64_t n_pixels = BandPixels(h);
+  hipLaunchKernelGGL(moments_fold_kernel, dim3(static_cast<uint32_t>((n_pixels + 255u) / 256u)), dim3(256), 0, h->stream, h->d_fb.p, h->img.batch.p, h->img.moments.p, n_pixels,
                      static_cast<float>(n_samples));
   HIP_TRY(hipGetLastError());
-  return AMBER_OK;
-}
-
-int MomentsClear(amber_hip_pt* h) {
-  const char* name = "amber_hip_pt_moments_clear";
-  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const bool fresh = !h->d_moments;
-  { const int rc = EnsureMoments(h, name); if (rc != AMBER_OK) return rc; }
-  if (!fresh) HIP_TRY(hipMemsetAsync(h->d_moments, 0, static_cast<size_t>(h->local_rows) * h->scene.sensor.w * sizeof(AmberMomentsPixel), h->stream));
-  return AMBER_OK;
-}
-
-int MomentsDownload(amber_hip_pt* h, AmberMomentsPixel* out) {
-  const char* name = "amber_hip_pt_moments_download";
-  if (!h || !out) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or output pointer");
-  HIP_TRY(hipSetDevice(h->device));
-  { const int rc = EnsureMoments(h, name); if (rc != AMBER_OK) return rc; }
-  const size_t n_pixels = static_cast<size_t>(h->local_rows) * h->scene.sensor.w;
-  if (n_pixels) HIP_TRY(hipMemcpyAsync(out, h->d_moments, n_pixels * sizeof(AmberMomentsPixel), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return AMBER_OK;
-}
-
-int DeviceMoments(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
-  const char* name = "amber_hip_pt_device_moments";
-  if (!h || !dptr) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or pointer");
-  HIP_TRY(hipSetDevice(h->device));
-  { const int rc = EnsureMoments(h, name); if (rc != AMBER_OK) return rc; }
-  *dptr = h->d_moments;                                                       // (null for an empty band)
-  if (n_pixels) *n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
   return AMBER_OK;
 }
 
 int DenoiseVariance(amber_hip_pt* h, uint32_t n_samples, const AmberDenoiseVarianceParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
   const std::string name = "amber_hip_pt_denoise_variance";
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (!params) return Fail(AMBER_EINVAL, name + ": null params");
-  if (n_samples == 0) return Fail(AMBER_EINVAL, name + ": n_samples is 0");
-  if (params->levels < 1u || params->levels > 8u) return Fail(AMBER_EINVAL, name + ": levels is " + std::to_string(params->levels) + ", not 1 .. 8");
-  const float k[4] = {params->k_normal, params->k_albedo, params->k_depth, params->k_lum};
-  const char* k_name[4] = {"k_normal", "k_albedo", "k_depth", "k_lum"};
-  for (int i = 0; i < 4; i++)
-    if (!(k[i] >= 0.f) || std::isinf(k[i])) return Fail(AMBER_EINVAL, name + ": " + k_name[i] + " is negative, NaN or infinite");
-  if (params->var_radius > 3u) return Fail(AMBER_EINVAL, name + ": var_radius is " + std::to_string(params->var_radius) + ", not 0 .. 3");
-  if (params->reserved[0] | params->reserved[1]) return Fail(AMBER_EINVAL, name + ": reserved fields must be 0");
-  DenoiseOutput o{};
-  { const int rc = CheckDenoiseOutput(h, name, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
+  const FilterExtra<AmberDenoiseVarianceParams> radius{&AmberDenoiseVarianceParams::var_radius, "var_radius", 0u, 3u, false};
+  AMBER_TRY(CheckFilterParams(name, h, params, n_samples, 1u, &AmberDenoiseVarianceParams::k_lum, "k_lum", &radius));
+  BandOutput o{};
+  { const int rc = CheckBandOutput(h, name, true, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
   const uint64_t n_pixels = o.n_pixels;
-  HIP_TRY(hipSetDevice(h->device));
-  if (h->pending && !h->pending_checked) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }      // as resolve: the sums must stand
-  { const int rc = EnsureAov(h, name.c_str()); if (rc != AMBER_OK) return rc; }
-  { const int rc = EnsureMoments(h, name.c_str()); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_denoise_color[0], static_cast<size_t>(n_pixels) * 3u, "denoise colour"); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_denoise_guide, static_cast<size_t>(n_pixels) * 2u, "denoise guide"); if (rc != AMBER_OK) return rc; }
-  for (DevBuf<float4>& r : h->d_dv_record) { const int rc = Grow(h, r, static_cast<size_t>(n_pixels), "denoise records"); if (rc != AMBER_OK) return rc; }
-  void* d_out = out;
-  if (o.host) {
-    const int rc = Grow(h, h->d_resolve_out, o.want, "resolve staging"); if (rc != AMBER_OK) return rc;
-    d_out = h->d_resolve_out.p;
-  }
+  AMBER_TRY(BeginFilter(h, name));
+  AMBER_TRY(EnsureMoments(h, name.c_str()));
+  ImageStageBufs& img = h->img;
+  AMBER_TRY(Grow(h, img.denoise_color[0], static_cast<size_t>(n_pixels) * 3u, "denoise colour"));
+  AMBER_TRY(Grow(h, img.denoise_guide, static_cast<size_t>(n_pixels) * 2u, "denoise guide"));
+  for (DevBuf<float4>& r : img.dv_record) AMBER_TRY(Grow(h, r, static_cast<size_t>(n_pixels), "denoise records"));
   const dim3 per_pixel(static_cast<uint32_t>((n_pixels + 255u) / 256u)), tiles(static_cast<uint32_t>(o.n_tiles));
-  hipLaunchKernelGGL(denoise_prepare_kernel, per_pixel, dim3(256), 0, h->stream, h->d_fb.p, h->d_aov.p, h->d_denoise_color[0].p, h->d_denoise_guide.p, n_pixels,
+  hipLaunchKernelGGL(denoise_prepare_kernel, per_pixel, dim3(256), 0, h->stream, h->d_fb.p, img.aov.p, img.denoise_color[0].p, img.denoise_guide.p, n_pixels,
                      static_cast<float>(n_samples));
-  hipLaunchKernelGGL(dv_moments_kernel, per_pixel, dim3(256), 0, h->stream, h->d_moments.p, h->d_dv_record[1].p, n_pixels);
+  hipLaunchKernelGGL(dv_moments_kernel, per_pixel, dim3(256), 0, h->stream, img.moments.p, img.dv_record[1].p, n_pixels);
   DvArgs a{};
-  a.guide = h->d_denoise_guide; a.width = o.width; a.rows = o.rows; a.blocks_x = o.blocks_x;
+  a.guide = img.denoise_guide; a.width = o.width; a.rows = o.rows; a.blocks_x = o.blocks_x;
   a.k_normal = params->k_normal; a.k_albedo = params->k_albedo; a.k_depth = params->k_depth; a.k_lum = params->k_lum;
-  a.in = h->d_dv_record[1]; a.out = h->d_dv_record[0]; a.c0 = h->d_denoise_color[0]; a.step = static_cast<int32_t>(params->var_radius);
+  a.in = img.dv_record[1]; a.out = img.dv_record[0]; a.c0 = img.denoise_color[0]; a.step = static_cast<int32_t>(params->var_radius);
   hipLaunchKernelGGL(dv_variance_kernel, tiles, dim3(256), 0, h->stream, a);
   a.c0 = nullptr;
   for (uint32_t i = 0; i < params->levels; i++) {
-    a.in = h->d_dv_record[i & 1u]; a.out = h->d_dv_record[(i + 1u) & 1u]; a.step = 1 << i;
-    a.out3 = i + 1u == params->levels ? h->d_denoise_color[0].p : nullptr;
+    a.in = img.dv_record[i & 1u]; a.out = img.dv_record[(i + 1u) & 1u]; a.step = 1 << i;
+    a.out3 = i + 1u == params->levels ? img.denoise_color[0].p : nullptr;
     hipLaunchKernelGGL(dv_level_kernel, tiles, dim3(256), 0, h->stream, a);
   }
-  const float* filtered = h->d_denoise_color[0];
-  if (format == AMBER_RESOLVE_MEAN_F32) LaunchResolve<AMBER_RESOLVE_MEAN_F32>(h, filtered, o.mirror, d_out, n_pixels, 1.0f);
-  else if (format == AMBER_RESOLVE_RGB8) LaunchResolve<AMBER_RESOLVE_RGB8>(h, filtered, o.mirror, d_out, n_pixels, 1.0f);
-  else LaunchResolve<AMBER_RESOLVE_RGBA8>(h, filtered, o.mirror, d_out, n_pixels, 1.0f);
-  HIP_TRY(hipGetLastError());
-  if (o.host) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, o.want, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return AMBER_OK;
+  return WriteBandOutput(h, o, format, img.denoise_color[0], 1.0f, out);
 }
 
 }  // namespace

@@ -12,7 +12,7 @@ void WithKatEngine(const amber_hip_pt* h, F&& f) {
 // Engine WAVEFRONT host loop: batches of <= max_chunks accumulation chunks; per batch generate, then bounce launches
 // until the live-ray count read back from the device is zero, then the ordered reduction into the framebuffer.
 int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
-  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   const uint64_t kMaxPaths = 1ull << 28;                       // 268 M paths: 2 x 14 GB of queues + 3.2 GB of measurements
   uint64_t max_chunks = kMaxPaths / (static_cast<uint64_t>(n_pixels) * AMBER_ACCUM_CHUNK);
   if (max_chunks == 0) return Fail(AMBER_EINVAL, "band too large for the wavefront engine");
@@ -28,7 +28,7 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
     const size_t q_len = shard_capacity * AMBER_WF_SHARDS;
     const size_t n_counts = static_cast<size_t>(kMaxBounces + 2) * AMBER_WF_SHARDS;
     const size_t bytes = (26 * q_len + 3 * n_paths) * 4 + n_counts * sizeof(unsigned int);
-    { const int rc = Grow(h, h->d_wf, bytes / sizeof(float), "wavefront queues"); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(Grow(h, h->d_wf, bytes / sizeof(float), "wavefront queues"));
     float* base = h->d_wf;
     WfQueue q[2];
     for (int k = 0; k < 2; k++) {
@@ -44,7 +44,7 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
     a.first_sample = first_sample + done; a.n_samples = n; a.n_paths = static_cast<uint32_t>(n_paths); a.bounce = 0; a.shard_capacity = static_cast<uint32_t>(shard_capacity);
     const uint32_t n_blocks = 2048u;                          // 8192 waves = 32 per shard
     std::pair<Event, Event>* evp = nullptr;
-    { const int rc = AcquireEventPair(h, &evp); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(AcquireEventPair(h, &evp));
     auto& ev = *evp;
     HIP_TRY(hipEventRecord(ev.first.v, h->stream));
     a.out = q[0]; a.in = q[1];
@@ -169,7 +169,7 @@ int amber_hip_kat_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);
   if (!h || !out || n_samples == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
-  const uint64_t n = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w * n_samples;
+  const uint64_t n = BandPixels(h) * n_samples;
   if (n == 0) return AMBER_OK;
   if ((n + 255) / 256 > 0x7fffffffull) return Fail(AMBER_EINVAL, "too many paths for one call");
   HIP_TRY(hipSetDevice(h->device));
@@ -195,7 +195,7 @@ int amber_hip_kat_traversal_rate(amber_hip_pt* h, uint32_t n, const float* origi
   const uint64_t n_virtual = static_cast<uint64_t>(n) * (repeats ? repeats : 1u);
   if (n_virtual > 0xfffffeffull) return Fail(AMBER_EINVAL, "n * repeats must stay below 2^32");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));
   std::vector<float4> packed(2ull * n);
   for (uint32_t i = 0; i < n; i++) {
     packed[2ull * i] = make_float4(origins[3ull * i], origins[3ull * i + 1], origins[3ull * i + 2], 0.f);
@@ -245,11 +245,11 @@ int amber_hip_kat_pixel_masks(amber_hip_pt* h, uint32_t* out_mask, uint32_t* out
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   if (!h->two_phase) return Fail(AMBER_EINVAL, "pixel masks belong to the two-phase engine");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
-  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  AMBER_TRY(ResolvePending(h));
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   if (out_mask || kernel_ms) {                                 // the slot table and the always-mask below do not need the kernel
     float ms = 0;
-    { const int rc = StartPixelMasks(h, kernel_ms ? &ms : nullptr); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(StartPixelMasks(h, kernel_ms ? &ms : nullptr));
     if (!h->pixel_mask_ready) return Fail(AMBER_EINVAL, "pixel masks are switched off (AMBER_PIXEL_MASK=0) or the band is empty");
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (out_mask) HIP_TRY(hipMemcpy(out_mask, h->d_pixel_mask, static_cast<size_t>(n_pixels) * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -267,7 +267,7 @@ int amber_hip_kat_bvh_dump(amber_hip_pt* h, uint32_t* nodes, uint32_t node_capac
   if (!h || !info) return Fail(AMBER_EINVAL, "null argument");
   if (h->hit_engine != AMBER_ENGINE_BVH) return Fail(AMBER_EINVAL, "the handle's engine is not BVH");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));
   HIP_TRY(hipStreamSynchronize(h->stream));
   static_assert(sizeof(DevBvhNodeQ) == 8 * sizeof(uint32_t), "a dumped node is 8 words");
   info->n_nodes = h->build.n_nodes; info->n_prims = h->scene.n_objects; info->root = h->scene.bvh_root; info->depth = h->build.depth;
@@ -283,20 +283,20 @@ int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_s
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
   if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, "signatures come from the work-queue kernels (engines list, two_phase, bvh)");
   const bool bvh_items = h->hit_engine == AMBER_ENGINE_BVH && !h->bvh_pool && !h->bvh_paths;        // pt_bvh_megakernel's signature instantiation
-  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   const uint64_t n = static_cast<uint64_t>(n_pixels) * n_samples;
   if (n == 0) return AMBER_OK;
   if (n > kMaxPathsPerLaunch) return Fail(AMBER_EINVAL, "too many paths for one call");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  { const int rc = Grow(h, h->d_sig, n, "signatures"); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, h->d_sig, n, "signatures"));
   HIP_TRY(hipMemsetAsync(h->d_sig, 0, n * sizeof(unsigned long long), h->stream));
   if (bvh_items) {
-    const int rc = RenderPassBvhItems(h, first_sample, n_samples, n_pixels, h->d_sig); if (rc != AMBER_OK) return rc;
+    AMBER_TRY(RenderPassBvhItems(h, first_sample, n_samples, n_pixels, h->d_sig));
   } else {
-    { const int rc = EnsureRecordCapacity(h, RecordSlack(h)); if (rc != AMBER_OK) return rc; }   // records of this launch are discarded
-    const int rc = LaunchPaths(h, first_sample, n_samples, n_pixels, h->d_sig); if (rc != AMBER_OK) return rc;
+    AMBER_TRY(EnsureRecordCapacity(h, RecordSlack(h)));   // records of this launch are discarded
+    AMBER_TRY(LaunchPaths(h, first_sample, n_samples, n_pixels, h->d_sig));
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, h->d_sig, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -311,12 +311,12 @@ int amber_hip_kat_lt_accumulate(amber_hip_pt* h, const AmberSplat* records, uint
   for (uint32_t i = 0; i < n; i++) if (records[i].pixel >= npx) return Fail(AMBER_EINVAL, "pixel index out of range");
   if (n == 0) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
-  { const int rc = EnsureLtSplats(h, n); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));
+  AMBER_TRY(EnsureLtSplats(h, n));
   static_assert(sizeof(AmberSplat) == sizeof(DevSplat), "splat layouts must agree");
   HIP_TRY(hipMemcpyAsync(h->d_splats, records, static_cast<size_t>(n) * sizeof(DevSplat), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemsetAsync(h->lt.longest.p, 0, sizeof(unsigned int), h->stream));
-  { const int rc = LtAccumulate(h, n, 32u); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(LtAccumulate(h, n, 32u));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return AMBER_OK;
 }); }

@@ -91,7 +91,7 @@ int EnsureLtSplats(amber_hip_pt* h, uint32_t capacity) {
   LtAccumBufs& s = h->lt;
   if (s.capacity < AMBER_LT_SPLAT_CAPACITY0) s.capacity = AMBER_LT_SPLAT_CAPACITY0;
   if (s.capacity < capacity) s.capacity = capacity;
-  { const int rc = Grow(h, h->d_splats, s.capacity, "splats"); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, h->d_splats, s.capacity, "splats"));
   if (!h->d_splat_count) HIP_TRY(h->d_splat_count.alloc(1));
   if (!s.longest) HIP_TRY(s.longest.alloc(1));
   return AMBER_OK;
@@ -104,16 +104,16 @@ int LtAccumulate(amber_hip_pt* h, uint32_t n, uint32_t path_bits) {
   const uint32_t n_pixels = h->scene.sensor.w * h->scene.sensor.h;
   const hipStream_t st = h->stream;
   for (int k = 0; k < 2; k++) {
-    { const int rc = Grow(h, s.key[k], n, "splat keys"); if (rc != AMBER_OK) return rc; }
-    { const int rc = Grow(h, s.index[k], n, "splat order"); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(Grow(h, s.key[k], n, "splat keys"));
+    AMBER_TRY(Grow(h, s.index[k], n, "splat order"));
   }
-  { const int rc = Grow(h, s.value, n, "sorted splats"); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, s.value, n, "sorted splats"));
   // (path, bounce): bounce has no bound (max_depth == 0), all its 32 bits count; (pixel, pass): pass is any 32-bit value, pixel < n_pixels
   const unsigned int path_end = 32u + path_bits, pixel_end = 32u + BitsFor(n_pixels);
   size_t bytes_a = 0, bytes_b = 0;
   HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes_a, s.key[0].p, s.key[1].p, s.index[0].p, s.index[1].p, n, 0u, path_end, st));
   HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes_b, s.key[0].p, s.key[1].p, s.index[1].p, s.index[0].p, n, 0u, pixel_end, st));
-  { const int rc = Grow(h, s.temp, std::max(bytes_a, bytes_b), "sort scratch"); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, s.temp, std::max(bytes_a, bytes_b), "sort scratch"));
   const dim3 grid((n + 255u) / 256u), wg(256);
 #ifdef AMBER_LAB
   if (s.stage_timing) {
@@ -159,8 +159,8 @@ int LtRenderPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, Amb
   if (!WholeFrame(h)) return Fail(AMBER_EINVAL, name + ": the handle renders a band or stripes of the frame; light paths land anywhere in it (use amber_hip_lt_trace_range and merge on the host)");
   if (n_samples == 0 || h->scene.n_lights == 0) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }   // the order of the sums: a path-tracing pass in flight must stand first
-  { const int rc = EnsureLtSplats(h, 0u); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));   // the order of the sums: a path-tracing pass in flight must stand first
+  AMBER_TRY(EnsureLtSplats(h, 0u));
   LtAccumBufs& s = h->lt;
   HIP_TRY(hipMemsetAsync(s.longest.p, 0, sizeof(unsigned int), h->stream));
   const uint32_t n_paths = h->scene.sensor.w * h->scene.sensor.h;
@@ -178,7 +178,7 @@ int LtRenderPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, Amb
       if (produced > 0x7fffffffu) return Fail(AMBER_ENOMEM, name + ": more than 2^31 records in one launch");
       HIP_TRY(hipMemcpyAsync(h->d_rays, &rays_kept, sizeof rays_kept, hipMemcpyHostToDevice, h->stream));
       HIP_TRY(hipStreamSynchronize(h->stream));
-      { const int rg = EnsureLtSplats(h, produced); if (rg != AMBER_OK) return rg; }
+      AMBER_TRY(EnsureLtSplats(h, produced));
       repeated = true; total.n_repeats++; *again = true;
       return AMBER_OK;
     }

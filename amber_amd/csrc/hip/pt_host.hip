@@ -1,7 +1,7 @@
 // pt_host.hip -- the ONE translation unit of the gfx950 path-tracing engine: the handle, the host side of every launch and the C ABI
 // (include/amber_hip.h).  The kernels live in files of their own and are included here, where they are launched:
 //   c_boundary.h           the rule of the C ABI: no exception crosses an extern "C" function -- every entry point that can allocate or form a message runs under
-//                          Guarded(name, f) (bad_alloc / system_error -> AMBER_ENOMEM, anything else -> AMBER_EHIP); the thread-local message, Fail, HIP_TRY
+//                          Guarded(name, f) (bad_alloc / system_error -> AMBER_ENOMEM, anything else -> AMBER_EHIP); the thread-local message, Fail, HIP_TRY, AMBER_TRY
 //   pt_args.h              RenderArgs; record emission (accumulation without owners)
 //   exact_div.h            exact division by a launch constant without a divide (the pixel bookkeeping of the render kernels)
 //   pt_megakernel.inc      pt_megakernel: persistent waves, work unit = ONE PATH (q = band pixel * n_samples + sample), a wave claims 1024 paths with
@@ -18,6 +18,9 @@
 //   ray_query.inc          amber_hip_pt_cast_rays / amber_hip_pt_occluded: the caller's rays through the handle's engine -- engine BVH in a persistent refill
 //                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>;
 //                          LaunchPerItem, the launch of every kernel with a thread per item (its engine front end: dev_closest_hit.h).
+//   image_stage.inc        what the five files below share, the stage that runs on the band after accumulation: BandPixels, the zero-on-first-use band
+//                          buffer (AOV sums, moments, history) with its clear / download / device pointer, the check of the output arguments and the
+//                          output tail, the check of the filters' parameters, the device helpers of the filters' kernels (stops, luminance, guide record).
 //   resolve.inc            amber_hip_pt_resolve: the framebuffer's sums as the mean or, through Filmic + Gamma, as 8-bit RGB / RGBA, in device memory --
 //                          a streaming kernel, four output pixels per thread, bytes equal to the host's output stage.
 //   aov.inc                amber_hip_pt_aov_pass and its three companions: the first-hit guide images (albedo, depth, normal, coverage) of the band --
@@ -157,6 +160,21 @@ struct LtAccumBufs {
   Event ev[3];
 #endif
 };
+// The image stage -- everything that runs on the band after accumulation (image_stage.inc and the five files behind it): its buffers, per band pixel
+struct ImageStageBufs {
+  DevBuf<uint8_t> resolve_out;              // AMBER_RESOLVE_HOST: staging of the output (WriteBandOutput), grown on first use and reused
+  DevBuf<float4> aov;                       // amber_hip_pt_aov_* (aov.inc): two float4, allocated and zeroed by the first call that needs them
+  DevBuf<float> denoise_color[2];           // amber_hip_pt_denoise (denoise.inc): the levels' input and output, 3 floats each, grown on first use
+  DevBuf<float4> denoise_guide;             // ... and the guide records {a.xyz, z} {n.xyz, rz}, two float4
+  DevBuf<float4> dv_record[2];              // amber_hip_pt_denoise_variance (denoise_variance.inc): {c.rgb, var}, the levels' input and output, grown on first use
+  DevBuf<float4> moments;                   // amber_hip_pt_render_batch / _moments_*: {m1, m2, batches, pad}, allocated and zeroed by the first call that needs it
+  DevBuf<float4> history[2];                // amber_hip_pt_temporal (temporal.inc): {color.rgb, length} {m1, m2, 0, 0}, used ping-pong, allocated and zeroed by the first call that needs them
+  DevBuf<float4> history_guide[2];          // ... and the guide records of the frame each history was written with
+  uint32_t history_cur = 0;                 // the pair that holds the current history
+  bool history_empty = true;                // nothing to reproject: set at create and by amber_hip_pt_temporal_reset
+  DevLens history_lens{};                   // the handle's lens as the call that wrote the current history saw it
+  DevBuf<float> batch;                      // amber_hip_pt_render_batch: the sums of the batch in flight, 3 floats, grown on first use
+};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -198,20 +216,9 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<unsigned int> d_query_next;        // engine BVH: the work counter
   DevBuf<float4> d_query_rays;              // AMBER_RAYS_HOST: staging of the rays and of the results, at most kQueryStageRays rays
   DevBuf<uint8_t> d_query_out;
-  DevBuf<uint8_t> d_resolve_out;            // amber_hip_pt_resolve with AMBER_RESOLVE_HOST (resolve.inc): staging of the output, grown on first use and reused
-  DevBuf<float4> d_aov;                     // amber_hip_pt_aov_* (aov.inc): two float4 per band pixel, allocated and zeroed by the first of those calls
-  DevBuf<float> d_denoise_color[2];         // amber_hip_pt_denoise (denoise.inc): the levels' input and output, 3 floats per band pixel each, grown on first use
-  DevBuf<float4> d_denoise_guide;           // ... and the guide records {a.xyz, z} {n.xyz, rz}, two float4 per band pixel
-  DevBuf<float4> d_dv_record[2];            // amber_hip_pt_denoise_variance (denoise_variance.inc): {c.rgb, var} per band pixel, the levels' input and output, grown on first use
-  DevBuf<float4> d_moments;                 // amber_hip_pt_render_batch / _moments_*: {m1, m2, batches, pad} per band pixel, allocated and zeroed by the first call that needs it
-  DevBuf<float4> d_history[2];              // amber_hip_pt_temporal (temporal.inc): {color.rgb, length} {m1, m2, 0, 0} per band pixel, used ping-pong, allocated and zeroed by the first call that needs them
-  DevBuf<float4> d_history_guide[2];        // ... and the guide records of the frame each history was written with
-  uint32_t history_cur = 0;                 // the pair that holds the current history
-  bool history_empty = true;                // nothing to reproject: set at create and by amber_hip_pt_temporal_reset
-  DevLens history_lens{};                   // the handle's lens as the call that wrote the current history saw it
-  DevBuf<float> d_batch;                    // amber_hip_pt_render_batch: the sums of the batch in flight, 3 floats per band pixel, grown on first use
+  ImageStageBufs img;                       // resolve, AOVs, the filters, batches
   DevBuf<float> d_fb;
-  float* accum_target = nullptr;            // where reduce_flagged_kernel and reduce_partials_kernel add a pass: d_fb, except inside amber_hip_pt_render_batch (d_batch)
+  float* accum_target = nullptr;            // where reduce_flagged_kernel and reduce_partials_kernel add a pass: d_fb, except inside amber_hip_pt_render_batch (img.batch)
   DevBuf<unsigned long long> d_rays;
   DevBuf<unsigned int> d_next;
   DevBuf<unsigned long long> d_stamps;
@@ -266,6 +273,7 @@ uint64_t HostSplitMix64(uint64_t z) {
 }
 
 int StartPixelMasks(amber_hip_pt* h, float* timing);      // defined with the launch code below
+uint64_t BandPixels(const amber_hip_pt* h);               // the band's pixel count (image_stage.inc)
 uint32_t PersistentBlocks(const amber_hip_pt* h, uint64_t n_items = ~0ull, bool pool = false);
 
 int ValidateScene(const AmberFlatScene* s, const AmberSensor* sensor) {
@@ -315,8 +323,7 @@ hipError_t Upload(amber_hip_pt* h, const std::vector<T>& v, size_t extra, P& dst
 int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtParams* params, amber_hip_pt** out) {
   const auto t_create = std::chrono::steady_clock::now();
   auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-  int rc = ValidateScene(s, sensor);
-  if (rc != AMBER_OK) return rc;
+  AMBER_TRY(ValidateScene(s, sensor));
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
     return Fail(AMBER_ENODEVICE, "no HIP device available (this engine has no CPU fallback)");
@@ -402,8 +409,7 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
       for (const DevObject& o : p.objects) if ((o.kind & 0xffu) == AMBER_PRIM_SPHERE) in.rmin = std::min(in.rmin, std::fabs(o.radius));
       for (int k = 0; k < 3; k++) in.small_kinds[k] = h->small_kinds[k];
       dbuild::BuildResult res{};
-      const int rc_build = DeviceBuildBvh(h.get(), in, scratch, &res);
-      if (rc_build != AMBER_OK) return rc_build;
+      AMBER_TRY(DeviceBuildBvh(h.get(), in, scratch, &res));
       reason = res.reason; n_nodes = res.n_nodes; depth = res.depth;
     }
     if (reason == AMBER_BUILD_REASON_NONE) {
@@ -451,7 +457,7 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
     HIP_TRY(h->d_ref_stack.alloc(bytes / sizeof(uint2)));
     sc.ref_stack = h->d_ref_stack; sc.ref_stack_stride = static_cast<uint32_t>(threads); h->ref_stack_threads = threads;
   }
-  { const int rc_masks = StartPixelMasks(h.get(), nullptr); if (rc_masks != AMBER_OK) return rc_masks; }   // asynchronous, on the render stream: in front of the handle's first launch
+  AMBER_TRY(StartPixelMasks(h.get(), nullptr));   // asynchronous, on the render stream: in front of the handle's first launch
   h->build.create_ms = ms_since(t_create);
   *out = h.release();
   return AMBER_OK;
@@ -585,8 +591,8 @@ int EnsureRecordCapacity(amber_hip_pt* h, uint64_t slots) {
   if (slots <= h->rec_capacity) return AMBER_OK;
   if (slots > 0xfffffff0ull) return Fail(AMBER_ENOMEM, "record buffer beyond 2^32 slots");
   h->rec_capacity = 0;
-  { const int rc = Grow(h, h->d_records, slots, "path records"); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_sorted, slots * 3u, "path records"); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, h->d_records, slots, "path records"));
+  AMBER_TRY(Grow(h, h->d_sorted, slots * 3u, "path records"));
   h->rec_capacity = static_cast<uint32_t>(slots);
   return AMBER_OK;
 }
@@ -606,7 +612,7 @@ int EnsureLaunchCtl(amber_hip_pt* h) {                                       // 
 // create -- in front of the handle's first launch.  The buffer is allocated once and owned by the handle (amber_hip_pt_destroy releases it
 // whatever step failed).  `timing` != null (amber_hip_kat_pixel_masks): run the kernel (again) between two events and report its duration.
 int StartPixelMasks(amber_hip_pt* h, float* timing) {
-  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   if (!(h->two_phase && h->env.pixel_mask) || n_pixels == 0 || (h->pixel_mask_ready && !timing)) return AMBER_OK;
   if (!h->d_pixel_mask) HIP_TRY(h->d_pixel_mask.alloc(n_pixels));
   PixelMaskArgs pm{};
@@ -670,31 +676,28 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
 #endif
   const size_t need_words = static_cast<size_t>((n_paths + 31u) / 32u) + 4u;
   if (need_words > h->d_flags.n) {
-    const int rc = Grow(h, h->d_flags, need_words, "path bitmap"); if (rc != AMBER_OK) return rc;
+    AMBER_TRY(Grow(h, h->d_flags, need_words, "path bitmap"));
     h->flags_dirty = true;
   }
   const size_t touched_words = static_cast<size_t>(n_pixels) / 32u + 2u;
-  { const int rc = Grow(h, h->d_touched, touched_words, "touched pixels"); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_excl, n_pixels, "pixel ranks"); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_block_sum, static_cast<size_t>(n_pixels) / 256u + 2u, "pixel ranks"); if (rc != AMBER_OK) return rc; }
-  { const int rc = EnsureLaunchCtl(h); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, h->d_touched, touched_words, "touched pixels"));
+  AMBER_TRY(Grow(h, h->d_excl, n_pixels, "pixel ranks"));
+  AMBER_TRY(Grow(h, h->d_block_sum, static_cast<size_t>(n_pixels) / 256u + 2u, "pixel ranks"));
+  AMBER_TRY(EnsureLaunchCtl(h));
   if (!h->h_rec_count.v) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_rec_count.v), sizeof(unsigned int), hipHostMallocDefault));
   if (!h->pending_event.v) HIP_TRY(hipEventCreateWithFlags(&h->pending_event.v, hipEventDisableTiming));
   const uint32_t n_blocks = PersistentBlocks(h, n_paths, bvh);
-  { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(CheckRefStack(h, n_blocks));
   {
     // measurements carried across bounces (degenerate paths only): pt_megakernel 3 floats per thread of the grid, pt_bvh_pool_kernel per ray of a wave
     size_t carried = static_cast<size_t>(PersistentBlocks(h)) * 256u * 3u * 2u;   // own slots + parked slots
 #ifdef AMBER_LAB
     if (bvh) carried = static_cast<size_t>(h->n_cus) * AMBER_BVH_POOL_WGS * 4u * AMBER_BVH_POOL_CARRIED_PER_WAVE;
 #endif
-    const int rc = Grow(h, h->d_carried, carried, "carried measurements"); if (rc != AMBER_OK) return rc;
+    AMBER_TRY(Grow(h, h->d_carried, carried, "carried measurements"));
   }
 #ifdef AMBER_LAB
-  if (bvh) {
-    const int rc = Grow(h, h->d_bvh_stack, static_cast<size_t>(h->n_cus) * AMBER_BVH_POOL_WGS * 256u * AMBER_BVH_POOL_GLOBAL_LEVELS, "traversal stacks");
-    if (rc != AMBER_OK) return rc;
-  }
+  if (bvh) AMBER_TRY(Grow(h, h->d_bvh_stack, static_cast<size_t>(h->n_cus) * AMBER_BVH_POOL_WGS * 256u * AMBER_BVH_POOL_GLOBAL_LEVELS, "traversal stacks"));
 #endif
   RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first, n);
   a.pixel_mask = h->pixel_mask_ready ? h->d_pixel_mask : nullptr;
@@ -708,7 +711,7 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
   h->flags_dirty = sig != nullptr || (n & 31u) != 0u;
   HIP_TRY(hipMemsetAsync(h->d_touched, 0, touched_words * sizeof(uint32_t), h->stream));
   std::pair<Event, Event>* evp = nullptr;
-  { const int rc = AcquireEventPair(h, &evp); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(AcquireEventPair(h, &evp));
   auto& ev = *evp;
   HIP_TRY(hipEventRecord(ev.first.v, h->stream));
 #ifdef AMBER_LAB
@@ -741,17 +744,16 @@ int ResolvePending(amber_hip_pt* h) {
     HIP_TRY(hipEventSynchronize(h->pending_event.v));
     h->pending = false;
     const uint64_t used = *h->h_rec_count.v;
-    const uint64_t n_paths = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w * h->pending_n;
+    const uint64_t n_paths = BandPixels(h) * h->pending_n;
     h->rec_density = n_paths ? static_cast<double>(used) / static_cast<double>(n_paths) : 0.0;
     h->density_known = true;
     if (used <= h->rec_capacity) break;
     // out of slots: nothing of that launch reached the framebuffer or the ray total (and its bits are still set)
     h->flags_dirty = true;
-    const int rc = EnsureRecordCapacity(h, used + used / 4u + RecordSlack(h));
-    if (rc != AMBER_OK) return rc;
+    AMBER_TRY(EnsureRecordCapacity(h, used + used / 4u + RecordSlack(h)));
     float* const target = h->accum_target;
     h->accum_target = h->pending_target;
-    const int rl = LaunchPaths(h, h->pending_first, h->pending_n, h->local_rows * h->scene.sensor.w, nullptr);
+    const int rl = LaunchPaths(h, h->pending_first, h->pending_n, static_cast<uint32_t>(BandPixels(h)), nullptr);
     h->accum_target = target;
     if (rl != AMBER_OK) return rl;
   }
@@ -766,7 +768,7 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
   while (done < n_samples) {
     // the previous launch must stand before the next one adds to the framebuffer (the order of the sums is part of the
     // contract), unless it had a slot for every path
-    if (h->pending && (!h->pending_checked || !h->density_known)) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+    if (h->pending && (!h->pending_checked || !h->density_known)) AMBER_TRY(ResolvePending(h));
     uint32_t n = n_samples - done;
     if (n > max_samples) n = static_cast<uint32_t>(max_samples);
     uint64_t slots;
@@ -790,12 +792,10 @@ int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
       slots = std::min<uint64_t>(all_n, static_cast<uint64_t>(per_sample * n) + 1u) + slack;
     }
     if (slots > h->rec_capacity) {
-      if (h->pending) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }     // the buffer is in use
-      const int rc = EnsureRecordCapacity(h, slots);
-      if (rc != AMBER_OK) return rc;
+      if (h->pending) AMBER_TRY(ResolvePending(h));     // the buffer is in use
+      AMBER_TRY(EnsureRecordCapacity(h, slots));
     }
-    const int rl = LaunchPaths(h, first_sample + done, n, n_pixels, nullptr);
-    if (rl != AMBER_OK) return rl;
+    AMBER_TRY(LaunchPaths(h, first_sample + done, n, n_pixels, nullptr));
     done += n;
   }
   return AMBER_OK;
@@ -832,9 +832,9 @@ int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
     a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = capacity;
     a.path_offset = path_begin; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
     const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
-    { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(CheckRefStack(h, n_blocks));
     std::pair<Event, Event>* evp = nullptr;
-    if (timed) { const int rc = AcquireEventPair(h, &evp); if (rc != AMBER_OK) return rc; }
+    if (timed) AMBER_TRY(AcquireEventPair(h, &evp));
     HIP_TRY(hipMemsetAsync(h->d_splat_count, 0, sizeof(unsigned int), h->stream));
     HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
     if (evp) HIP_TRY(hipEventRecord(evp->first.v, h->stream));
@@ -851,7 +851,7 @@ int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
     HIP_TRY(hipMemcpyAsync(&rays_now, h->d_rays, sizeof rays_now, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     bool again = false;
-    { const int rc = after_launch(first_sample + done, n, produced, rays_before, rays_now, &again); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(after_launch(first_sample + done, n, produced, rays_before, rays_now, &again));
     if (!again) done += n;
   }
   return AMBER_OK;
@@ -859,6 +859,7 @@ int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 }  // namespace
 
 #include "ray_query.inc"
+#include "image_stage.inc"
 #include "resolve.inc"
 #include "aov.inc"
 #include "denoise.inc"
@@ -878,7 +879,7 @@ int amber_hip_pt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   if (n_samples == 0) return AMBER_OK;
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
   HIP_TRY(hipSetDevice(h->device));
-  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   if (n_pixels == 0) return AMBER_OK;                    // empty band
 #ifdef AMBER_LAB
   if (h->engine == AMBER_ENGINE_WAVEFRONT) return RenderPassWavefront(h, first_sample, n_samples);
@@ -895,18 +896,18 @@ int amber_hip_pt_render_batch(amber_hip_pt* h, uint32_t first_sample, uint32_t n
   if (n_samples == 0) return AMBER_OK;
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, name + ": sample index overflow");
   HIP_TRY(hipSetDevice(h->device));
-  const uint32_t n_pixels = h->local_rows * h->scene.sensor.w;
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   if (n_pixels == 0) return AMBER_OK;                    // empty band
   if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, name + ": not part of the lab engine WAVEFRONT");
   // a pass in flight whose record buffer was sized from an estimate may have to be repeated: it must stand before the target moves
-  if (h->pending && !h->pending_checked) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
-  { const int rc = EnsureMoments(h, name.c_str()); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_batch, static_cast<size_t>(n_pixels) * 3u, "batch sums"); if (rc != AMBER_OK) return rc; }
-  HIP_TRY(hipMemsetAsync(h->d_batch, 0, static_cast<size_t>(n_pixels) * 3u * sizeof(float), h->stream));
+  if (h->pending && !h->pending_checked) AMBER_TRY(ResolvePending(h));
+  AMBER_TRY(EnsureMoments(h, name.c_str()));
+  AMBER_TRY(Grow(h, h->img.batch, static_cast<size_t>(n_pixels) * 3u, "batch sums"));
+  HIP_TRY(hipMemsetAsync(h->img.batch, 0, static_cast<size_t>(n_pixels) * 3u * sizeof(float), h->stream));
   {
     struct Target {
       amber_hip_pt* h;
-      explicit Target(amber_hip_pt* handle) : h(handle) { h->accum_target = h->d_batch; }
+      explicit Target(amber_hip_pt* handle) : h(handle) { h->accum_target = h->img.batch; }
       ~Target() { h->accum_target = h->d_fb; }
     } target(h);
     int rc = (h->hit_engine != AMBER_ENGINE_BVH || h->bvh_pool || h->bvh_paths) ? RenderPassPaths(h, first_sample, n_samples, n_pixels)
@@ -939,9 +940,9 @@ static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n
     if (n > cap) n = static_cast<uint32_t>(cap);
     const uint32_t n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
     const size_t need = static_cast<size_t>(n_chunks) * n_pixels * 3u;
-    { const int rc = Grow(h, h->d_partial, need, "partial sums"); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(Grow(h, h->d_partial, need, "partial sums"));
     if (sig && n != n_samples) return Fail(AMBER_EINVAL, "too many paths for one signature launch");
-    if (sig) { const int rc = EnsureLaunchCtl(h); if (rc != AMBER_OK) return rc; }
+    if (sig) AMBER_TRY(EnsureLaunchCtl(h));
     RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first_sample + done, n);
     a.partial = h->d_partial; a.ray_count = sig ? h->d_rays_launch : h->d_rays; a.next_item = h->d_next; a.stamps = h->d_stamps;
     a.n_items = n_pixels * n_chunks; a.sig = sig; a.shade_batch = h->bvh_shade_batch;
@@ -949,7 +950,7 @@ static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n
     const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
     HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
     std::pair<Event, Event>* evp = nullptr;
-    { const int rc = AcquireEventPair(h, &evp); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(AcquireEventPair(h, &evp));
     auto& ev = *evp;
     HIP_TRY(hipEventRecord(ev.first.v, h->stream));
 #ifdef AMBER_LAB
@@ -981,9 +982,9 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   const uint32_t n_paths = path_end - path_begin;
   if (n_samples == 0 || n_paths == 0 || h->scene.n_lights == 0) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));
   const uint32_t dev_capacity = capacity ? capacity : 1u;
-  { const int rc = Grow(h, h->d_splats, dev_capacity, "splats"); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, h->d_splats, dev_capacity, "splats"));
   if (!h->d_splat_count) HIP_TRY(h->d_splat_count.alloc(1));
   uint64_t total = 0;                                         // splats produced (also beyond the caller's capacity)
   unsigned long long rays_first = 0, rays_last = 0;
@@ -1030,8 +1031,8 @@ int amber_hip_lt_trace(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sample
 int amber_hip_pt_clear(amber_hip_pt* h) { return Guarded("amber_hip_pt_clear", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
-  const size_t fb_floats = static_cast<size_t>(h->local_rows) * h->scene.sensor.w * 3;
+  AMBER_TRY(ResolvePending(h));
+  const size_t fb_floats = static_cast<size_t>(BandPixels(h)) * 3u;
   HIP_TRY(hipMemsetAsync(h->d_fb, 0, fb_floats * sizeof(float), h->stream));
   HIP_TRY(hipMemsetAsync(h->d_rays, 0, sizeof(unsigned long long), h->stream));
   // (no host synchronisation: the two fills are ordered on the handle's stream like everything else; event pairs handed out before
@@ -1043,7 +1044,7 @@ int amber_hip_pt_clear(amber_hip_pt* h) { return Guarded("amber_hip_pt_clear", [
 int amber_hip_pt_sync(amber_hip_pt* h) { return Guarded("amber_hip_pt_sync", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return AMBER_OK;
 }); }
@@ -1051,8 +1052,8 @@ int amber_hip_pt_sync(amber_hip_pt* h) { return Guarded("amber_hip_pt_sync", [&]
 int amber_hip_pt_download(amber_hip_pt* h, float* rgb_sum, uint64_t* ray_count) { return Guarded("amber_hip_pt_download", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
-  const size_t fb_floats = static_cast<size_t>(h->local_rows) * h->scene.sensor.w * 3;
+  AMBER_TRY(ResolvePending(h));
+  const size_t fb_floats = static_cast<size_t>(BandPixels(h)) * 3u;
   if (rgb_sum) HIP_TRY(hipMemcpyAsync(rgb_sum, h->d_fb, fb_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   unsigned long long r = 0;
   HIP_TRY(hipMemcpyAsync(&r, h->d_rays, sizeof r, hipMemcpyDeviceToHost, h->stream));
@@ -1064,7 +1065,7 @@ int amber_hip_pt_download(amber_hip_pt* h, float* rgb_sum, uint64_t* ray_count) 
 int amber_hip_pt_device_framebuffer(amber_hip_pt* h, void** dptr, uint64_t* n_floats) { return Guarded("amber_hip_pt_device_framebuffer", [&]() -> int {
   if (!h || !dptr) return Fail(AMBER_EINVAL, "null argument");
   *dptr = h->d_fb;
-  if (n_floats) *n_floats = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w * 3;
+  if (n_floats) *n_floats = BandPixels(h) * 3;
   return AMBER_OK;
 }); }
 
@@ -1161,7 +1162,7 @@ int amber_hip_pt_build_info(amber_hip_pt* h, AmberBuildInfo* out) { return Guard
 int amber_hip_pt_kernel_time(amber_hip_pt* h, uint32_t* n_launches, double* total_ms) { return Guarded("amber_hip_pt_kernel_time", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
-  { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(ResolvePending(h));
   HIP_TRY(hipStreamSynchronize(h->stream));
   double tot = h->timed_ms;
   for (size_t i = 0; i < h->events_used; i++) {

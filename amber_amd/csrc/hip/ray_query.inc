@@ -143,7 +143,7 @@ uint32_t QueryGridCap(const amber_hip_pt* h) { return static_cast<uint32_t>(h->n
 template <typename F>
 int LaunchPerItem(amber_hip_pt* h, uint64_t n_items, F&& launch) {
   const uint32_t n_blocks = h->hit_engine == AMBER_ENGINE_BVH ? BlocksFor(n_items, QueryGridCap(h)) : PersistentBlocks(h, n_items);
-  { const int rc = CheckRefStack(h, n_blocks); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(CheckRefStack(h, n_blocks));
   WithHitEngine(h->hit_engine, [&](auto engine) -> int { launch(engine, n_blocks); return AMBER_OK; });
   HIP_TRY(hipGetLastError());
   return AMBER_OK;
@@ -195,12 +195,12 @@ int RayQuery(amber_hip_pt* h, uint64_t n, const AmberRay* rays, void* out, uint3
   // host pointers: through the handle's staging buffers, kQueryStageRays at a time, and back before the call returns
   const size_t out_size = any_hit ? 1u : sizeof(AmberRayHit);
   const uint64_t chunk = n < kQueryStageRays ? n : kQueryStageRays;
-  { const int rc = Grow(h, h->d_query_rays, chunk * 2u, "ray staging"); if (rc != AMBER_OK) return rc; }
-  { const int rc = Grow(h, h->d_query_out, chunk * out_size, "ray staging"); if (rc != AMBER_OK) return rc; }
+  AMBER_TRY(Grow(h, h->d_query_rays, chunk * 2u, "ray staging"));
+  AMBER_TRY(Grow(h, h->d_query_out, chunk * out_size, "ray staging"));
   for (uint64_t done = 0; done < n; done += chunk) {
     const uint64_t m = n - done < chunk ? n - done : chunk;
     HIP_TRY(hipMemcpyAsync(h->d_query_rays, rays + done, m * sizeof(AmberRay), hipMemcpyHostToDevice, h->stream));
-    { const int rc = LaunchRayQuery(h, m, h->d_query_rays, h->d_query_out, any_hit); if (rc != AMBER_OK) return rc; }
+    AMBER_TRY(LaunchRayQuery(h, m, h->d_query_rays, h->d_query_out, any_hit));
     HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(out) + done * out_size, h->d_query_out, m * out_size, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   }

@@ -12,6 +12,8 @@
 // Arithmetic: every operation binary32 and rounded alone (-ffp-contract=off), in the order of oracle_tonemap; the constant products, kE / kF,
 // Map(kW) and 1 / 2.2f are binary32 constant expressions there and here.  min is the comparison (p < 1) ? p : 1 -- std::min<float>(1, p) -- so a NaN
 // p gives 1.  No LDS, no scratch, no tuning surface: 256 threads per workgroup, registers left to the compiler (twelve independent Pow per thread).
+// Host side: the checks of the output arguments and the output tail (staging, launch, copy) are image_stage.inc's CheckBandOutput and WriteBandOutput,
+// which the three filters share; this file holds the kernel, its launch and the entry point.
 namespace {
 
 constexpr float kFilmicA = 0.22f, kFilmicB = 0.30f, kFilmicC = 0.10f, kFilmicD = 0.20f, kFilmicE = 0.01f, kFilmicF = 0.30f, kFilmicW = 0.70f, kFilmicExposure = 16.0f;
@@ -103,10 +105,8 @@ __global__ void __launch_bounds__(256) resolve_kernel(const float* __restrict__ 
   }
 }
 
-constexpr uint64_t kResolveBytesPerPixel[3] = {12u, 3u, 4u};                  // MEAN_F32, RGB8, RGBA8
-
 template <int kFormat>
-void LaunchResolve(amber_hip_pt* h, const float* src, bool mirror, void* d_out, uint64_t n_pixels, float n) {   // src: sums of the band's layout (the framebuffer; denoise.inc: a filtered mean with n = 1)
+void LaunchResolve(amber_hip_pt* h, const float* src, bool mirror, void* d_out, uint64_t n_pixels, float n) {   // WriteBandOutput's launch (image_stage.inc)
   const uint64_t n_vector = reinterpret_cast<uintptr_t>(d_out) % 16u == 0u ? n_pixels / 4u * 4u : 0u;
   const uint32_t n_blocks = static_cast<uint32_t>(((n_pixels + 3u) / 4u + 255u) / 256u);      // n_pixels < 2^32: at most 2^22 workgroups
   if (mirror) hipLaunchKernelGGL((resolve_kernel<kFormat, true>), dim3(n_blocks), dim3(256), 0, h->stream, src, d_out, n_pixels, n_vector, h->scene.sensor.w, n);
@@ -114,41 +114,16 @@ void LaunchResolve(amber_hip_pt* h, const float* src, bool mirror, void* d_out, 
 }
 
 int Resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
-  const char* name = "amber_hip_pt_resolve";
-  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
-  if (n_samples == 0) return Fail(AMBER_EINVAL, std::string(name) + ": n_samples is 0");
-  if (format > AMBER_RESOLVE_RGBA8) return Fail(AMBER_EINVAL, std::string(name) + ": unknown format " + std::to_string(format));
-  if (flags & ~static_cast<uint32_t>(AMBER_RESOLVE_HOST | AMBER_RESOLVE_MIRROR_X)) return Fail(AMBER_EINVAL, std::string(name) + ": unknown flag bits");
-  const uint64_t n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
-  const uint64_t want = n_pixels * kResolveBytesPerPixel[format];
-  if (out_bytes != want)
-    return Fail(AMBER_EINVAL, std::string(name) + ": out_bytes is " + std::to_string(out_bytes) + ", the band takes exactly " + std::to_string(want) + " (" +
-                                  std::to_string(h->local_rows) + " rows of " + std::to_string(h->scene.sensor.w) + " pixels, " + std::to_string(kResolveBytesPerPixel[format]) + " bytes each)");
-  if (n_pixels == 0) return AMBER_OK;                                         // empty band
-  if (!out) return Fail(AMBER_EINVAL, std::string(name) + ": null output pointer");
-  const bool host = (flags & AMBER_RESOLVE_HOST) != 0u;
-  if (!host && format != AMBER_RESOLVE_RGB8 && reinterpret_cast<uintptr_t>(out) % 4u != 0u)
-    return Fail(AMBER_EINVAL, std::string(name) + ": a device pointer for MEAN_F32 or RGBA8 must be 4-byte aligned");
+  const std::string name = "amber_hip_pt_resolve";
+  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
+  if (n_samples == 0) return Fail(AMBER_EINVAL, name + ": n_samples is 0");
+  BandOutput o{};
+  { const int rc = CheckBandOutput(h, name, false, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
   HIP_TRY(hipSetDevice(h->device));
   // a pass whose record buffer was sized from an estimate may have to be repeated before its sums stand (ResolvePending): wait for that one, as
   // clear and download do; a pass with a slot for every path, and every pass of the item kernel, needs no waiting
-  if (h->pending && !h->pending_checked) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }
-  void* d_out = out;
-  if (host) {
-    const int rc = Grow(h, h->d_resolve_out, want, "resolve staging"); if (rc != AMBER_OK) return rc;
-    d_out = h->d_resolve_out.p;
-  }
-  const float n = static_cast<float>(n_samples);
-  const bool mirror = (flags & AMBER_RESOLVE_MIRROR_X) != 0u;
-  if (format == AMBER_RESOLVE_MEAN_F32) LaunchResolve<AMBER_RESOLVE_MEAN_F32>(h, h->d_fb.p, mirror, d_out, n_pixels, n);
-  else if (format == AMBER_RESOLVE_RGB8) LaunchResolve<AMBER_RESOLVE_RGB8>(h, h->d_fb.p, mirror, d_out, n_pixels, n);
-  else LaunchResolve<AMBER_RESOLVE_RGBA8>(h, h->d_fb.p, mirror, d_out, n_pixels, n);
-  HIP_TRY(hipGetLastError());
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, want, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return AMBER_OK;
+  if (h->pending && !h->pending_checked) AMBER_TRY(ResolvePending(h));
+  return WriteBandOutput(h, o, format, h->d_fb, static_cast<float>(n_samples), out);
 }
 
 }  // namespace

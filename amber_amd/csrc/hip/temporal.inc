@@ -3,7 +3,8 @@
 // and the thin lens), validated against the previous frame's guide record with amber_hip_pt_denoise's three guide stops, blended with this frame's
 // mean as a running mean of capped length, and handed to denoise.inc's level kernel and resolve.inc's output stage.  A fixed sequence of binary32
 // operations, each rounded alone (-ffp-contract=off); the contract of include/amber_hip.h states it (its numpy restatement: tests/temporal_reference.py).
-// Part of the one translation unit pt_host.hip; the guide record, DenoiseGuideStop and the output checks are denoise.inc's, lum is denoise_variance.inc's.
+// Part of the one translation unit pt_host.hip; the guide record, DenoiseGuideStop, lum, the history's BandBuf, the checks of the parameters and of the
+// output arguments and the output tail are image_stage.inc's, the levels denoise.inc's LaunchDenoiseLevels.
 //
 //   temporal_kernel   ONE kernel for prepare, reprojection, validation, blend and the three writes (no denoise_prepare_kernel in front of it): one
 //                     thread per band pixel on the level kernel's 64 x 4 tile, so a wave is 64 consecutive pixels of a row.  Per pixel it reads this
@@ -51,14 +52,9 @@ __global__ void __launch_bounds__(256) temporal_kernel(const TemporalArgs a) {
   const float* s = a.fb + 3u * p;
   const float cr = s[0] / a.n, cg = s[1] / a.n, cb = s[2] / a.n;
   const float4 a0 = a.aov[2u * p], a1 = a.aov[2u * p + 1u];
-  const float cov = a1.w;
-  const bool covered = cov > 0.f;
-  float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
-  if (covered) {
-    g0.x = a0.x / cov; g0.y = a0.y / cov; g0.z = a0.z / cov; g0.w = a0.w / cov;
-    g1.x = a1.x / cov; g1.y = a1.y / cov; g1.z = a1.z / cov;
-  }
-  g1.w = g0.w > 0.f ? 1.0f / g0.w : 0.f;
+  const bool covered = a1.w > 0.f;
+  float4 g0, g1;
+  GuideRecord(a0, a1, g0, g1);
   const float yl = DvLuminance(cr, cg, cb);
   // ---- where the pixel was: the taps' local coordinates, their weights, the expected depth
   int64_t ix = static_cast<int64_t>(x), iy = static_cast<int64_t>(y);
@@ -123,81 +119,43 @@ bool TemporalSameLens(const DevLens& u, const DevLens& v) {
          std::memcmp(&u.sensor_distance, &v.sensor_distance, 4) == 0 && std::memcmp(&u.p_area, &v.p_area, 4) == 0 && u.n_blades == v.n_blades && u.kind == v.kind;
 }
 
-// The four buffers of the band: allocated and zeroed (on the handle's stream) by the first entry point that needs them; nothing for an empty band.
-int EnsureHistory(amber_hip_pt* h, const char* name) {
-  const uint64_t n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
-  if (n_pixels == 0 || h->d_history[0]) return AMBER_OK;
-  DevBuf<float4> fresh[4];
-  for (DevBuf<float4>& f : fresh) {
-    const hipError_t e = f.alloc(static_cast<size_t>(n_pixels) * 2u);
-    if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string(name) + ": hipMalloc(history buffers): " + hipGetErrorString(e));
-    HIP_TRY(hipMemsetAsync(f, 0, static_cast<size_t>(n_pixels) * sizeof(AmberHistoryPixel), h->stream));
-  }
-  for (int i = 0; i < 2; i++) { h->d_history[i].swap(fresh[i]); h->d_history_guide[i].swap(fresh[2 + i]); }
-  h->history_cur = 0; h->history_empty = true;
-  return AMBER_OK;
+// The two history buffers and the two guide buffers of the band, zeroed together by the first entry point that needs them: image_stage.inc's BandBuf,
+// the current history in front (until there is one, pair 0 is current and the history empty)
+BandBuf HistoryBuf(amber_hip_pt* h) {
+  ImageStageBufs& img = h->img;
+  return {{&img.history[img.history_cur], &img.history[img.history_cur ^ 1u], &img.history_guide[0], &img.history_guide[1]}, 4, 2u, "history buffers"};
 }
+int EnsureHistory(amber_hip_pt* h, const char* name) { return EnsureBand(h, HistoryBuf(h), name); }
 
 int Temporal(amber_hip_pt* h, uint32_t n_samples, const AmberTemporalParams* params, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
   const std::string name = "amber_hip_pt_temporal";
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (!params) return Fail(AMBER_EINVAL, name + ": null params");
-  if (n_samples == 0) return Fail(AMBER_EINVAL, name + ": n_samples is 0");
-  if (params->levels > 8u) return Fail(AMBER_EINVAL, name + ": levels is " + std::to_string(params->levels) + ", not 0 .. 8");
-  if (params->max_history < 1u || params->max_history > 65535u) return Fail(AMBER_EINVAL, name + ": max_history is " + std::to_string(params->max_history) + ", not 1 .. 65535");
-  const float k[4] = {params->k_normal, params->k_albedo, params->k_depth, params->k_color};
-  const char* k_name[4] = {"k_normal", "k_albedo", "k_depth", "k_color"};
-  for (int i = 0; i < 4; i++)
-    if (!(k[i] >= 0.f) || std::isinf(k[i])) return Fail(AMBER_EINVAL, name + ": " + k_name[i] + " is negative, NaN or infinite");
-  if (params->reserved[0] | params->reserved[1]) return Fail(AMBER_EINVAL, name + ": reserved fields must be 0");
-  DenoiseOutput o{};
-  { const int rc = CheckDenoiseOutput(h, name, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
-  const uint64_t n_pixels = o.n_pixels;
-  HIP_TRY(hipSetDevice(h->device));
-  if (h->pending && !h->pending_checked) { const int rc = ResolvePending(h); if (rc != AMBER_OK) return rc; }      // as resolve: the sums must stand
-  { const int rc = EnsureAov(h, name.c_str()); if (rc != AMBER_OK) return rc; }
-  { const int rc = EnsureHistory(h, name.c_str()); if (rc != AMBER_OK) return rc; }
-  for (DevBuf<float>& c : h->d_denoise_color) { const int rc = Grow(h, c, static_cast<size_t>(n_pixels) * 3u, "denoise colour"); if (rc != AMBER_OK) return rc; }
-  void* d_out = out;
-  if (o.host) {
-    const int rc = Grow(h, h->d_resolve_out, o.want, "resolve staging"); if (rc != AMBER_OK) return rc;
-    d_out = h->d_resolve_out.p;
-  }
-  const uint32_t cur = h->history_cur, next = cur ^ 1u;
+  const FilterExtra<AmberTemporalParams> history{&AmberTemporalParams::max_history, "max_history", 1u, 65535u, true};
+  AMBER_TRY(CheckFilterParams(name, h, params, n_samples, 0u, &AmberTemporalParams::k_color, "k_color", &history));
+  BandOutput o{};
+  { const int rc = CheckBandOutput(h, name, true, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
+  AMBER_TRY(BeginFilter(h, name));
+  AMBER_TRY(EnsureHistory(h, name.c_str()));
+  ImageStageBufs& img = h->img;
+  for (DevBuf<float>& c : img.denoise_color) AMBER_TRY(Grow(h, c, static_cast<size_t>(o.n_pixels) * 3u, "denoise colour"));
+  const uint32_t cur = img.history_cur, next = cur ^ 1u;
   TemporalArgs t{};
-  t.fb = h->d_fb; t.aov = h->d_aov; t.hist_in = h->d_history[cur]; t.guide_in = h->d_history_guide[cur];
-  t.hist_out = h->d_history[next]; t.guide_out = h->d_history_guide[next]; t.color_out = h->d_denoise_color[0];
+  t.fb = h->d_fb; t.aov = img.aov; t.hist_in = img.history[cur]; t.guide_in = img.history_guide[cur];
+  t.hist_out = img.history[next]; t.guide_out = img.history_guide[next]; t.color_out = img.denoise_color[0];
   t.width = o.width; t.rows = o.rows; t.blocks_x = o.blocks_x; t.row_begin = h->row_begin;
-  t.mode = h->history_empty ? TEMPORAL_EMPTY : TemporalSameLens(h->lens, h->history_lens) ? TEMPORAL_SAME_LENS : TEMPORAL_MOVED_LENS;
+  t.mode = img.history_empty ? TEMPORAL_EMPTY : TemporalSameLens(h->lens, img.history_lens) ? TEMPORAL_SAME_LENS : TEMPORAL_MOVED_LENS;
   t.n = static_cast<float>(n_samples); t.max_history = static_cast<float>(params->max_history);
   t.k_normal = params->k_normal; t.k_albedo = params->k_albedo; t.k_depth = params->k_depth;
   t.wf = h->scene.sensor.wf; t.hf = h->scene.sensor.hf; t.sw = h->scene.sensor.sw; t.sh = h->scene.sensor.sh;
   std::memcpy(t.now.origin, h->lens.origin, sizeof t.now.origin); std::memcpy(t.now.m, h->lens.global_, sizeof t.now.m); t.now.sensor_distance = h->lens.sensor_distance;
   if (t.mode == TEMPORAL_MOVED_LENS) {                                        // (the only mode that reads it)
-    const DevLens& before = h->history_lens;
+    const DevLens& before = img.history_lens;
     std::memcpy(t.before.origin, before.origin, sizeof t.before.origin); std::memcpy(t.before.m, before.local_, sizeof t.before.m); t.before.sensor_distance = before.sensor_distance;
   }
-  const dim3 tiles(static_cast<uint32_t>(o.n_tiles));
-  hipLaunchKernelGGL(temporal_kernel, tiles, dim3(256), 0, h->stream, t);
-  DenoiseLevelArgs a{};
-  a.guide = h->d_history_guide[next]; a.width = o.width; a.rows = o.rows; a.blocks_x = o.blocks_x;
-  a.k_normal = params->k_normal; a.k_albedo = params->k_albedo; a.k_depth = params->k_depth; a.k_color = params->k_color;
-  for (uint32_t i = 0; i < params->levels; i++) {
-    a.cin = h->d_denoise_color[i & 1u]; a.cout = h->d_denoise_color[(i + 1u) & 1u]; a.step = 1 << i;
-    hipLaunchKernelGGL(denoise_level_kernel, tiles, dim3(256), 0, h->stream, a);
-    a.k_color = a.k_color * 4.0f;                                             // kc_{i+1} = kc_i * 4
-  }
-  const float* filtered = h->d_denoise_color[params->levels & 1u];
-  if (format == AMBER_RESOLVE_MEAN_F32) LaunchResolve<AMBER_RESOLVE_MEAN_F32>(h, filtered, o.mirror, d_out, n_pixels, 1.0f);
-  else if (format == AMBER_RESOLVE_RGB8) LaunchResolve<AMBER_RESOLVE_RGB8>(h, filtered, o.mirror, d_out, n_pixels, 1.0f);
-  else LaunchResolve<AMBER_RESOLVE_RGBA8>(h, filtered, o.mirror, d_out, n_pixels, 1.0f);
-  HIP_TRY(hipGetLastError());
-  if (o.host) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, o.want, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
+  hipLaunchKernelGGL(temporal_kernel, dim3(static_cast<uint32_t>(o.n_tiles)), dim3(256), 0, h->stream, t);
+  const float* filtered = LaunchDenoiseLevels(h, o, img.history_guide[next], params->levels, params->k_normal, params->k_albedo, params->k_depth, params->k_color);
+  AMBER_TRY(WriteBandOutput(h, o, format, filtered, 1.0f, out));
   // the commit: until here the history in use is what it was (the kernel wrote the other pair)
-  h->history_cur = next; h->history_lens = h->lens; h->history_empty = false;
+  img.history_cur = next; img.history_lens = h->lens; img.history_empty = false;
   return AMBER_OK;
 }
 
@@ -205,32 +163,15 @@ int TemporalReset(amber_hip_pt* h) {
   const char* name = "amber_hip_pt_temporal_reset";
   if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
   HIP_TRY(hipSetDevice(h->device));
-  const size_t bytes = static_cast<size_t>(h->local_rows) * h->scene.sensor.w * sizeof(AmberHistoryPixel);
-  // a history never used is empty and reads as zeros already: nothing is allocated for it; an emptied one reads as zeros too
-  if (h->d_history[0] && bytes) HIP_TRY(hipMemsetAsync(h->d_history[h->history_cur], 0, bytes, h->stream));
-  h->history_empty = true;
+  // a history never used is empty and reads as zeros already: nothing is allocated for it (an empty band never has one); an emptied one reads as zeros too
+  DevBuf<float4>& current = h->img.history[h->img.history_cur];
+  if (current) HIP_TRY(hipMemsetAsync(current, 0, static_cast<size_t>(BandPixels(h)) * sizeof(AmberHistoryPixel), h->stream));
+  h->img.history_empty = true;
   return AMBER_OK;
 }
 
-int HistoryDownload(amber_hip_pt* h, AmberHistoryPixel* out) {
-  const char* name = "amber_hip_pt_history_download";
-  if (!h || !out) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or output pointer");
-  HIP_TRY(hipSetDevice(h->device));
-  { const int rc = EnsureHistory(h, name); if (rc != AMBER_OK) return rc; }
-  const size_t n_pixels = static_cast<size_t>(h->local_rows) * h->scene.sensor.w;
-  if (n_pixels) HIP_TRY(hipMemcpyAsync(out, h->d_history[h->history_cur], n_pixels * sizeof(AmberHistoryPixel), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return AMBER_OK;
-}
-
-int DeviceHistory(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) {
-  const char* name = "amber_hip_pt_device_history";
-  if (!h || !dptr) return Fail(AMBER_EINVAL, std::string(name) + ": null handle or pointer");
-  HIP_TRY(hipSetDevice(h->device));
-  { const int rc = EnsureHistory(h, name); if (rc != AMBER_OK) return rc; }
-  *dptr = h->d_history[h->history_cur];                                       // (null for an empty band); the CURRENT history: the next amber_hip_pt_temporal moves it
-  if (n_pixels) *n_pixels = static_cast<uint64_t>(h->local_rows) * h->scene.sensor.w;
-  return AMBER_OK;
-}
+// (the CURRENT history: the next amber_hip_pt_temporal moves it)
+int HistoryDownload(amber_hip_pt* h, AmberHistoryPixel* out) { return BandDownload(h, HistoryBuf, out, "amber_hip_pt_history_download"); }
+int DeviceHistory(amber_hip_pt* h, void** dptr, uint64_t* n_pixels) { return BandPointer(h, HistoryBuf, dptr, n_pixels, "amber_hip_pt_device_history"); }
 
 }  // namespace
