@@ -172,6 +172,7 @@ LAB_SYMBOLS = [
     "amber_hip_kat_cast", "amber_hip_kat_sample", "amber_hip_kat_eye", "amber_hip_kat_trace", "amber_hip_kat_math", "amber_hip_kat_signatures", "amber_hip_pt_signatures",
     "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump", "amber_hip_kat_division",
     "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep", "amber_hip_kat_lt_accumulate", "amber_hip_kat_lt_stage_ms",
+    "amber_hip_kat_light_ray", "amber_hip_kat_lens_response", "amber_hip_kat_radiance", "amber_host_kat_scene_lights",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -272,6 +273,11 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "amber_hip_kat_lt_accumulate"):    # the same
             lib.amber_hip_kat_lt_accumulate.argtypes = [vp, vp, u32]
             lib.amber_hip_kat_lt_stage_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        if hasattr(lib, "amber_hip_kat_light_ray"):        # the same
+            lib.amber_hip_kat_light_ray.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+            lib.amber_hip_kat_lens_response.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+            lib.amber_hip_kat_radiance.argtypes = [vp, u32, vp, vp, vp, vp]
+            lib.amber_host_kat_scene_lights.argtypes = [vp, C.POINTER(FlatLight), C.POINTER(u32)]
     lib.amber_host_cornell_box.restype = vp
     lib.amber_host_cornell_box.argtypes = [C.c_float, C.c_float, u32]
     lib.amber_host_scene_import.restype = vp
@@ -370,6 +376,15 @@ class HostScene:
         objs, mats, lens = (FlatObject * no.value)(), (FlatMaterial * nm.value)(), FlatThinLens()
         _check(lib.amber_host_scene_flatten(self._h, objs, C.byref(no), mats, C.byref(nm), C.byref(lens)), host=True)
         return objs, mats, lens
+
+    def lights(self):
+        """Lab build: the light table flatten() computes for amber_hip_pt_create (FlatLight records in the light set's order)."""
+        lib = load_library()
+        n = C.c_uint32(0)
+        _check(lib.amber_host_kat_scene_lights(self._h, None, C.byref(n)), host=True)
+        out = (FlatLight * max(1, n.value))()
+        _check(lib.amber_host_kat_scene_lights(self._h, out, C.byref(n)), host=True)
+        return list(out[:n.value])
 
     def render(self, sensor: Sensor, spp: int, seed: int = 12345, max_depth: int = 0, device: int = 0,
                samples_per_launch: int = 0, algorithm: str = "pt", devices=None):
@@ -843,6 +858,32 @@ class PathTracer:
         p, s = np.ascontiguousarray(pixel, np.uint32), np.ascontiguousarray(sample, np.uint32)
         out = np.empty((len(p), 7), np.float32)
         _check(load_library().amber_hip_kat_eye(self._h, len(p), p.ctypes.data, s.ctypes.data, out.ctypes.data))
+        return out
+
+    def kat_light_ray(self, rng_state):
+        """GenerateLightRay from every XorShift state: (origin, dir, weight, position in the light table, state after)."""
+        st = np.ascontiguousarray(rng_state, np.uint64).copy()
+        n = len(st)
+        o, d, w = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        light = np.empty(n, np.uint32)
+        _check(load_library().amber_hip_kat_light_ray(self._h, n, st.ctypes.data, o.ctypes.data, d.ctypes.data, w.ctypes.data, light.ctypes.data))
+        return o, d, w, light, st
+
+    def kat_lens_response(self, position, direction_out):
+        """LensResponse of every ray: (reached, pixel index, value); pixel and value are 0 where reached is 0."""
+        p, d = _f32(position).reshape(-1, 3), _f32(direction_out).reshape(-1, 3)
+        n = len(p)
+        reached, pixel, value = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.float32)
+        _check(load_library().amber_hip_kat_lens_response(self._h, n, p.ctypes.data, d.ctypes.data, reached.ctypes.data, pixel.ctypes.data,
+                                                          value.ctypes.data))
+        return reached, pixel, value
+
+    def kat_radiance(self, material, normals, dirs_out):
+        """Radiance() of material[i] (index into the handle's material table) for every (normal, dir_out)."""
+        m = np.ascontiguousarray(material, np.uint32)
+        nn, dd = _f32(normals).reshape(-1, 3), _f32(dirs_out).reshape(-1, 3)
+        out = np.empty((len(m), 3), np.float32)
+        _check(load_library().amber_hip_kat_radiance(self._h, len(m), m.ctypes.data, nn.ctypes.data, dd.ctypes.data, out.ctypes.data))
         return out
 
     def kat_trace(self, pixel, sample, max_bounces: int = 16):

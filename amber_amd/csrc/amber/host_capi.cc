@@ -5,6 +5,9 @@
 #include <vector>
 
 #include "../../../include/amber_host.h"
+#ifdef AMBER_LAB
+#include "../../../include/amber_hip_lab.h"
+#endif
 #include "import.h"
 #include "postprocess.h"
 #include "rendering.h"
@@ -107,6 +110,22 @@ int amber_host_scene_flatten(const amber_host_scene* s, AmberFlatObject* objects
     return AMBER_OK;
   } catch (const std::exception& e) { return Fail(AMBER_EINVAL, e.what()); }
 }
+
+#ifdef AMBER_LAB
+// lab build only (include/amber_hip_lab.h): the light table of Flatten(), which amber_host_scene_flatten does not hand out
+int amber_host_kat_scene_lights(const amber_host_scene* s, AmberFlatLight* lights, uint32_t* n_lights) {
+  if (!s || !n_lights) return Fail(AMBER_EINVAL, "null argument");
+  try {
+    const scene::FlatScene fs = s->scene.Flatten();
+    if (lights) {
+      if (*n_lights < fs.lights.size()) return Fail(AMBER_EINVAL, "light buffer too small");
+      if (!fs.lights.empty()) std::memcpy(lights, fs.lights.data(), fs.lights.size() * sizeof(AmberFlatLight));
+    }
+    *n_lights = static_cast<uint32_t>(fs.lights.size());
+    return AMBER_OK;
+  } catch (const std::exception& e) { return Fail(AMBER_EINVAL, e.what()); }
+}
+#endif
 
 int amber_host_pt_create(const amber_host_scene* s, const AmberSensor* sensor, const AmberPtParams* params, amber_hip_pt** out) {
   if (!s) return Fail(AMBER_EINVAL, "null scene");

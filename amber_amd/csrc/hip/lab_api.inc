@@ -143,6 +143,66 @@ int amber_hip_kat_eye(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const 
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_light_ray(amber_hip_pt* h, uint32_t n, uint64_t* rng_state, float* out_origin, float* out_dir, float* out_weight,
+                            uint32_t* out_light) { return Guarded("amber_hip_kat_light_ray", [&]() -> int {
+  if (!h || !rng_state || !out_origin || !out_dir || !out_weight || !out_light) return Fail(AMBER_EINVAL, "null argument");
+  if (h->scene.n_lights == 0) return Fail(AMBER_EINVAL, "amber_hip_kat_light_ray: the handle's scene has no lights");
+  if (h->lights_stale) return Fail(AMBER_EINVAL, "lights are stale after amber_hip_pt_update_objects: re-create the handle");
+  if (n == 0) return AMBER_OK;
+  if (n > 0x3fffffffu) return Fail(AMBER_EINVAL, "too many items for one call");
+  HIP_TRY(hipSetDevice(h->device));
+  DevBuf<uint64_t> d_r; DevBuf<float> d_o, d_d, d_w; DevBuf<uint32_t> d_l;
+  HIP_TRY(d_r.alloc(n)); HIP_TRY(d_o.alloc(3ull * n)); HIP_TRY(d_d.alloc(3ull * n)); HIP_TRY(d_w.alloc(3ull * n)); HIP_TRY(d_l.alloc(n));
+  HIP_TRY(hipMemcpy(d_r.p, rng_state, 8ull * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kat_light_ray_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_r.p, d_o.p, d_d.p, d_w.p, d_l.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(rng_state, d_r.p, 8ull * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_origin, d_o.p, 12ull * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_dir, d_d.p, 12ull * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, d_w.p, 12ull * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_light, d_l.p, 4ull * n, hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
+
+int amber_hip_kat_lens_response(amber_hip_pt* h, uint32_t n, const float* position, const float* direction_out, uint32_t* out_reached,
+                                uint32_t* out_pixel, float* out_value) { return Guarded("amber_hip_kat_lens_response", [&]() -> int {
+  if (!h || !position || !direction_out || !out_reached || !out_pixel || !out_value) return Fail(AMBER_EINVAL, "null argument");
+  if (n == 0) return AMBER_OK;
+  if (n > 0x3fffffffu) return Fail(AMBER_EINVAL, "too many items for one call");
+  HIP_TRY(hipSetDevice(h->device));
+  DevBuf<float> d_p, d_d, d_v; DevBuf<uint32_t> d_r, d_x;
+  HIP_TRY(d_p.alloc(3ull * n)); HIP_TRY(d_d.alloc(3ull * n)); HIP_TRY(d_v.alloc(n)); HIP_TRY(d_r.alloc(n)); HIP_TRY(d_x.alloc(n));
+  HIP_TRY(hipMemcpy(d_p.p, position, 12ull * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_d.p, direction_out, 12ull * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kat_lens_response_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_p.p, d_d.p, d_r.p, d_x.p, d_v.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(out_reached, d_r.p, 4ull * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_pixel, d_x.p, 4ull * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_value, d_v.p, 4ull * n, hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
+
+int amber_hip_kat_radiance(amber_hip_pt* h, uint32_t n, const uint32_t* material, const float* normals, const float* dirs_out,
+                           float* out) { return Guarded("amber_hip_kat_radiance", [&]() -> int {
+  if (!h || !material || !normals || !dirs_out || !out) return Fail(AMBER_EINVAL, "null argument");
+  if (n == 0) return AMBER_OK;
+  if (n > 0x3fffffffu) return Fail(AMBER_EINVAL, "too many items for one call");
+  for (uint32_t i = 0; i < n; i++) if (material[i] >= h->n_materials) return Fail(AMBER_EINVAL, "material index out of range");
+  HIP_TRY(hipSetDevice(h->device));
+  DevBuf<uint32_t> d_m; DevBuf<float> d_n, d_d, d_o;
+  HIP_TRY(d_m.alloc(n)); HIP_TRY(d_n.alloc(3ull * n)); HIP_TRY(d_d.alloc(3ull * n)); HIP_TRY(d_o.alloc(3ull * n));
+  HIP_TRY(hipMemcpy(d_m.p, material, 4ull * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_n.p, normals, 12ull * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_d.p, dirs_out, 12ull * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kat_radiance_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_m.p, d_n.p, d_d.p, d_o.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(out, d_o.p, 12ull * n, hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
+
 int amber_hip_kat_trace(amber_hip_pt* h, uint32_t n, const uint32_t* pixel, const uint32_t* sample,
                         uint32_t max_bounces, uint32_t* out_records, uint32_t* out_casts) { return Guarded("amber_hip_kat_trace", [&]() -> int {
   if (h && h->hit_engine == AMBER_ENGINE_REFERENCE_BVH) return Fail(AMBER_EINVAL, kKatNoRefBvh);

@@ -55,6 +55,43 @@ __global__ void kat_eye_kernel(const DevScene sc, uint64_t hashed_seed, uint32_t
   p[0] = o.x; p[1] = o.y; p[2] = o.z; p[3] = d.x; p[4] = d.y; p[5] = d.z; p[6] = w;
 }
 
+// The start of a light path from the item's own state, as pt_megakernel's light instantiation calls it.  out_light: the position in the light
+// table, formed once more from the first draw (GenerateLightRay hands back only what a path needs).
+__global__ void kat_light_ray_kernel(const DevScene sc, uint32_t n, uint64_t* rng_state, float* out_org, float* out_dir, float* out_w, uint32_t* out_light) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t rng = rng_state[i];
+  uint64_t first = rng;
+  const float x = Uniform(first) * sc.total_power;                        // the choice, recomputed: the first draw against the running sums
+  uint32_t pos = 0;
+  while (pos + 1u < sc.n_lights && sc.lights[pos].cum_power < x) ++pos;
+  V3 o, d, w; int origin_slot;
+  GenerateLightRay(sc, rng, o, d, w, origin_slot);
+  rng_state[i] = rng;
+  out_org[3 * i] = o.x; out_org[3 * i + 1] = o.y; out_org[3 * i + 2] = o.z;
+  out_dir[3 * i] = d.x; out_dir[3 * i + 1] = d.y; out_dir[3 * i + 2] = d.z;
+  out_w[3 * i] = w.x; out_w[3 * i + 1] = w.y; out_w[3 * i + 2] = w.z;
+  out_light[i] = pos;
+}
+
+__global__ void kat_lens_response_kernel(const DevScene sc, uint32_t n, const float* position, const float* direction_out,
+                                         uint32_t* out_reached, uint32_t* out_pixel, float* out_value) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t pixel = 0u; float value = 0.f;
+  const bool reached = LensResponse(sc, ld3(position + 3 * i), ld3(direction_out + 3 * i), pixel, value);
+  out_reached[i] = reached ? 1u : 0u;
+  out_pixel[i] = reached ? pixel : 0u;
+  out_value[i] = reached ? value : 0.f;
+}
+
+__global__ void kat_radiance_kernel(const DevScene sc, uint32_t n, const uint32_t* material, const float* normals, const float* dirs_out, float* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 r = Radiance(sc.materials[material[i]], ld3(normals + 3 * i), ld3(dirs_out + 3 * i));
+  out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+
 template <int kEngine>
 __global__ void kat_trace_kernel(const DevScene sc, uint64_t hashed_seed, uint32_t n, const uint32_t* pixel,
                                  const uint32_t* sample, uint32_t max_bounces, uint32_t* out_records, uint32_t* out_casts) {

@@ -29,6 +29,26 @@ int amber_hip_kat_sample(amber_hip_pt*, uint32_t n, const uint32_t* material /*n
                          const float* dirs_out, uint64_t* rng_state /*n, in/out*/, float* out_dir_in, float* out_weight);
 /* eye rays for (pixel index, sample) pairs: out = origin[3] dir[3] weight */
 int amber_hip_kat_eye(amber_hip_pt*, uint32_t n, const uint32_t* pixel, const uint32_t* sample, float* out7);
+/* The start of a light path (GenerateLightRay: the light chosen by cumulative power, a point of its surface, a cosine-weighted direction,
+ * weight = irradiance / pdf_area) exactly as the light-tracing kernel calls it, item i from the XorShift state rng_state[i]; the state after
+ * the call is written back, so the number of draws shows.  out_light[i] = the position of the chosen light in the handle's light table
+ * (AmberFlatScene.lights order; amber_host_kat_scene_lights gives that table for a host scene).  AMBER_EINVAL, without a launch, for a handle
+ * whose scene has no lights or whose lights are stale. */
+int amber_hip_kat_light_ray(amber_hip_pt*, uint32_t n, uint64_t* rng_state /*n, in/out*/, float* out_origin /*n*3*/, float* out_dir /*n*3*/,
+                            float* out_weight /*n*3*/, uint32_t* out_light /*n*/);
+/* Lens::Response of Ray(position[i], direction_out[i]) through LensResponse, the inverse camera of the light-tracing kernel (and the
+ * arithmetic amber_hip_pt_temporal's reprojection repeats): out_reached[i] = 1 when the ray reaches the sensor, then out_pixel[i] = x + y * width
+ * and out_value[i] = the response; both are written as 0 where out_reached[i] = 0. */
+int amber_hip_kat_lens_response(amber_hip_pt*, uint32_t n, const float* position /*n*3*/, const float* direction_out /*n*3*/,
+                                uint32_t* out_reached /*n*/, uint32_t* out_pixel /*n*/, float* out_value /*n*/);
+/* Radiance() of material[i] (an index into the handle's material table; AMBER_EINVAL when out of range) seen from dir_out at a surface with
+ * the given normal: the emitter's rho where dir_out . normal > 0, else 0. */
+int amber_hip_kat_radiance(amber_hip_pt*, uint32_t n, const uint32_t* material /*n*/, const float* normals /*n*3*/, const float* dirs_out /*n*3*/,
+                           float* out /*n*3*/);
+/* The light table Scene::Flatten() hands to amber_hip_pt_create for this host scene (no device needed): call with lights = NULL for the
+ * count, then with a buffer of *n_lights records. */
+struct amber_host_scene;
+int amber_host_kat_scene_lights(const struct amber_host_scene*, AmberFlatLight* lights, uint32_t* n_lights);
 /* full per-path trace: for item i writes up to max_bounces records of
  * {object(int32 as float bits), t, pos[3], weight[3], measurement[3]} (11 x 4 bytes) and the cast count */
 int amber_hip_kat_trace(amber_hip_pt*, uint32_t n, const uint32_t* pixel, const uint32_t* sample,

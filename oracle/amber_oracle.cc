@@ -1262,12 +1262,11 @@ namespace {
 
 struct SplatRecord { uint32_t path, sample, bounce, pixel; float rgb[3]; };
 
-// LightTracing::Thread::Render algorithm_lt.cc:125-163 for one light path; appends the splats it makes.
-uint32_t TraceLightPath(const oracle_scene& sc, const Sensor& S, uint32_t path, uint32_t sample, Sampler& smp, const Math& M,
-                        uint32_t max_depth, std::vector<SplatRecord>& out) {
+// LightSet::GenerateRay light_set.h:84-104: the start of a light path (the scene has lights).  TraceLightPath begins with it and
+// oracle_light_rays exports it: one code path.
+struct LightRay { V3 origin, dir, weight; uint32_t object; };
+LightRay GenerateLightRay(const oracle_scene& sc, Sampler& smp, const Math& M) {
   const LightSet& ls = sc.light_set;
-  if (ls.lights.empty()) return 0;
-  // LightSet::GenerateRay light_set.h:84-104
   const float x = UniformF(ls.total(), smp);
   std::size_t pos = 0;
   while (pos < ls.lights.size() && ls.lights[pos].cum_power < x) pos++;          // std::lower_bound
@@ -1278,8 +1277,16 @@ uint32_t TraceLightPath(const oracle_scene& sc, const Sensor& S, uint32_t path, 
   SampleSurfacePoint(lobj, smp, M, origin, normal);
   const V3 dir = HemispherePSA(normal, smp, M);
   const float pdf_area = (light.irradiance.x + light.irradiance.y + light.irradiance.z) / ls.total();   // light_set.h:107-111
-  Ray ray{origin, dir};
-  V3 weight = light.irradiance / splat(pdf_area);
+  return LightRay{origin, dir, light.irradiance / splat(pdf_area), light.object};
+}
+
+// LightTracing::Thread::Render algorithm_lt.cc:125-163 for one light path; appends the splats it makes.
+uint32_t TraceLightPath(const oracle_scene& sc, const Sensor& S, uint32_t path, uint32_t sample, Sampler& smp, const Math& M,
+                        uint32_t max_depth, std::vector<SplatRecord>& out) {
+  if (sc.light_set.lights.empty()) return 0;
+  const LightRay start = GenerateLightRay(sc, smp, M);
+  Ray ray{start.origin, start.dir};
+  V3 weight = start.weight;
   const float size_f = static_cast<float>(S.w * S.h);
   uint32_t casts = 0;
   for (;;) {
@@ -1777,6 +1784,48 @@ void oracle_radiance(const oracle_material* m, const float normal[3], const floa
   Material mm; mm.kind = m->kind; mm.rho = v3(m->rho[0], m->rho[1], m->rho[2]); mm.param = m->param;
   const V3 r = Radiance(mm, v3(normal[0], normal[1], normal[2]), v3(dir_out[0], dir_out[1], dir_out[2]));
   out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+// The start of n light paths (GenerateLightRay above, the head of TraceLightPath), item i with the XorShift state states[i], which is
+// advanced.  object = the scene index of the chosen light.  Returns -1, with nothing written, for a scene without lights.
+int oracle_light_rays(const oracle_scene* sc, uint32_t n, uint64_t* states, int math, float* origin, float* dir, float* weight, uint32_t* object) {
+  if (sc->light_set.lights.empty()) return -1;
+  const Math M{math};
+  for (uint32_t i = 0; i < n; i++) {
+    XorShiftSampler smp(states[i]);
+    const LightRay r = GenerateLightRay(*sc, smp, M);
+    states[i] = smp.s;
+    origin[3 * i] = r.origin.x; origin[3 * i + 1] = r.origin.y; origin[3 * i + 2] = r.origin.z;
+    dir[3 * i] = r.dir.x; dir[3 * i + 1] = r.dir.y; dir[3 * i + 2] = r.dir.z;
+    weight[3 * i] = r.weight.x; weight[3 * i + 1] = r.weight.y; weight[3 * i + 2] = r.weight.z;
+    object[i] = r.object;
+  }
+  return 0;
+}
+// Lens::Response of n rays (position, direction_out) as TraceLightPath asks for it: reached (0 / 1), pixel = x + y * width and value,
+// both 0 where the ray does not reach the sensor.
+void oracle_lens_responses(const oracle_scene* sc, const oracle_sensor* sensor, uint32_t n, const float* position, const float* direction_out,
+                           int math, uint32_t* reached, uint32_t* pixel, float* value) {
+  const Sensor S{sensor->width, sensor->height, sensor->scene_width, sensor->scene_height};
+  const Math M{math};
+  for (uint32_t i = 0; i < n; i++) {
+    uint64_t x = 0, y = 0; float v = 0;
+    const bool ok = LensResponse(sc->lens, S, v3(position[3 * i], position[3 * i + 1], position[3 * i + 2]),
+                                 v3(direction_out[3 * i], direction_out[3 * i + 1], direction_out[3 * i + 2]), M, x, y, v);
+    reached[i] = ok ? 1u : 0u;
+    pixel[i] = ok ? static_cast<uint32_t>(x + y * S.w) : 0u;
+    value[i] = ok ? v : 0.0f;
+  }
+}
+// The light set in its order (ascending power): the scene index, the running sum of the powers and the irradiance (3 floats) of every
+// light.  Returns their number; the arrays may be NULL.
+uint32_t oracle_scene_get_lights(const oracle_scene* sc, uint32_t* object, float* cum_power, float* irradiance) {
+  const std::vector<Light>& ls = sc->light_set.lights;
+  for (std::size_t i = 0; i < ls.size(); i++) {
+    if (object) object[i] = ls[i].object;
+    if (cum_power) cum_power[i] = ls[i].cum_power;
+    if (irradiance) { irradiance[3 * i] = ls[i].irradiance.x; irradiance[3 * i + 1] = ls[i].irradiance.y; irradiance[3 * i + 2] = ls[i].irradiance.z; }
+  }
+  return static_cast<uint32_t>(ls.size());
 }
 void oracle_eye_ray(const oracle_scene* sc, const oracle_sensor* sensor, uint32_t px, uint32_t py, const double u[5],
                     int math, float origin[3], float normal[3], float dir[3], float* weight, uint32_t* blade) {

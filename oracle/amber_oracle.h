@@ -195,6 +195,17 @@ uint32_t oracle_sample_material(const oracle_material* m, const float normal[3],
 uint32_t oracle_sample_material_xorshift(const oracle_material* m, const float normal[3], const float dir_out[3], uint64_t state,
                                          int importance, int math, float dir_in[3], float weight[3]);
 void oracle_radiance(const oracle_material* m, const float normal[3], const float dir_out[3], float out[3]);
+/* Light tracing stage by stage, in batches of n items (arrays of n or 3 n entries).
+ * oracle_light_rays: the start of a light path -- LightSet::GenerateRay, the first lines of the tracer behind oracle_render_lt_xorshift,
+ * the same function -- from the XorShift state states[i], which is advanced; object = the scene index of the chosen light.  Returns -1
+ * (nothing written) for a scene without lights, else 0.
+ * oracle_lens_responses: Lens::Response of Ray(position, direction_out); pixel = x + y * width; pixel and value are 0 where reached is 0.
+ * oracle_scene_get_lights: the light set in its order (ascending power): scene index, running sum of the powers, irradiance (3 floats);
+ * returns the number of lights, the arrays may be NULL. */
+int oracle_light_rays(const oracle_scene*, uint32_t n, uint64_t* states, int math, float* origin, float* dir, float* weight, uint32_t* object);
+void oracle_lens_responses(const oracle_scene*, const oracle_sensor*, uint32_t n, const float* position, const float* direction_out,
+                           int math, uint32_t* reached, uint32_t* pixel, float* value);
+uint32_t oracle_scene_get_lights(const oracle_scene*, uint32_t* object, float* cum_power, float* irradiance);
 /* eye ray: 5 uniforms in draw order (blade, tri-u, tri-v, jitter-Y, jitter-X -- g++ order) */
 void oracle_eye_ray(const oracle_scene*, const oracle_sensor*, uint32_t px, uint32_t py, const double u[5],
                     int math, float origin[3], float normal[3], float dir[3], float* weight, uint32_t* blade);

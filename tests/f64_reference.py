@@ -1,4 +1,4 @@
-"""The path's primitives, materials and eye rays once more, in binary64 numpy, from their geometric and optical definitions.
+"""The path's primitives, materials, eye rays, light table, light rays and lens response once more, in binary64 numpy, from their geometric and optical definitions.
 
 The oracle and the kernels are the same function by construction (bit parity); this module is a third statement that shares
 no order of operations with either.  It imports numpy only.  Inputs are binary32 values widened exactly.  Every function
@@ -432,6 +432,128 @@ def eye_ray_to_pixel(lens_kind, lens_origin, rotation, focus_distance, sensor_di
             inside = np.minimum(inside, dot(np.cross(e, P - Va), nh) / norm(e))
         dist = np.minimum(dist, np.maximum(off, np.maximum(-inside, 0.0)))
     return dict(sensor=sensor, pixel=pixel, focus=focus, blade_distance=dist)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# light paths: the light table, the start of a path, the lens response
+# ------------------------------------------------------------------------------------------------------------------
+def surface_area(kind, p):
+    p = np.asarray(p, np.float64)
+    if kind == TRIANGLE:
+        return 0.5 * float(norm(np.cross(p[3:6] - p[:3], p[6:9] - p[:3])))
+    if kind == SPHERE:
+        return 4.0 * np.pi * p[3] ** 2
+    if kind == DISK:
+        return np.pi * p[6] ** 2
+    return 2.0 * np.pi * p[6] * p[7]
+
+
+def light_table(kinds, params, materials):
+    """The light set of a scene, from its definition.  materials: per object the emitted radiance rho (3,), or None for an object that is no
+    emitter.  Irradiance = pi rho, power = area x sum(irradiance); lights in ascending order of power (equal powers in scene order), with
+    running sums.  Returns object, kind, params, irradiance (n, 3), power, cum_power, total, pdf_area = sum(irradiance) / total."""
+    idx = [i for i, m in enumerate(materials) if m is not None]
+    irr = np.array([np.pi * np.asarray(materials[i], np.float64) for i in idx]).reshape(len(idx), 3)
+    power = np.array([surface_area(int(kinds[i]), params[i]) * irr[k].sum() for k, i in enumerate(idx)])
+    order = np.argsort(power, kind="stable")
+    obj = np.array(idx, np.int64)[order]
+    cum = np.cumsum(power[order])
+    total = float(cum[-1]) if len(cum) else 0.0
+    return dict(object=obj, kind=np.asarray(kinds, np.int64)[obj], params=np.asarray(params, np.float64)[obj], irradiance=irr[order], power=power[order],
+                cum_power=cum, total=total, pdf_area=irr[order].sum(1) / total if len(cum) else np.zeros(0))
+
+
+LIGHT_DRAWS = 5                                    # the choice, two for the surface point, two for the direction: every kind
+
+
+def light_ray(table, state, side=(0.0, False)):
+    """The start of a light path for n sampler states (uint64): the light = the first one whose cumulative power >= u x total; a point of its
+    surface -- triangle: barycentric (u, v), reflected to (1 - u, 1 - v) where u + v >= 1; sphere: centre + r (r0 cos phi, r0 sin phi,
+    sqrt(1 - r0^2)) with r0 = 2 u - 1 in [-1, 1), which is NOT the uniform sphere (it covers z >= 0 of the local frame only); disk: centre +
+    sqrt(u r^2) (a cos theta + b sin theta) on the frame (a, b) of its normal; cylinder: centre + u h axis + r (a cos theta + b sin theta) --
+    then a cosine-weighted direction about the surface normal there (triangle: unit(E1 x E2); sphere, cylinder: the radial unit vector; disk:
+    the normal as given); weight = irradiance / pdf_area.
+    side = (b_choice, other_axis): the answer with the choice taken as if u were larger by b_choice and the direction's frame on the other
+    axis.  The fold has no side: the draws are multiples of 2^-24, rounding their sum to binary32 is monotone and 1 is a binary32 number, so
+    "u + v >= 1" is decided as in exact arithmetic -- also where u + v = 1 exactly.  Returns light (position in the table), object, origin,
+    normal, dir, weight, draws, state (after), and the conditioning: cond_choice (|u - cum_k / total|, nearest k), cond_axis (||n.x| - |n.y||
+    of the normal where it is computed), cond_root (1 - r0^2 for the sphere, where its square root is not Lipschitz), cond = their minimum."""
+    b_choice, other_axis = side
+    st = np.array(state, np.uint64).copy()
+    n = len(st)
+    b_choice = np.broadcast_to(b_choice, (n,))
+    u = [xorshift_uniform(st) for _ in range(LIGHT_DRAWS)]
+    cum, total = table["cum_power"], table["total"]
+    edges = cum[:-1] / total                                              # the last light ends at u = 1, which is never drawn
+    light = np.minimum((edges[None, :] < (u[0] + b_choice)[:, None]).sum(1), len(cum) - 1)
+    cond_choice = np.abs(edges[None, :] - u[0][:, None]).min(1) if len(edges) else np.full(n, np.inf)
+    origin, normal = np.zeros((n, 3)), np.zeros((n, 3))
+    cond_root = np.full(n, np.inf)
+    for k in range(len(cum)):
+        s = light == k
+        if not s.any():
+            continue
+        kind, p = int(table["kind"][k]), table["params"][k]
+        a, b = u[1][s], u[2][s]
+        if kind == TRIANGLE:
+            A, B, Cc = p[:3], p[3:6], p[6:9]
+            fold = a + b >= 1.0
+            a, b = np.where(fold, 1.0 - a, a), np.where(fold, 1.0 - b, b)
+            origin[s] = (1.0 - a - b)[:, None] * A + a[:, None] * B + b[:, None] * Cc
+            normal[s] = unit(np.cross(B - A, Cc - A))
+        elif kind == SPHERE:
+            r0, phi = 2.0 * a - 1.0, 2.0 * np.pi * b
+            root = np.sqrt(np.maximum(1.0 - r0 * r0, 0.0))
+            normal[s] = np.stack([r0 * np.cos(phi), r0 * np.sin(phi), root], 1)
+            origin[s] = p[:3] + p[3] * normal[s]
+            cond_root[s] = 1.0 - r0 * r0
+        else:
+            N = np.broadcast_to(p[3:6], (int(s.sum()), 3))
+            fa, fb = _frame(N)
+            theta = 2.0 * np.pi * b
+            ring = fa * np.cos(theta)[:, None] + fb * np.sin(theta)[:, None]
+            if kind == DISK:
+                origin[s] = p[:3] + ring * np.sqrt(a * p[6] * p[6])[:, None]
+                normal[s] = N
+            else:
+                origin[s] = p[:3] + N * (a * p[7])[:, None] + ring * p[6]
+                normal[s] = unit(ring)
+    cond_axis = np.where(table["kind"][light] == DISK, np.inf, np.abs(np.abs(normal[:, 0]) - np.abs(normal[:, 1])))      # a disk's normal is its input: decided exactly
+    d = _lobe(normal, np.sqrt(u[3]), u[4], other_axis)
+    weight = table["irradiance"][light] / table["pdf_area"][light][:, None]
+    return dict(light=light, object=table["object"][light], origin=origin, normal=normal, dir=d, weight=weight, draws=np.full(n, LIGHT_DRAWS), state=st,
+                u=np.stack(u, 1), cond_choice=cond_choice, cond_axis=cond_axis, cond_root=cond_root,
+                cond=_smin(cond_choice, cond_axis, cond_root))
+
+
+def lens_response(lens_kind, lens_origin, rotation, focus_distance, sensor_distance, width, height, sensor_w, sensor_h, position, direction_out):
+    """The inverse camera as the light tracer asks for it: does the ray that arrives at `position` on the lens from direction_out (pointing
+    from the lens into the scene: an eye ray's own direction) reach the sensor, at which pixel, with which value?  Built on eye_ray_to_pixel.
+    Thin lens: no response for a direction with local z >= 0 (from behind); value = (unit(sensor_point - aperture_point).z / direction.z)^4,
+    direction as given (not normalised).  Pinhole: value 1, no refusal by sign.
+    Returns reached, pixel (n, 2) real-valued, index (floor, clamped: x + y width), value, z (the local z of the direction),
+    edge: the distance of the real-valued pixel position from the nearest pixel edge (sensor edges included), in pixels."""
+    R = np.asarray(rotation, np.float64).reshape(3, 3)
+    Rinv = np.linalg.inv(R)
+    pos, do = np.asarray(position, np.float64), np.asarray(direction_out, np.float64)
+    with np.errstate(all="ignore"):
+        r = eye_ray_to_pixel(lens_kind, lens_origin, rotation, focus_distance, sensor_distance, np.zeros((0, 3, 3)), width, height, sensor_w, sensor_h, pos, do)
+        dl = do @ Rinv.T
+        pix = r["pixel"]
+        size = np.array([width, height], np.float64)
+        inside = np.isfinite(pix).all(1) & (pix >= 0).all(1) & (pix < size).all(1)
+        if lens_kind == 1:
+            reached, value = inside, np.ones(len(pos))
+        else:
+            reached = inside & (dl[:, 2] < 0)
+            ap = (pos - np.asarray(lens_origin, np.float64)) @ Rinv.T
+            sp = np.concatenate([r["sensor"], np.full((len(pos), 1), float(sensor_distance))], 1)
+            value = (unit(sp - ap)[:, 2] / dl[:, 2]) ** 4
+        cell = np.minimum(np.floor(np.where(np.isfinite(pix), pix, 0.0)), size - 1)
+        index = np.where(reached, cell[:, 0] + cell[:, 1] * width, 0).astype(np.int64)
+        edge = np.abs(pix - np.clip(np.round(pix), 0.0, size)).min(1)
+        edge = np.where(np.isfinite(edge), edge, np.inf)
+    return dict(reached=reached, pixel=pix, index=index, value=np.where(reached, value, 0.0), z=dl[:, 2], edge=edge)
 
 
 if __name__ == "__main__":

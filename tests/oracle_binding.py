@@ -107,6 +107,11 @@ def load():
     L.oracle_sample_material_xorshift.restype = u32
     L.oracle_sample_material_xorshift.argtypes = [C.POINTER(OMaterial), vp, vp, u64, C.c_int, C.c_int, vp, vp]
     L.oracle_radiance.argtypes = [C.POINTER(OMaterial), C.POINTER(f), C.POINTER(f), C.POINTER(f)]
+    L.oracle_light_rays.restype = C.c_int
+    L.oracle_light_rays.argtypes = [vp, u32, vp, C.c_int, vp, vp, vp, vp]
+    L.oracle_lens_responses.argtypes = [vp, C.POINTER(OSensor), u32, vp, vp, C.c_int, vp, vp, vp]
+    L.oracle_scene_get_lights.restype = u32
+    L.oracle_scene_get_lights.argtypes = [vp, vp, vp, vp]
     L.oracle_eye_ray.argtypes = [vp, C.POINTER(OSensor), u32, u32, C.POINTER(C.c_double), C.c_int, C.POINTER(f), C.POINTER(f),
                                  C.POINTER(f), C.POINTER(f), C.POINTER(u32)]
     L.oracle_mt_uniforms.argtypes = [u64, u32, vp, vp, vp]
@@ -264,6 +269,32 @@ class Scene:
         pos, nrm = (C.c_float * 3)(), (C.c_float * 3)()
         idx = self.L.oracle_cast(self.h, f3(o), f3(d), C.byref(t), pos, nrm)
         return idx, np.float32(t.value), np.array(pos[:], np.float32), np.array(nrm[:], np.float32)
+
+    def light_rays(self, states, math=None):
+        """oracle_light_rays: (origin, dir, weight, scene index of the chosen light, states after) -- the head of the light tracer."""
+        st = np.ascontiguousarray(states, np.uint64).copy()
+        n = len(st)
+        o, d, w = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        obj = np.zeros(n, np.uint32)
+        if self.L.oracle_light_rays(self.h, n, st.ctypes.data, _m(math), o.ctypes.data, d.ctypes.data, w.ctypes.data, obj.ctypes.data) != 0:
+            raise ValueError("this oracle scene has no lights")
+        return o, d, w, obj, st
+
+    def lens_responses(self, w, h, position, direction_out, math=None):
+        """oracle_lens_responses on a w x h sensor: (reached, pixel index, value)."""
+        s = sensor(w, h)
+        p, d = np.ascontiguousarray(position, np.float32).reshape(-1, 3), np.ascontiguousarray(direction_out, np.float32).reshape(-1, 3)
+        n = len(p)
+        reached, pixel, value = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        self.L.oracle_lens_responses(self.h, C.byref(s), n, p.ctypes.data, d.ctypes.data, _m(math), reached.ctypes.data, pixel.ctypes.data, value.ctypes.data)
+        return reached, pixel, value
+
+    def lights(self):
+        """The light set in its order: (scene index (n,), cumulative power (n,), irradiance (n, 3))."""
+        n = self.L.oracle_scene_get_lights(self.h, None, None, None)
+        obj, cum, irr = np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        self.L.oracle_scene_get_lights(self.h, obj.ctypes.data, cum.ctypes.data, irr.ctypes.data)
+        return obj, cum, irr
 
     def objects(self):
         out = []

@@ -129,10 +129,14 @@ def test_the_product_exports_the_function_and_not_the_hook(amber):
     """A child process that loads only libamber_hip.so."""
     lib = ROOT / "amber_amd" / "lib" / amber.api.PRODUCT_LIB
     code = ("import ctypes, json, sys; lib = ctypes.CDLL(sys.argv[1]); "
-            "print(json.dumps({n: hasattr(lib, n) for n in ('amber_hip_lt_render_pass', 'amber_hip_lt_trace', 'amber_hip_kat_lt_accumulate', 'amber_hip_kat_lt_stage_ms')}))")
+            "print(json.dumps({n: hasattr(lib, n) for n in ('amber_hip_lt_render_pass', 'amber_hip_lt_trace', 'amber_hip_kat_lt_accumulate', 'amber_hip_kat_lt_stage_ms', "
+            "'amber_hip_kat_light_ray', 'amber_hip_kat_lens_response', 'amber_hip_kat_radiance', 'amber_host_kat_scene_lights')}))")
     out = subprocess.run([sys.executable, "-c", code, str(lib)], capture_output=True, text=True, check=True).stdout
-    assert json.loads(out) == {"amber_hip_lt_render_pass": True, "amber_hip_lt_trace": True, "amber_hip_kat_lt_accumulate": False, "amber_hip_kat_lt_stage_ms": False}
+    assert json.loads(out) == {"amber_hip_lt_render_pass": True, "amber_hip_lt_trace": True, "amber_hip_kat_lt_accumulate": False, "amber_hip_kat_lt_stage_ms": False,
+                               "amber_hip_kat_light_ray": False, "amber_hip_kat_lens_response": False, "amber_hip_kat_radiance": False,
+                               "amber_host_kat_scene_lights": False}
     assert "amber_hip_lt_render_pass" in amber.api.ABI_SYMBOLS and "amber_hip_kat_lt_accumulate" in amber.api.LAB_SYMBOLS
+    assert {"amber_hip_kat_light_ray", "amber_hip_kat_lens_response", "amber_hip_kat_radiance", "amber_host_kat_scene_lights"} <= set(amber.api.LAB_SYMBOLS)
 
 
 def test_the_hook_refuses_what_it_cannot_place(amber, scene):
