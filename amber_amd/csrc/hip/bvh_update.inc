@@ -20,7 +20,7 @@
 // carried box never holds a NaN (reset, then grow), so the unions are a function of the scene alone, never of the arrival order.
 
 namespace {
-int ResolvePending(amber_hip_pt* h);                          // pt_host.hip, with the launch code
+int ResolvePending(amber_hip_pt* h);                          // pt_launch.inc
 
 namespace dupd {
 

@@ -92,7 +92,7 @@ static_assert(sizeof(AmberDenoiseParams) == 32, "AmberDenoiseParams is 32 bytes"
 // What every filter does once its arguments have passed: the device, the sums (as resolve: a pass that may have to be repeated must stand) and the AOV buffer
 int BeginFilter(amber_hip_pt* h, const std::string& name) {
   HIP_TRY(hipSetDevice(h->device));
-  if (h->pending && !h->pending_checked) AMBER_TRY(ResolvePending(h));
+  AMBER_TRY(SettlePending(h));
   return EnsureAov(h, name.c_str());
 }
 

@@ -6,7 +6,7 @@
 // the luminance, the moments' BandBuf, the checks of the parameters and of the output arguments and the output tail are image_stage.inc's.
 //
 //   moments_fold_kernel     one thread per band pixel, after a batch has been rendered into the handle's batch buffer instead of the framebuffer (the
-//                           accumulation target of pt_host.hip): fb = fb + B, and the luminance of B / n into the pixel's {m1, m2, batches, pad}
+//                           `target` of pt_launch.inc's launches): fb = fb + B, and the luminance of B / n into the pixel's {m1, m2, batches, pad}
 //                           (one float4 load and store).
 //   dv_moments_kernel       one thread per band pixel: {u1, u2, e, batches} -- the two divisions by `batches` once per pixel, not once per tap.
 //   dv_variance_kernel      one thread per band pixel, denoise_level_kernel's tiling: the (2R + 1)^2 taps of step 3 over the guide and those records;

@@ -17,10 +17,12 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
   uint64_t max_chunks = kMaxPaths / (static_cast<uint64_t>(n_pixels) * AMBER_ACCUM_CHUNK);
   if (max_chunks == 0) return Fail(AMBER_EINVAL, "band too large for the wavefront engine");
   const uint32_t kMaxBounces = 4096;
-  uint32_t done = 0;
-  while (done < n_samples) {
-    uint32_t n = n_samples - done;
-    if (n > max_chunks * AMBER_ACCUM_CHUNK) n = static_cast<uint32_t>(max_chunks * AMBER_ACCUM_CHUNK);
+  const uint64_t cap = max_chunks * AMBER_ACCUM_CHUNK;
+  return SplitSamples(first_sample, n_samples, "band too large for the wavefront engine", [&](uint32_t left, amber_plan::Launch* l) -> int {
+    *l = {left > cap ? static_cast<uint32_t>(cap) : left, 0};
+    return AMBER_OK;
+  }, [&](uint32_t first, const amber_plan::Launch& l, bool*) -> int {
+    const uint32_t n = l.n;
     const uint32_t n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
     const size_t n_paths = static_cast<size_t>(n_chunks) * n_pixels * AMBER_ACCUM_CHUNK;
     // every queue array holds AMBER_WF_SHARDS shards of shard_capacity rays
@@ -41,42 +43,39 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
     WfArgs a;
     a.scene = h->scene; a.meas = meas; a.counts = counts; a.ray_count = h->d_rays; a.hashed_seed = h->hashed_seed;
     a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels;
-    a.first_sample = first_sample + done; a.n_samples = n; a.n_paths = static_cast<uint32_t>(n_paths); a.bounce = 0; a.shard_capacity = static_cast<uint32_t>(shard_capacity);
+    a.first_sample = first; a.n_samples = n; a.n_paths = static_cast<uint32_t>(n_paths); a.bounce = 0; a.shard_capacity = static_cast<uint32_t>(shard_capacity);
     const uint32_t n_blocks = 2048u;                          // 8192 waves = 32 per shard
-    std::pair<Event, Event>* evp = nullptr;
-    AMBER_TRY(AcquireEventPair(h, &evp));
-    auto& ev = *evp;
-    HIP_TRY(hipEventRecord(ev.first.v, h->stream));
-    a.out = q[0]; a.in = q[1];
-    hipLaunchKernelGGL(wf_generate_kernel, dim3(n_blocks), dim3(256), 0, h->stream, a);
-    HIP_TRY(hipGetLastError());
-    uint32_t bounce = 0;
-    for (;;) {
-      const uint32_t burst = bounce < 16 ? 8 : 16;            // launches enqueued before the live count is read back
-      for (uint32_t k = 0; k < burst && bounce < kMaxBounces; k++, bounce++) {
-        a.bounce = bounce; a.in = q[bounce & 1]; a.out = q[(bounce + 1) & 1];
-        WithHitEngine(h->hit_engine, [&](auto engine) -> int {          // instantiated for TWO_PHASE and BVH (the engines WAVEFRONT resolves to), else LIST
-          constexpr int kEngine = decltype(engine)::value == ENGINE_TWO_PHASE || decltype(engine)::value == ENGINE_BVH ? decltype(engine)::value : ENGINE_LIST;
-          hipLaunchKernelGGL(wf_bounce_kernel<kEngine>, dim3(n_blocks), dim3(256), 0, h->stream, a);
-          return AMBER_OK;
-        });
-        HIP_TRY(hipGetLastError());
+    AMBER_TRY(TimedLaunch(h, true, [&]() -> int {
+      a.out = q[0]; a.in = q[1];
+      hipLaunchKernelGGL(wf_generate_kernel, dim3(n_blocks), dim3(256), 0, h->stream, a);
+      HIP_TRY(hipGetLastError());
+      uint32_t bounce = 0;
+      for (;;) {
+        const uint32_t burst = bounce < 16 ? 8 : 16;            // launches enqueued before the live count is read back
+        for (uint32_t k = 0; k < burst && bounce < kMaxBounces; k++, bounce++) {
+          a.bounce = bounce; a.in = q[bounce & 1]; a.out = q[(bounce + 1) & 1];
+          WithHitEngine(h->hit_engine, [&](auto engine) -> int {          // instantiated for TWO_PHASE and BVH (the engines WAVEFRONT resolves to), else LIST
+            constexpr int kEngine = decltype(engine)::value == ENGINE_TWO_PHASE || decltype(engine)::value == ENGINE_BVH ? decltype(engine)::value : ENGINE_LIST;
+            hipLaunchKernelGGL(wf_bounce_kernel<kEngine>, dim3(n_blocks), dim3(256), 0, h->stream, a);
+            return AMBER_OK;
+          });
+          HIP_TRY(hipGetLastError());
+        }
+        unsigned int shard_live[AMBER_WF_SHARDS];
+        HIP_TRY(hipMemcpyAsync(shard_live, counts + static_cast<size_t>(bounce) * AMBER_WF_SHARDS, sizeof shard_live, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        unsigned long long live = 0;
+        for (unsigned int v : shard_live) live += v;
+        if (live == 0) break;
+        if (bounce >= kMaxBounces) return Fail(AMBER_EHIP, "wavefront engine: path longer than 4096 bounces");
       }
-      unsigned int shard_live[AMBER_WF_SHARDS];
-      HIP_TRY(hipMemcpyAsync(shard_live, counts + static_cast<size_t>(bounce) * AMBER_WF_SHARDS, sizeof shard_live, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      unsigned long long live = 0;
-      for (unsigned int v : shard_live) live += v;
-      if (live == 0) break;
-      if (bounce >= kMaxBounces) return Fail(AMBER_EHIP, "wavefront engine: path longer than 4096 bounces");
-    }
-    HIP_TRY(hipEventRecord(ev.second.v, h->stream));
+      return AMBER_OK;
+    }));
     const uint32_t n_elems = n_pixels * 3u;
     hipLaunchKernelGGL(wf_reduce_kernel, dim3((n_elems + 255u) / 256u), dim3(256), 0, h->stream, h->d_fb, meas, n_pixels, n_chunks);
     HIP_TRY(hipGetLastError());
-    done += n;
-  }
-  return AMBER_OK;
+    return AMBER_OK;
+  });
 }
 
 }  // namespace
@@ -342,7 +341,6 @@ int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_s
   if (!h || !out || n_samples == 0) return Fail(AMBER_EINVAL, "bad argument");
   if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
   if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, "signatures come from the work-queue kernels (engines list, two_phase, bvh)");
-  const bool bvh_items = h->hit_engine == AMBER_ENGINE_BVH && !h->bvh_pool && !h->bvh_paths;        // pt_bvh_megakernel's signature instantiation
   const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   const uint64_t n = static_cast<uint64_t>(n_pixels) * n_samples;
   if (n == 0) return AMBER_OK;
@@ -352,12 +350,7 @@ int amber_hip_pt_signatures(amber_hip_pt* h, uint32_t first_sample, uint32_t n_s
   HIP_TRY(hipStreamSynchronize(h->stream));
   AMBER_TRY(Grow(h, h->d_sig, n, "signatures"));
   HIP_TRY(hipMemsetAsync(h->d_sig, 0, n * sizeof(unsigned long long), h->stream));
-  if (bvh_items) {
-    AMBER_TRY(RenderPassBvhItems(h, first_sample, n_samples, n_pixels, h->d_sig));
-  } else {
-    AMBER_TRY(EnsureRecordCapacity(h, RecordSlack(h)));   // records of this launch are discarded
-    AMBER_TRY(LaunchPaths(h, first_sample, n_samples, n_pixels, h->d_sig));
-  }
+  AMBER_TRY(RenderSamples(h, first_sample, n_samples, n_pixels, h->d_fb, h->d_sig));   // (nothing of a signature launch reaches the target)
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(out, h->d_sig, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return AMBER_OK;

@@ -1,7 +1,7 @@
 // lt_accumulate.inc -- amber_hip_lt_render_pass: a light-tracing pass into the handle's framebuffer on the device, in the reference's order.
 // Part of the one translation unit pt_host.hip (kernels are launched from there); see its header comment and include/amber_hip.h for the contract.
 //
-// The trace launch is amber_hip_lt_trace_range's (LtTraceLaunches, pt_host.hip).  It leaves the splat records of one launch in arrival order: the
+// The trace launch is amber_hip_lt_trace_range's (LtTraceLaunches, pt_launch.inc).  It leaves the splat records of one launch in arrival order: the
 // slot of a record comes from an atomic counter.  What is new here takes them to the framebuffer:
 //   1. order      an index permutation sorted by (pixel, pass, path, bounce), all four full 32-bit fields: two stable 64-bit radix sorts (rocPRIM),
 //                 first by (path, bounce), then by (pixel, pass).  The 32-byte records never move; the colours are gathered once, into sorted order.

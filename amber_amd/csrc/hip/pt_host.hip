@@ -1,5 +1,5 @@
-// pt_host.hip -- the ONE translation unit of the gfx950 path-tracing engine: the handle, the host side of every launch and the C ABI
-// (include/amber_hip.h).  The kernels live in files of their own and are included here, where they are launched:
+// pt_host.hip -- the ONE translation unit of the gfx950 path-tracing engine: the handle, create and the C ABI (include/amber_hip.h).  The kernels and
+// the host side of their launches live in files of their own and are included here:
 //   c_boundary.h           the rule of the C ABI: no exception crosses an extern "C" function -- every entry point that can allocate or form a message runs under
 //                          Guarded(name, f) (bad_alloc / system_error -> AMBER_ENOMEM, anything else -> AMBER_EHIP); the thread-local message, Fail, HIP_TRY, AMBER_TRY
 //   pt_args.h              RenderArgs; record emission (accumulation without owners)
@@ -11,6 +11,9 @@
 //   pt_bvh_megakernel.inc  pt_bvh_megakernel: engine BVH on deep trees -- lanes own (pixel, chunk of 8 samples) items, the closest hit is a RESUMABLE
 //                          per-lane traversal of the 2-wide binary16-plane tree advanced in wave rounds until a batch of lanes has finished; per-item
 //                          sums, reduce_partials_kernel.
+//   launch_plan.h, pt_launch.inc   the host side of a render launch: the samples and record slots of the next launch as pure functions (launch_plan.h); grids,
+//                          the timed-launch bracket, the loop that splits a pass into launches, the path-granular launch with its repeat (ResolvePending,
+//                          SettlePending), the item launch, light tracing's launches; where a pass adds its sums is an argument (RenderSamples)
 //   bvh_device_build.inc   AMBER_PT_FLAG_DEVICE_BUILD: engine BVH's tree built by kernels at create (Morton order, radix-tree hierarchy, the host builder's
 //                          bounds / padding / outward binary16 planes) instead of bvh_build.h's binned-SAH build on the host.
 //   bvh_update.inc         amber_hip_pt_update_objects: new object geometry into a live handle -- records converted and checked by a kernel, then the
@@ -64,6 +67,7 @@
 #include "c_boundary.h"
 #include "pt_device.h"
 #include "exact_div.h"
+#include "launch_plan.h"
 #include "bvh_build.h"
 #include "filter_build.h"
 #include "ref_bvh_build.h"
@@ -175,6 +179,41 @@ struct ImageStageBufs {
   DevLens history_lens{};                   // the handle's lens as the call that wrote the current history saw it
   DevBuf<float> batch;                      // amber_hip_pt_render_batch: the sums of the batch in flight, 3 floats, grown on first use
 };
+// amber_hip_pt_cast_rays / amber_hip_pt_occluded (ray_query.inc): allocated by the first query, reused by every later one
+struct RayQueryBufs {
+  DevBuf<int32_t> stack;                    // engine BVH: the global levels of the hybrid traversal stack, [level][thread of the largest query grid]
+  uint64_t stack_threads = 0;               // ... and the threads it was allocated for
+  DevBuf<unsigned int> next;                // engine BVH: the work counter
+  DevBuf<float4> rays;                      // AMBER_RAYS_HOST: staging of the rays and of the results, at most kQueryStageRays rays
+  DevBuf<uint8_t> out;
+};
+// Path-granular launches (pt_launch.inc: LaunchPaths, ResolvePending): bitmap, records in arrival order, measurements in path order, ranks -- and
+// the launch whose record counter the host has not looked at yet
+struct PathLaunchBufs {
+  DevBuf<uint32_t> flags;  bool flags_dirty = true;   // dirty: must be cleared before the next launch
+  DevBuf<uint32_t> touched;
+  DevBuf<uint4> records;   DevBuf<float> sorted;   uint32_t rec_capacity = 0;
+  DevBuf<unsigned int> launch_ctl;          // [0] queue head of the path kernels, [1] = *rec_count, [2..3] = *rays_launch
+  unsigned int* rec_count = nullptr;
+  unsigned long long* rays_launch = nullptr;
+  DevBuf<uint32_t> excl, block_sum;
+  Owned<unsigned int*, hipHostFree> h_rec_count;   // pinned: the record counter of the launch in flight
+  Event pending_event;
+  bool pending = false, pending_checked = true;   // a launch whose record counter has not been looked at yet; checked = it cannot have run out of slots
+  uint32_t pending_first = 0, pending_n = 0;
+  float* pending_target = nullptr;          // where that launch adds its sums (the framebuffer, a batch buffer): a repeat adds to the same buffer
+  bool density_known = false;
+  double rec_density = 0;                   // record slots used per path, as the last launch measured it
+  DevBuf<float> carried;                    // measurements carried across bounces (degenerate paths only)
+};
+// amber_hip_pt_kernel_time: the render kernels between event pairs (pt_launch.inc: TimedLaunch)
+struct LaunchTimer {
+  std::vector<std::pair<Event, Event>> events;   // pool of event pairs, one per timed launch in flight
+  size_t used = 0;
+  uint32_t folded_launches = 0;             // launches already folded into folded_ms
+  double folded_ms = 0;
+  void reset() { used = 0; folded_launches = 0; folded_ms = 0; }
+};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -210,15 +249,9 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   double area_host[4] = {0, 0, 0, 0};       // where the two area measurements of an update are copied to
   DevBuf<uint2> d_ref_stack;                // engine REFERENCE_BVH: the traversal stack of the reference's tree, [level][thread of the largest grid]
   uint64_t ref_stack_threads = 0;           // ... and the threads it was allocated for: no launch that walks that tree may have more (CheckRefStack)
-  // ---- amber_hip_pt_cast_rays / amber_hip_pt_occluded (ray_query.inc): allocated by the first query, reused by every later one
-  DevBuf<int32_t> d_query_stack;            // engine BVH: the global levels of the hybrid traversal stack, [level][thread of the largest query grid]
-  uint64_t query_stack_threads = 0;         // ... and the threads it was allocated for
-  DevBuf<unsigned int> d_query_next;        // engine BVH: the work counter
-  DevBuf<float4> d_query_rays;              // AMBER_RAYS_HOST: staging of the rays and of the results, at most kQueryStageRays rays
-  DevBuf<uint8_t> d_query_out;
+  RayQueryBufs query;                       // amber_hip_pt_cast_rays / amber_hip_pt_occluded
   ImageStageBufs img;                       // resolve, AOVs, the filters, batches
   DevBuf<float> d_fb;
-  float* accum_target = nullptr;            // where reduce_flagged_kernel and reduce_partials_kernel add a pass: d_fb, except inside amber_hip_pt_render_batch (img.batch)
   DevBuf<unsigned long long> d_rays;
   DevBuf<unsigned int> d_next;
   DevBuf<unsigned long long> d_stamps;
@@ -227,23 +260,8 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   uint64_t hashed_seed_lt = 0;
   LtAccumBufs lt;                           // amber_hip_lt_render_pass
   DevBuf<float> d_partial;                  // pt_bvh_megakernel: per-item sums
-  // path-granular accumulation (RenderPassPaths): bitmap, records in arrival order, measurements in path order, ranks
-  DevBuf<uint32_t> d_flags;  bool flags_dirty = true;   // dirty: must be cleared before the next launch
-  DevBuf<uint32_t> d_touched;
-  DevBuf<uint4> d_records;   DevBuf<float> d_sorted;   uint32_t rec_capacity = 0;
-  DevBuf<unsigned int> d_launch_ctl;        // [0] queue head of the path kernels, [1] = *d_rec_count, [2..3] = *d_rays_launch
-  unsigned int* d_rec_count = nullptr;
-  unsigned long long* d_rays_launch = nullptr;
-  DevBuf<uint32_t> d_excl, d_block_sum;
-  Owned<unsigned int*, hipHostFree> h_rec_count;   // pinned: the record counter of the launch in flight
-  Event pending_event;
-  bool pending = false, pending_checked = true;   // a launch whose record counter has not been looked at yet; checked = it cannot have run out of slots
-  uint32_t pending_first = 0, pending_n = 0;
-  float* pending_target = nullptr;          // the accumulation target of that launch: a repeat adds to the same buffer
-  bool density_known = false;
-  double rec_density = 0;                   // record slots used per path, as the last launch measured it
-  DevBuf<int32_t> d_bvh_stack;              // pt_bvh_pool_kernel: deep traversal-stack levels
-  DevBuf<float> d_carried;                  // ... and carried measurements
+  PathLaunchBufs paths;                     // the path-granular launches and the one in flight
+  DevBuf<int32_t> d_bvh_stack;              // pt_bvh_pool_kernel (lab build): deep traversal-stack levels
   DevBuf<unsigned long long> d_sig;         // amber_hip_pt_signatures
   DevBuf<uint32_t> d_pixel_mask;            // two-phase engine: primary-ray candidates per band pixel
   // pixel_mask_kernel is enqueued on the render stream by create (0.07 ms since the masks are per 4 x 4 block of pixels: it no longer pays to
@@ -254,10 +272,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   uint64_t seed = 0, hashed_seed = 0;
   DevBuf<float> d_wf;                       // WAVEFRONT: queues + meas + counts in one allocation
   uint32_t n_materials = 0;
-  std::vector<std::pair<Event, Event>> events;   // pool of event pairs, one per timed launch in flight
-  size_t events_used = 0;
-  uint32_t timed_launches = 0;     // launches already folded into timed_ms
-  double timed_ms = 0;
+  LaunchTimer timer;                        // amber_hip_pt_kernel_time
 };
 
 #include "bvh_device_build.inc"
@@ -272,7 +287,7 @@ uint64_t HostSplitMix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 
-int StartPixelMasks(amber_hip_pt* h, float* timing);      // defined with the launch code below
+int StartPixelMasks(amber_hip_pt* h, float* timing);      // defined with the launch code (pt_launch.inc)
 uint64_t BandPixels(const amber_hip_pt* h);               // the band's pixel count (image_stage.inc)
 uint32_t PersistentBlocks(const amber_hip_pt* h, uint64_t n_items = ~0ull, bool pool = false);
 
@@ -438,7 +453,6 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
   HIP_TRY(Upload(h.get(), std::vector<DevLens>{p.lens}, 0, sc.lens));
   const size_t fb_floats = static_cast<size_t>(local_rows) * sensor->width * 3;
   HIP_TRY(h->d_fb.alloc(fb_floats));
-  h->accum_target = h->d_fb;
   HIP_TRY(h->d_rays.alloc(1));
   HIP_TRY(h->d_next.alloc(1));
 #ifdef AMBER_STAMPS
@@ -485,378 +499,7 @@ int amber_hip_pt_create(const AmberFlatScene* s, const AmberSensor* sensor, cons
 
 }  // extern "C"
 
-namespace {
-// Hands out the next event pair; when the pool of 64 is used up the finished launches are folded into the running
-// totals (one stream synchronisation every 64 launches), so long renders (--spp 0 until expiry) do not grow the pool.
-int AcquireEventPair(amber_hip_pt* h, std::pair<Event, Event>** out) {
-  if (h->events_used == 64) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (size_t i = 0; i < h->events_used; i++) {
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, h->events[i].first.v, h->events[i].second.v));
-      h->timed_ms += ms;
-    }
-    h->timed_launches += static_cast<uint32_t>(h->events_used);
-    h->events_used = 0;
-  }
-  if (h->events_used == h->events.size()) {
-    std::pair<Event, Event> ev;
-    HIP_TRY(hipEventCreate(&ev.first.v)); HIP_TRY(hipEventCreate(&ev.second.v));
-    h->events.push_back(std::move(ev));
-  }
-  *out = &h->events[h->events_used++];
-  return AMBER_OK;
-}
-
-// Workgroups of the persistent kernels that fit a CU at once: pt_bvh_megakernel is bounded by its 24-entry LDS traversal stacks and
-// VGPRs; the others are capped to AMBER_MEGAKERNEL_WAVES_PER_SIMD by their launch bounds.
-uint32_t ResidentBlocksPerCu(uint32_t hit_engine) {
-  return hit_engine == AMBER_ENGINE_BVH ? static_cast<uint32_t>(AMBER_BVH_WGS) : (AMBER_MEGAKERNEL_WAVES_PER_SIMD > 5 ? static_cast<uint32_t>(AMBER_MEGAKERNEL_WAVES_PER_SIMD) : 5u);   // uncapped: 87 VGPRs -> 5
-}
-
-// Workgroups of 256 threads for n_items work units (one thread each), `resident` at the most.
-uint32_t BlocksFor(uint64_t n_items, uint32_t resident) {
-  const uint64_t by_work = n_items / 256u + (n_items % 256u != 0u);
-  return by_work < resident ? static_cast<uint32_t>(by_work) : resident;
-}
-
-// The grid of every persistent launch: workgroups of 256 threads, as many as fit the device at once, fewer if n_items work units (one
-// thread each) do not need them.  The default n_items gives the largest grid, for which engine REFERENCE_BVH's stack is sized.  `pool`:
-// pt_bvh_pool_kernel's grid (lab build).
-uint32_t PersistentBlocks(const amber_hip_pt* h, uint64_t n_items, bool pool) {
-  uint32_t n_blocks = static_cast<uint32_t>(h->n_cus) * ResidentBlocksPerCu(h->hit_engine);
-#ifdef AMBER_LAB
-  if (pool) n_blocks = static_cast<uint32_t>(h->n_cus) * static_cast<uint32_t>(AMBER_BVH_POOL_WGS);
-#endif
-  return BlocksFor(n_items, n_blocks);
-}
-
-// The one mapping from a handle's closest-hit engine to the engine its kernels are instantiated with: f(std::integral_constant<int, kEngine>).
-// Each caller picks its kernel with `if constexpr`, so nothing is instantiated that is never launched.
-template <typename F>
-int WithHitEngine(uint32_t hit_engine, F&& f) {
-  switch (hit_engine) {
-    case AMBER_ENGINE_TWO_PHASE: return f(std::integral_constant<int, ENGINE_TWO_PHASE>());
-    case kHitTwoPhaseN: return f(std::integral_constant<int, ENGINE_TWO_PHASE_N>());
-    case AMBER_ENGINE_BVH: return f(std::integral_constant<int, ENGINE_BVH>());
-    case AMBER_ENGINE_REFERENCE_BVH: return f(std::integral_constant<int, ENGINE_REF_BVH>());
-    default: return f(std::integral_constant<int, ENGINE_LIST>());
-  }
-}
-
-// Engine REFERENCE_BVH's stack has one column per thread of the largest grid (create; the handle remembers how many): a launch must not have more
-// threads.  Every launch site of a kernel that walks that tree -- the render passes, light tracing, the ray queries, which share the one stack -- asks
-// here first, before it takes anything (an event pair) it would have to give back.
-int CheckRefStack(const amber_hip_pt* h, uint32_t n_blocks) {
-  if (h->hit_engine == AMBER_ENGINE_REFERENCE_BVH && static_cast<uint64_t>(n_blocks) * 256u > h->ref_stack_threads)
-    return Fail(AMBER_EINVAL, "engine REFERENCE_BVH: a grid of " + std::to_string(n_blocks) + " workgroups outgrows the traversal stack (" + std::to_string(h->ref_stack_threads) + " threads)");
-  return AMBER_OK;
-}
-
-// Grows a buffer of the handle to at least n elements.  It may be in use: the stream is synchronised before it is freed.
-template <typename T>
-int Grow(amber_hip_pt* h, DevBuf<T>& b, size_t n, const char* what) {
-  if (n <= b.n) return AMBER_OK;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  const hipError_t e = b.alloc(n);
-  if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e));
-  return AMBER_OK;
-}
-
-// What every launch of a render kernel states first: the scene, the seed, the handle's band, the samples and their chunks (with the dividers).
-RenderArgs MakeRenderArgs(const amber_hip_pt* h, uint64_t hashed_seed, uint32_t n_pixels, uint32_t first_sample, uint32_t n_samples) {
-  RenderArgs a{};
-  a.scene = h->scene; a.hashed_seed = hashed_seed; a.SetBand(h->row_begin, h->stripe_rows, h->stripe_period); a.n_pixels = n_pixels;
-  a.SetSamples(first_sample, n_samples); a.n_chunks = (n_samples + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
-  return a;
-}
-
-}  // namespace
-
-namespace {
-// ---- path-granular launches (pt_megakernel for engines LIST / TWO_PHASE, pt_bvh_pool_kernel for engine BVH) --------------
-// One launch = megakernel + rank / scan / place / reduce.  The record buffer is sized from the density the previous launch
-// measured (record slots per path), with a margin; the very first launch of a handle is one accumulation chunk, whose buffer
-// can hold a record for EVERY path, and doubles as the probe.  A launch that still runs out of slots leaves the framebuffer
-// and the ray total untouched (the device-side kernels check the counter); the host notices when it next touches the handle
-// (ResolvePending), grows the buffer and repeats exactly that launch, so results never depend on the sizing.  Launches are
-// split on chunk boundaries, which leaves the summation order unchanged.
-constexpr uint64_t kMaxPathsPerLaunch = 1ull << 30;       // q and its bitmap index stay 32-bit; bitmap 128 MiB
-constexpr uint64_t kMaxRecordSlots = 48ull << 20;         // 28 B per slot (record + sorted measurement): 1.3 GiB at most
-
-// record slots that stay unused because every wave reserves them AMBER_REC_BLOCK at a time, plus a floor
-uint64_t RecordSlack(const amber_hip_pt* h) { return static_cast<uint64_t>(h->n_cus) * 8u * 4u * AMBER_REC_BLOCK + 4096u; }
-
-int EnsureRecordCapacity(amber_hip_pt* h, uint64_t slots) {
-  if (slots <= h->rec_capacity) return AMBER_OK;
-  if (slots > 0xfffffff0ull) return Fail(AMBER_ENOMEM, "record buffer beyond 2^32 slots");
-  h->rec_capacity = 0;
-  AMBER_TRY(Grow(h, h->d_records, slots, "path records"));
-  AMBER_TRY(Grow(h, h->d_sorted, slots * 3u, "path records"));
-  h->rec_capacity = static_cast<uint32_t>(slots);
-  return AMBER_OK;
-}
-
-// Enqueues one launch over samples [first, first + n) of the band.  `sig` != nullptr: the signature variant of the same
-// kernel; nothing is reduced (amber_hip_pt_signatures).
-int EnsureLaunchCtl(amber_hip_pt* h) {                                       // queue head | record count | rays of the launch: one block, one memset per launch
-  if (!h->d_launch_ctl) {
-    HIP_TRY(h->d_launch_ctl.alloc(4));
-    h->d_rec_count = h->d_launch_ctl + 1;
-    h->d_rays_launch = reinterpret_cast<unsigned long long*>(h->d_launch_ctl + 2);
-  }
-  return AMBER_OK;
-}
-
-// Two-phase engine, once per handle: the candidate mask of every band pixel's eye rays (pixel_mask_kernel), enqueued on the render stream by
-// create -- in front of the handle's first launch.  The buffer is allocated once and owned by the handle (amber_hip_pt_destroy releases it
-// whatever step failed).  `timing` != null (amber_hip_kat_pixel_masks): run the kernel (again) between two events and report its duration.
-int StartPixelMasks(amber_hip_pt* h, float* timing) {
-  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
-  if (!(h->two_phase && h->env.pixel_mask) || n_pixels == 0 || (h->pixel_mask_ready && !timing)) return AMBER_OK;
-  if (!h->d_pixel_mask) HIP_TRY(h->d_pixel_mask.alloc(n_pixels));
-  PixelMaskArgs pm{};
-  for (int i = 0; i < 4; i++) for (int c = 0; c < 3; c++) pm.ap[i][c] = static_cast<double>(h->aperture_rect[i][c]) - static_cast<double>(h->scene.fp_center[c]);
-  pm.inv_w = 1.0 / static_cast<double>(h->scene.sensor.wf); pm.inv_h = 1.0 / static_cast<double>(h->scene.sensor.hf);
-  pm.focal_scale = h->lens.kind == 1u ? -(8.0 * static_cast<double>(h->scene.fp_reach) + 1.0) / static_cast<double>(h->lens.sensor_distance)
-                                      : static_cast<double>(h->lens.focus_distance) / -static_cast<double>(h->lens.sensor_distance);
-  pm.row_begin = h->row_begin; pm.stripe_rows = h->stripe_rows; pm.stripe_period = h->stripe_period; pm.n_pixels = n_pixels;
-  pm.block = (h->stripe_rows == 0u || h->stripe_rows % 4u == 0u) ? 4u : 1u;
-  if (h->env.pixel_mask_block && (h->stripe_rows == 0u || h->stripe_rows % h->env.pixel_mask_block == 0u)) pm.block = h->env.pixel_mask_block;   // measurement hook
-  pm.local_rows = h->local_rows;
-  pm.blocks_x = (h->scene.sensor.w + pm.block - 1u) / pm.block;
-  pm.n_blocks = pm.blocks_x * ((h->local_rows + pm.block - 1u) / pm.block);
-  {
-    // "does plane i cut the aperture rectangle?" -- the kernel's own expressions (binary64, the slack of its first lines), evaluated once
-    const DevScene& sc = h->scene;
-    const double cx = sc.fp_center[0], cy = sc.fp_center[1], cz = sc.fp_center[2], reach = sc.fp_reach;
-    const double world_mag = std::max(std::max(std::fabs(cx), std::max(std::fabs(cy), std::fabs(cz))) + reach,
-                                      std::max(std::fabs(double(h->lens.origin[0])), std::max(std::fabs(double(h->lens.origin[1])), std::fabs(double(h->lens.origin[2])))));
-    const double slack = 1e-5 * reach + 32.0 * 5.9604644775390625e-08 * world_mag;
-    pm.planes_cut_a = h->host_planes.size() > 32 ? 0xffffffffu : 0u;
-    for (size_t i = 0; i < h->host_planes.size() && i < 32; i++) {
-      const DevPlane& q = h->host_planes[i];
-      bool above = true, below = true;
-      for (int k = 0; k < 4; k++) {
-        const double sa = double(q.n[0]) * pm.ap[k][0] + double(q.n[1]) * pm.ap[k][1] + double(q.n[2]) * pm.ap[k][2] - double(q.d0);
-        above = above && sa > 10.0 * slack; below = below && sa < -10.0 * slack;
-      }
-      if (!(above || below)) pm.planes_cut_a |= 1u << i;
-    }
-  }
-  Event ev0, ev1;
-  if (timing) { HIP_TRY(hipEventCreate(&ev0.v)); HIP_TRY(hipEventCreate(&ev1.v)); HIP_TRY(hipEventRecord(ev0.v, h->stream)); }
-  hipLaunchKernelGGL(pixel_mask_kernel, dim3((pm.n_blocks + 15u) / 16u), dim3(256), 0, h->stream, h->scene, pm, h->d_pixel_mask);   // 16 lanes per block of pixels
-  HIP_TRY(hipGetLastError());
-  if (timing) { HIP_TRY(hipEventRecord(ev1.v, h->stream)); HIP_TRY(hipEventSynchronize(ev1.v)); HIP_TRY(hipEventElapsedTime(timing, ev0.v, ev1.v)); }
-  h->pixel_mask_ready = true;
-  return AMBER_OK;
-}
-
-// pt_megakernel of the handle's engine, or pt_bvh_pool_kernel (`pool`, lab build); kSig: their signature instantiations
-template <bool kSig>
-void LaunchPathKernel(const amber_hip_pt* h, bool pool, uint32_t n_blocks, const RenderArgs& a) {
-  WithHitEngine(h->hit_engine, [&](auto engine) -> int {
-    constexpr int kEngine = decltype(engine)::value;
-#ifdef AMBER_LAB
-    if (kEngine == ENGINE_BVH && pool) { hipLaunchKernelGGL((pt_bvh_pool_kernel<kSig>), dim3(n_blocks), dim3(256), 0, h->stream, a); return AMBER_OK; }
-#endif
-    hipLaunchKernelGGL((pt_megakernel<kEngine, false, kSig>), dim3(n_blocks), dim3(256), 0, h->stream, a);
-    return AMBER_OK;
-  });
-}
-
-int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, unsigned long long* sig) {
-  const uint64_t n_paths = static_cast<uint64_t>(n_pixels) * n;
-#ifdef AMBER_LAB
-  const bool bvh = h->hit_engine == AMBER_ENGINE_BVH && !h->bvh_paths;       // pt_bvh_pool_kernel (bvh_paths: pt_megakernel<ENGINE_BVH>)
-#else
-  const bool bvh = false;
-  if (sig) return Fail(AMBER_EINVAL, "path signatures are part of the lab build");
-#endif
-  const size_t need_words = static_cast<size_t>((n_paths + 31u) / 32u) + 4u;
-  if (need_words > h->d_flags.n) {
-    AMBER_TRY(Grow(h, h->d_flags, need_words, "path bitmap"));
-    h->flags_dirty = true;
-  }
-  const size_t touched_words = static_cast<size_t>(n_pixels) / 32u + 2u;
-  AMBER_TRY(Grow(h, h->d_touched, touched_words, "touched pixels"));
-  AMBER_TRY(Grow(h, h->d_excl, n_pixels, "pixel ranks"));
-  AMBER_TRY(Grow(h, h->d_block_sum, static_cast<size_t>(n_pixels) / 256u + 2u, "pixel ranks"));
-  AMBER_TRY(EnsureLaunchCtl(h));
-  if (!h->h_rec_count.v) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_rec_count.v), sizeof(unsigned int), hipHostMallocDefault));
-  if (!h->pending_event.v) HIP_TRY(hipEventCreateWithFlags(&h->pending_event.v, hipEventDisableTiming));
-  const uint32_t n_blocks = PersistentBlocks(h, n_paths, bvh);
-  AMBER_TRY(CheckRefStack(h, n_blocks));
-  {
-    // measurements carried across bounces (degenerate paths only): pt_megakernel 3 floats per thread of the grid, pt_bvh_pool_kernel per ray of a wave
-    size_t carried = static_cast<size_t>(PersistentBlocks(h)) * 256u * 3u * 2u;   // own slots + parked slots
-#ifdef AMBER_LAB
-    if (bvh) carried = static_cast<size_t>(h->n_cus) * AMBER_BVH_POOL_WGS * 4u * AMBER_BVH_POOL_CARRIED_PER_WAVE;
-#endif
-    AMBER_TRY(Grow(h, h->d_carried, carried, "carried measurements"));
-  }
-#ifdef AMBER_LAB
-  if (bvh) AMBER_TRY(Grow(h, h->d_bvh_stack, static_cast<size_t>(h->n_cus) * AMBER_BVH_POOL_WGS * 256u * AMBER_BVH_POOL_GLOBAL_LEVELS, "traversal stacks"));
-#endif
-  RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first, n);
-  a.pixel_mask = h->pixel_mask_ready ? h->d_pixel_mask : nullptr;
-  a.flags = h->d_flags; a.touched = h->d_touched; a.records = h->d_records; a.rec_count = h->d_rec_count; a.rec_capacity = h->rec_capacity;
-  a.ray_count = h->d_rays_launch; a.next_item = h->d_launch_ctl; a.stamps = h->d_stamps;
-  a.bvh_stack = h->d_bvh_stack; a.carried = h->d_carried; a.sig = sig; a.n_items = static_cast<uint32_t>(n_paths);
-  HIP_TRY(hipMemsetAsync(h->d_launch_ctl, 0, 4 * sizeof(unsigned int), h->stream));
-  // The bitmap is cleared by the reduction itself where it can be (whole words per pixel); the host clears all of it only when a
-  // launch left it dirty: the first use, sample counts that are not multiples of 32, signature launches, a launch that ran out of slots.
-  if (h->flags_dirty) HIP_TRY(hipMemsetAsync(h->d_flags, 0, h->d_flags.n * sizeof(uint32_t), h->stream));
-  h->flags_dirty = sig != nullptr || (n & 31u) != 0u;
-  HIP_TRY(hipMemsetAsync(h->d_touched, 0, touched_words * sizeof(uint32_t), h->stream));
-  std::pair<Event, Event>* evp = nullptr;
-  AMBER_TRY(AcquireEventPair(h, &evp));
-  auto& ev = *evp;
-  HIP_TRY(hipEventRecord(ev.first.v, h->stream));
-#ifdef AMBER_LAB
-  if (sig) LaunchPathKernel<true>(h, bvh, n_blocks, a);      // the signature instantiations of the same kernels (amber_hip_pt_signatures)
-  else
-#endif
-  LaunchPathKernel<false>(h, bvh, n_blocks, a);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev.second.v, h->stream));
-  if (sig) return AMBER_OK;
-  const uint32_t n_rank_blocks = (n_pixels + 255u) / 256u;
-  hipLaunchKernelGGL(rec_rank_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, h->d_flags, h->d_touched, n_pixels, n, h->d_excl, h->d_block_sum);
-  hipLaunchKernelGGL(rec_scan_blocks_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_block_sum, n_rank_blocks, h->d_rec_count, h->rec_capacity, h->d_rays, h->d_rays_launch);
-  hipLaunchKernelGGL(rec_place_kernel, dim3(static_cast<uint32_t>(h->n_cus) * 8u), dim3(256), 0, h->stream, h->d_records, h->d_rec_count, h->rec_capacity, h->d_flags,
-                     h->d_excl, h->d_block_sum, n, MakeExactDiv(n), h->d_sorted);
-  hipLaunchKernelGGL(reduce_flagged_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, h->accum_target, h->d_flags, h->d_touched, h->d_sorted, h->d_excl, h->d_block_sum,
-                     h->d_rec_count, h->rec_capacity, n_pixels, n);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_rec_count.v, h->d_rec_count, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipEventRecord(h->pending_event.v, h->stream));
-  h->pending = true; h->pending_first = first; h->pending_n = n; h->pending_target = h->accum_target;
-  h->pending_checked = n_paths + RecordSlack(h) <= h->rec_capacity;      // a slot for every path: cannot run out
-  return AMBER_OK;
-}
-
-// Looks at the record counter of the launch in flight (waits for it), remembers the density, and repeats the launch with a
-// larger buffer if it ran out of slots.  Every entry point that reads results, or enqueues work whose order matters, calls it.
-int ResolvePending(amber_hip_pt* h) {
-  while (h->pending) {
-    HIP_TRY(hipEventSynchronize(h->pending_event.v));
-    h->pending = false;
-    const uint64_t used = *h->h_rec_count.v;
-    const uint64_t n_paths = BandPixels(h) * h->pending_n;
-    h->rec_density = n_paths ? static_cast<double>(used) / static_cast<double>(n_paths) : 0.0;
-    h->density_known = true;
-    if (used <= h->rec_capacity) break;
-    // out of slots: nothing of that launch reached the framebuffer or the ray total (and its bits are still set)
-    h->flags_dirty = true;
-    AMBER_TRY(EnsureRecordCapacity(h, used + used / 4u + RecordSlack(h)));
-    float* const target = h->accum_target;
-    h->accum_target = h->pending_target;
-    const int rl = LaunchPaths(h, h->pending_first, h->pending_n, static_cast<uint32_t>(BandPixels(h)), nullptr);
-    h->accum_target = target;
-    if (rl != AMBER_OK) return rl;
-  }
-  return AMBER_OK;
-}
-
-int RenderPassPaths(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t n_pixels) {
-  uint64_t max_samples = kMaxPathsPerLaunch / n_pixels / AMBER_ACCUM_CHUNK * AMBER_ACCUM_CHUNK;
-  if (max_samples == 0) return Fail(AMBER_EINVAL, "band too large for one launch");
-  const uint64_t slack = h->env.test_density_scale > 0 ? 64u : RecordSlack(h);   // (test hook: no cushion either)
-  uint32_t done = 0;
-  while (done < n_samples) {
-    // the previous launch must stand before the next one adds to the framebuffer (the order of the sums is part of the
-    // contract), unless it had a slot for every path
-    if (h->pending && (!h->pending_checked || !h->density_known)) AMBER_TRY(ResolvePending(h));
-    uint32_t n = n_samples - done;
-    if (n > max_samples) n = static_cast<uint32_t>(max_samples);
-    uint64_t slots;
-    if (!h->density_known) {
-      // first launch of the handle: a slot for every path, and at most one chunk unless the job is small -- it measures the density
-      if (static_cast<uint64_t>(n_pixels) * n > (4ull << 20) && n > AMBER_ACCUM_CHUNK) n = AMBER_ACCUM_CHUNK;
-      slots = static_cast<uint64_t>(n_pixels) * n + slack;
-    } else {
-      double density = h->rec_density;
-      if (h->env.test_density_scale > 0) density *= h->env.test_density_scale;   // test hook: a wrong estimate must only cost a repeated launch
-      const double per_sample = std::max(1e-9, density * 1.5) * static_cast<double>(n_pixels);   // slots one sample of the band needs, with margin
-      const uint64_t all = static_cast<uint64_t>(n_pixels) * n;
-      const double want = per_sample * n;
-      if (want + static_cast<double>(slack) > static_cast<double>(kMaxRecordSlots) && all + slack > kMaxRecordSlots) {
-        // a dense scene: shorter launches instead of a larger buffer
-        uint64_t fit = static_cast<uint64_t>((static_cast<double>(kMaxRecordSlots) - static_cast<double>(slack)) / per_sample) / AMBER_ACCUM_CHUNK * AMBER_ACCUM_CHUNK;
-        if (fit < AMBER_ACCUM_CHUNK) fit = AMBER_ACCUM_CHUNK;
-        if (n > fit) n = static_cast<uint32_t>(fit);
-      }
-      const uint64_t all_n = static_cast<uint64_t>(n_pixels) * n;
-      slots = std::min<uint64_t>(all_n, static_cast<uint64_t>(per_sample * n) + 1u) + slack;
-    }
-    if (slots > h->rec_capacity) {
-      if (h->pending) AMBER_TRY(ResolvePending(h));     // the buffer is in use
-      AMBER_TRY(EnsureRecordCapacity(h, slots));
-    }
-    AMBER_TRY(LaunchPaths(h, first_sample + done, n, n_pixels, nullptr));
-    done += n;
-  }
-  return AMBER_OK;
-}
-
-// The launches of light tracing over the passes [first_sample, first_sample + n_samples) of the light paths [path_begin, path_begin + n_paths): what
-// amber_hip_lt_trace_range and amber_hip_lt_render_pass share.  Each launch leaves its splat records at h->d_splats in arrival order (at most
-// `capacity` of them, read again before every launch: the callback may have grown the buffer) and is waited for; then
-//   after_launch(first, n, produced, rays_before, rays_now, &again)
-// sees the passes of the launch, the records it produced (also beyond the capacity) and the handle's ray counter before the first launch and now.
-// It returns a status other than AMBER_OK to stop, or sets `again` to have exactly this launch repeated.  `timed`: amber_hip_pt_kernel_time counts
-// the launches.  n_samples and n_paths are not zero.
-template <typename F>
-int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t n_paths, bool timed, const uint32_t& capacity, F&& after_launch) {
-  const bool bvh = h->hit_engine == AMBER_ENGINE_BVH;
-  // One launch numbers its work units with 31 bits -- pt_megakernel: (light path, pass) pairs; pt_bvh_megakernel: (light
-  // path, chunk of passes) items -- so a long range of passes is traced in several launches, each a whole number of chunks.
-  // Launches run in pass order and each one's splats are sorted, so the concatenation is in (pass, path, bounce) order.
-  const uint64_t max_units = 0x7fffffffull / n_paths;
-  if (max_units == 0) return Fail(AMBER_EINVAL, "too many light paths for one launch");
-  uint64_t max_samples = bvh ? max_units * AMBER_ACCUM_CHUNK : max_units / AMBER_ACCUM_CHUNK * AMBER_ACCUM_CHUNK;
-  if (max_samples == 0) max_samples = max_units;               // fewer than a chunk fits: any split is valid for light tracing (nothing is summed across launches)
-  unsigned long long rays_before = 0, rays_now = 0;
-  HIP_TRY(hipMemcpyAsync(&rays_before, h->d_rays, sizeof rays_before, hipMemcpyDeviceToHost, h->stream));
-  uint32_t done = 0;
-  while (done < n_samples) {
-    uint32_t n = n_samples - done;
-    if (n > max_samples) n = static_cast<uint32_t>(max_samples);
-    const uint32_t n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
-    const uint64_t n_work = bvh ? static_cast<uint64_t>(n_paths) * n_chunks : static_cast<uint64_t>(n_paths) * n;
-    RenderArgs a = MakeRenderArgs(h, h->hashed_seed_lt, n_paths, first_sample + done, n);
-    a.SetBand(0u, 0u, 0u);                                    // light paths have no band; every divider of the launch is a valid record all the same
-    a.ray_count = h->d_rays; a.next_item = h->d_next;
-    a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = capacity;
-    a.path_offset = path_begin; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
-    const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
-    AMBER_TRY(CheckRefStack(h, n_blocks));
-    std::pair<Event, Event>* evp = nullptr;
-    if (timed) AMBER_TRY(AcquireEventPair(h, &evp));
-    HIP_TRY(hipMemsetAsync(h->d_splat_count, 0, sizeof(unsigned int), h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
-    if (evp) HIP_TRY(hipEventRecord(evp->first.v, h->stream));
-    WithHitEngine(h->hit_engine, [&](auto engine) -> int {
-      constexpr int kEngine = decltype(engine)::value;
-      if constexpr (kEngine == ENGINE_BVH) hipLaunchKernelGGL((pt_bvh_megakernel<true, 24>), dim3(n_blocks), dim3(256), 0, h->stream, a);   // light tracing on engine BVH: always the item kernel
-      else hipLaunchKernelGGL((pt_megakernel<kEngine, true>), dim3(n_blocks), dim3(256), 0, h->stream, a);
-      return AMBER_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    if (evp) HIP_TRY(hipEventRecord(evp->second.v, h->stream));
-    unsigned int produced = 0;
-    HIP_TRY(hipMemcpyAsync(&produced, h->d_splat_count, sizeof produced, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(&rays_now, h->d_rays, sizeof rays_now, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    bool again = false;
-    AMBER_TRY(after_launch(first_sample + done, n, produced, rays_before, rays_now, &again));
-    if (!again) done += n;
-  }
-  return AMBER_OK;
-}
-}  // namespace
+#include "pt_launch.inc"
 
 #include "ray_query.inc"
 #include "image_stage.inc"
@@ -867,106 +510,49 @@ int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
 #include "temporal.inc"
 #include "lt_accumulate.inc"
 
-extern "C" {
-
-static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t n_pixels, unsigned long long* sig);   // internal: not part of the ABI
+namespace {
 #ifdef AMBER_LAB
-namespace { int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples); }      // lab_api.inc
+int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples);      // lab_api.inc
 #endif
 
-int amber_hip_pt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) { return Guarded("amber_hip_pt_render_pass", [&]() -> int {
-  if (!h) return Fail(AMBER_EINVAL, "null handle");
+// amber_hip_pt_render_pass (batch_name null: the samples are added to the framebuffer) and amber_hip_pt_render_batch (its name, which its messages begin
+// with): the samples into the handle's batch buffer (zeroed) instead, then moments_fold_kernel: fb = fb + B and the batch's luminance into the moments.
+int RenderBand(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, const char* batch_name) {
+  const std::string prefix = batch_name ? std::string(batch_name) + ": " : std::string();
+  if (!h) return Fail(AMBER_EINVAL, prefix + "null handle");
   if (n_samples == 0) return AMBER_OK;
-  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
+  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, prefix + "sample index overflow");
   HIP_TRY(hipSetDevice(h->device));
   const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
   if (n_pixels == 0) return AMBER_OK;                    // empty band
+  if (!batch_name) {
 #ifdef AMBER_LAB
-  if (h->engine == AMBER_ENGINE_WAVEFRONT) return RenderPassWavefront(h, first_sample, n_samples);
+    if (h->engine == AMBER_ENGINE_WAVEFRONT) return RenderPassWavefront(h, first_sample, n_samples);
 #endif
-  if (h->hit_engine != AMBER_ENGINE_BVH || h->bvh_pool || h->bvh_paths) return RenderPassPaths(h, first_sample, n_samples, n_pixels);
-  return RenderPassBvhItems(h, first_sample, n_samples, n_pixels, nullptr);
-}); }
-
-// render_pass into the handle's batch buffer (zeroed) instead of the framebuffer, then moments_fold_kernel: fb = fb + B and the batch's luminance into
-// the moments.  The accumulation target points at the batch buffer only inside this call: every way out restores it.
-int amber_hip_pt_render_batch(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) { return Guarded("amber_hip_pt_render_batch", [&]() -> int {
-  const std::string name = "amber_hip_pt_render_batch";
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (n_samples == 0) return AMBER_OK;
-  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, name + ": sample index overflow");
-  HIP_TRY(hipSetDevice(h->device));
-  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
-  if (n_pixels == 0) return AMBER_OK;                    // empty band
-  if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, name + ": not part of the lab engine WAVEFRONT");
-  // a pass in flight whose record buffer was sized from an estimate may have to be repeated: it must stand before the target moves
-  if (h->pending && !h->pending_checked) AMBER_TRY(ResolvePending(h));
-  AMBER_TRY(EnsureMoments(h, name.c_str()));
+    return RenderSamples(h, first_sample, n_samples, n_pixels, h->d_fb, nullptr);
+  }
+  if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, prefix + "not part of the lab engine WAVEFRONT");
+  // a pass in flight whose record buffer was sized from an estimate may have to be repeated: it must stand before the batch buffer is zeroed behind it
+  AMBER_TRY(SettlePending(h));
+  AMBER_TRY(EnsureMoments(h, batch_name));
   AMBER_TRY(Grow(h, h->img.batch, static_cast<size_t>(n_pixels) * 3u, "batch sums"));
   HIP_TRY(hipMemsetAsync(h->img.batch, 0, static_cast<size_t>(n_pixels) * 3u * sizeof(float), h->stream));
-  {
-    struct Target {
-      amber_hip_pt* h;
-      explicit Target(amber_hip_pt* handle) : h(handle) { h->accum_target = h->img.batch; }
-      ~Target() { h->accum_target = h->d_fb; }
-    } target(h);
-    int rc = (h->hit_engine != AMBER_ENGINE_BVH || h->bvh_pool || h->bvh_paths) ? RenderPassPaths(h, first_sample, n_samples, n_pixels)
-                                                                                 : RenderPassBvhItems(h, first_sample, n_samples, n_pixels, nullptr);
-    // ... and so must the batch's own last launch before the fold reads its sums (as amber_hip_pt_resolve waits)
-    if (rc == AMBER_OK && h->pending && !h->pending_checked) rc = ResolvePending(h);
-    // (after a failure here a launch may stay pending with the batch buffer for its target: a repeat of it then adds to a buffer nobody reads -- the
-    // next batch zeroes it behind that repeat on the stream -- so nothing of a failed batch reaches the framebuffer or the moments)
-    if (rc != AMBER_OK) return rc;
-  }
+  // (after a failure of the two calls below a launch may stay pending with the batch buffer for its target: a repeat of it then adds to a buffer nobody
+  // reads -- the next batch zeroes it behind that repeat on the stream -- so nothing of a failed batch reaches the framebuffer or the moments)
+  AMBER_TRY(RenderSamples(h, first_sample, n_samples, n_pixels, h->img.batch, nullptr));
+  AMBER_TRY(SettlePending(h));                           // ... and so must the batch's own last launch before the fold reads its sums (as amber_hip_pt_resolve waits)
   return FoldBatch(h, n_samples);
-}); }
+}
+}  // namespace
 
-// sig != null (amber_hip_pt_signatures): one launch of the signature instantiation; nothing reaches the framebuffer or the ray total
-static int RenderPassBvhItems(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t n_pixels, unsigned long long* sig) {
-  // engine BVH, default scheduler (pt_bvh_megakernel: lanes own (pixel, chunk) items).  A launch covers at most kMaxPartialFloats
-  // of per-item sums and < 2^31 items; longer passes are split on chunk boundaries, which leaves the summation order unchanged
-#ifndef AMBER_LAB
-  if (sig) return Fail(AMBER_EINVAL, "path signatures are part of the lab build");
-#endif
-  const uint64_t kMaxPartialFloats = 768ull << 20;    // 3 GiB
-  uint64_t max_chunks = kMaxPartialFloats / (static_cast<uint64_t>(n_pixels) * 3u);
-  const uint64_t by_items = 0x7fffffffull / n_pixels;
-  if (by_items < max_chunks) max_chunks = by_items;
-  if (max_chunks == 0) return Fail(AMBER_EINVAL, "band too large for one launch");
-  uint32_t done = 0;
-  while (done < n_samples) {
-    uint32_t n = n_samples - done;
-    const uint64_t cap = max_chunks * AMBER_ACCUM_CHUNK;
-    if (n > cap) n = static_cast<uint32_t>(cap);
-    const uint32_t n_chunks = (n + AMBER_ACCUM_CHUNK - 1) / AMBER_ACCUM_CHUNK;
-    const size_t need = static_cast<size_t>(n_chunks) * n_pixels * 3u;
-    AMBER_TRY(Grow(h, h->d_partial, need, "partial sums"));
-    if (sig && n != n_samples) return Fail(AMBER_EINVAL, "too many paths for one signature launch");
-    if (sig) AMBER_TRY(EnsureLaunchCtl(h));
-    RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first_sample + done, n);
-    a.partial = h->d_partial; a.ray_count = sig ? h->d_rays_launch : h->d_rays; a.next_item = h->d_next; a.stamps = h->d_stamps;
-    a.n_items = n_pixels * n_chunks; a.sig = sig; a.shade_batch = h->bvh_shade_batch;
-    // persistent workers: one workgroup of 4 waves per CU and resident wave slot, fewer if the queue is short
-    const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
-    HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
-    std::pair<Event, Event>* evp = nullptr;
-    AMBER_TRY(AcquireEventPair(h, &evp));
-    auto& ev = *evp;
-    HIP_TRY(hipEventRecord(ev.first.v, h->stream));
-#ifdef AMBER_LAB
-    if (sig) hipLaunchKernelGGL((pt_bvh_megakernel<false, 24, true>), dim3(n_blocks), dim3(256), 0, h->stream, a);
-    else
-#endif
-    hipLaunchKernelGGL((pt_bvh_megakernel<false, 24>), dim3(n_blocks), dim3(256), 0, h->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.second.v, h->stream));
-    if (sig) return AMBER_OK;                                  // the signature launch: nothing reaches the framebuffer
-    const uint32_t n_elems = n_pixels * 3u;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((n_elems + 255u) / 256u), dim3(256), 0, h->stream, h->accum_target, h->d_partial, n_elems, n_chunks);
-    HIP_TRY(hipGetLastError());
-    done += n;
-  }
-  return AMBER_OK;
+extern "C" {
+
+int amber_hip_pt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
+  return Guarded("amber_hip_pt_render_pass", [&] { return RenderBand(h, first_sample, n_samples, nullptr); });
+}
+
+int amber_hip_pt_render_batch(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples) {
+  return Guarded("amber_hip_pt_render_batch", [&] { return RenderBand(h, first_sample, n_samples, "amber_hip_pt_render_batch"); });
 }
 
 int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end,
@@ -1037,7 +623,7 @@ int amber_hip_pt_clear(amber_hip_pt* h) { return Guarded("amber_hip_pt_clear", [
   HIP_TRY(hipMemsetAsync(h->d_rays, 0, sizeof(unsigned long long), h->stream));
   // (no host synchronisation: the two fills are ordered on the handle's stream like everything else; event pairs handed out before
   //  this call have either been read by kernel_time() or are dropped here)
-  h->events_used = 0; h->timed_launches = 0; h->timed_ms = 0;
+  h->timer.reset();
   return AMBER_OK;
 }); }
 
@@ -1164,13 +750,14 @@ int amber_hip_pt_kernel_time(amber_hip_pt* h, uint32_t* n_launches, double* tota
   HIP_TRY(hipSetDevice(h->device));
   AMBER_TRY(ResolvePending(h));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  double tot = h->timed_ms;
-  for (size_t i = 0; i < h->events_used; i++) {
+  const LaunchTimer& t = h->timer;
+  double tot = t.folded_ms;
+  for (size_t i = 0; i < t.used; i++) {
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, h->events[i].first.v, h->events[i].second.v));
+    HIP_TRY(hipEventElapsedTime(&ms, t.events[i].first.v, t.events[i].second.v));
     tot += ms;
   }
-  if (n_launches) *n_launches = h->timed_launches + static_cast<uint32_t>(h->events_used);
+  if (n_launches) *n_launches = t.folded_launches + static_cast<uint32_t>(t.used);
   if (total_ms) *total_ms = tot;
   return AMBER_OK;
 }); }

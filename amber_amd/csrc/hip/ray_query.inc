@@ -156,19 +156,19 @@ int LaunchRayQuery(amber_hip_pt* h, uint64_t n, const float4* d_rays, void* d_ou
   uint8_t* occluded = any_hit ? static_cast<uint8_t*>(d_out) : nullptr;
   if (h->hit_engine == AMBER_ENGINE_BVH) {
     const uint32_t max_blocks = QueryGridCap(h);
-    if (!h->d_query_stack) {
-      const hipError_t e = h->d_query_stack.alloc(static_cast<size_t>(max_blocks) * 256u * (AMBER_BVH_STACK - AMBER_QUERY_LDS_LEVELS));
+    if (!h->query.stack) {
+      const hipError_t e = h->query.stack.alloc(static_cast<size_t>(max_blocks) * 256u * (AMBER_BVH_STACK - AMBER_QUERY_LDS_LEVELS));
       if (e != hipSuccess) return Fail(AMBER_ENOMEM, std::string("hipMalloc(query traversal stacks): ") + hipGetErrorString(e));
-      h->query_stack_threads = static_cast<uint64_t>(max_blocks) * 256u;
+      h->query.stack_threads = static_cast<uint64_t>(max_blocks) * 256u;
     }
-    if (!h->d_query_next) HIP_TRY(h->d_query_next.alloc(1));
+    if (!h->query.next) HIP_TRY(h->query.next.alloc(1));
     const uint32_t n_blocks = BlocksFor(n, max_blocks);
-    if (static_cast<uint64_t>(n_blocks) * 256u > h->query_stack_threads)
-      return Fail(AMBER_EINVAL, "ray query: a grid of " + std::to_string(n_blocks) + " workgroups outgrows the traversal stack (" + std::to_string(h->query_stack_threads) + " threads)");
-    HIP_TRY(hipMemsetAsync(h->d_query_next, 0, sizeof(unsigned int), h->stream));
-    const uint32_t stride = static_cast<uint32_t>(h->query_stack_threads);
-    if (any_hit) hipLaunchKernelGGL(bvh_query_kernel<true>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->d_query_next.p, h->d_query_stack.p, stride);
-    else hipLaunchKernelGGL(bvh_query_kernel<false>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->d_query_next.p, h->d_query_stack.p, stride);
+    if (static_cast<uint64_t>(n_blocks) * 256u > h->query.stack_threads)
+      return Fail(AMBER_EINVAL, "ray query: a grid of " + std::to_string(n_blocks) + " workgroups outgrows the traversal stack (" + std::to_string(h->query.stack_threads) + " threads)");
+    HIP_TRY(hipMemsetAsync(h->query.next, 0, sizeof(unsigned int), h->stream));
+    const uint32_t stride = static_cast<uint32_t>(h->query.stack_threads);
+    if (any_hit) hipLaunchKernelGGL(bvh_query_kernel<true>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->query.next.p, h->query.stack.p, stride);
+    else hipLaunchKernelGGL(bvh_query_kernel<false>, dim3(n_blocks), dim3(256), 0, h->stream, h->scene, static_cast<uint32_t>(n), d_rays, hits, occluded, h->query.next.p, h->query.stack.p, stride);
     HIP_TRY(hipGetLastError());
     return AMBER_OK;
   }
@@ -195,13 +195,13 @@ int RayQuery(amber_hip_pt* h, uint64_t n, const AmberRay* rays, void* out, uint3
   // host pointers: through the handle's staging buffers, kQueryStageRays at a time, and back before the call returns
   const size_t out_size = any_hit ? 1u : sizeof(AmberRayHit);
   const uint64_t chunk = n < kQueryStageRays ? n : kQueryStageRays;
-  AMBER_TRY(Grow(h, h->d_query_rays, chunk * 2u, "ray staging"));
-  AMBER_TRY(Grow(h, h->d_query_out, chunk * out_size, "ray staging"));
+  AMBER_TRY(Grow(h, h->query.rays, chunk * 2u, "ray staging"));
+  AMBER_TRY(Grow(h, h->query.out, chunk * out_size, "ray staging"));
   for (uint64_t done = 0; done < n; done += chunk) {
     const uint64_t m = n - done < chunk ? n - done : chunk;
-    HIP_TRY(hipMemcpyAsync(h->d_query_rays, rays + done, m * sizeof(AmberRay), hipMemcpyHostToDevice, h->stream));
-    AMBER_TRY(LaunchRayQuery(h, m, h->d_query_rays, h->d_query_out, any_hit));
-    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(out) + done * out_size, h->d_query_out, m * out_size, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->query.rays, rays + done, m * sizeof(AmberRay), hipMemcpyHostToDevice, h->stream));
+    AMBER_TRY(LaunchRayQuery(h, m, h->query.rays, h->query.out, any_hit));
+    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(out) + done * out_size, h->query.out, m * out_size, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
   return AMBER_OK;

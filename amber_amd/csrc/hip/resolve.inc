@@ -120,9 +120,9 @@ int Resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uin
   BandOutput o{};
   { const int rc = CheckBandOutput(h, name, false, format, out, out_bytes, flags, o); if (rc != AMBER_OK || o.n_pixels == 0) return rc; }
   HIP_TRY(hipSetDevice(h->device));
-  // a pass whose record buffer was sized from an estimate may have to be repeated before its sums stand (ResolvePending): wait for that one, as
+  // a pass whose record buffer was sized from an estimate may have to be repeated before its sums stand (SettlePending): wait for that one, as
   // clear and download do; a pass with a slot for every path, and every pass of the item kernel, needs no waiting
-  if (h->pending && !h->pending_checked) AMBER_TRY(ResolvePending(h));
+  AMBER_TRY(SettlePending(h));
   return WriteBandOutput(h, o, format, h->d_fb, static_cast<float>(n_samples), out);
 }
 
