@@ -83,6 +83,12 @@ class LtPassInfo(C.Structure):
                 ("longest_run", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class AccumulateInfo(C.Structure):
+    """AmberAccumulateInfo (lab build): what one amber_hip_kat_accumulate call did."""
+    _fields_ = [("n_launches", C.c_uint32), ("n_repeats", C.c_uint32), ("rec_count", C.c_uint32), ("flag_words_set", C.c_uint32),
+                ("flags_dirty", C.c_uint32)]
+
+
 LT_SPLAT_CAPACITY0 = 65536   # AMBER_LT_SPLAT_CAPACITY0: records the handle's splat buffer holds before the first growth
 SPLAT_DTYPE = np.dtype([("path", np.uint32), ("sample", np.uint32), ("bounce", np.uint32), ("pixel", np.uint32), ("rgb", np.float32, (3,)), ("pad", np.uint32)])   # AmberSplat
 
@@ -173,6 +179,7 @@ LAB_SYMBOLS = [
     "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump", "amber_hip_kat_division",
     "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep", "amber_hip_kat_lt_accumulate", "amber_hip_kat_lt_stage_ms",
     "amber_hip_kat_light_ray", "amber_hip_kat_lens_response", "amber_hip_kat_radiance", "amber_host_kat_scene_lights",
+    "amber_hip_kat_accumulate",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -278,6 +285,8 @@ def load_library() -> C.CDLL:
             lib.amber_hip_kat_lens_response.argtypes = [vp, u32, vp, vp, vp, vp, vp]
             lib.amber_hip_kat_radiance.argtypes = [vp, u32, vp, vp, vp, vp]
             lib.amber_host_kat_scene_lights.argtypes = [vp, C.POINTER(FlatLight), C.POINTER(u32)]
+        if hasattr(lib, "amber_hip_kat_accumulate"):       # the same
+            lib.amber_hip_kat_accumulate.argtypes = [vp, u32, vp, vp, u32, u32, u32, u64, C.POINTER(AccumulateInfo)]
     lib.amber_host_cornell_box.restype = vp
     lib.amber_host_cornell_box.argtypes = [C.c_float, C.c_float, u32]
     lib.amber_host_scene_import.restype = vp
@@ -827,6 +836,18 @@ class PathTracer:
         lt_trace's dtype, in any order -- into the framebuffer."""
         rec = np.ascontiguousarray(records, SPLAT_DTYPE)
         _check(load_library().amber_hip_kat_lt_accumulate(self._h, rec.ctypes.data if len(rec) else None, len(rec)))
+
+    def kat_accumulate(self, n_samples: int, q, rgb, n_waves: int = 4, rec_capacity: int = 0, rays: int = 0) -> dict:
+        """Lab build: one path launch over n_samples samples of the band whose records are the caller's -- q[i] = band pixel * n_samples + sample,
+        0xffffffff for a lane that emits nothing, rgb[i] its measurement -- through the product's emitters, reduction and repeat into the framebuffer
+        (include/amber_hip_lab.h; tests/path_accumulate_reference.py restates the sum).  Returns AmberAccumulateInfo as a dict."""
+        qq = np.ascontiguousarray(q, np.uint32).reshape(-1)
+        cc = _f32(rgb).reshape(-1, 3)
+        assert len(qq) == len(cc)
+        info = AccumulateInfo()
+        _check(load_library().amber_hip_kat_accumulate(self._h, n_samples, qq.ctypes.data if len(qq) else None, cc.ctypes.data if len(qq) else None,
+                                                       len(qq), n_waves, rec_capacity, rays, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in AccumulateInfo._fields_}
 
     def kat_lt_stage_ms(self):
         """Lab build: (sort ms, sum ms) of lt_render_pass's device path since the previous call; the first call switches the timing on."""

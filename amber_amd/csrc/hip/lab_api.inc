@@ -78,6 +78,21 @@ int RenderPassWavefront(amber_hip_pt* h, uint32_t first_sample, uint32_t n_sampl
   });
 }
 
+// One path launch over n samples of the band whose records come from kat_accumulate_kernel (amber_hip_kat_accumulate): LaunchPaths with the other
+// producer.  ResolvePending repeats it from here when it ran out of slots.
+int LaunchLabRecords(amber_hip_pt* h, uint32_t n, uint32_t n_pixels, float* target, const RecordProducer& producer) {
+  AMBER_TRY(BeginPathLaunch(h, n, n_pixels, false));
+  RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, 0u, n);
+  SetRecordArgs(h, a);
+  a.n_items = n_pixels * n;
+  AMBER_TRY(TimedLaunch(h, false, [&]() -> int {
+    hipLaunchKernelGGL(kat_accumulate_kernel, dim3((producer.n_waves + 3u) / 4u), dim3(256), 0, h->stream, a, producer.q, producer.rgb, producer.n_items,
+                       producer.n_waves, producer.rays);
+    return AMBER_OK;
+  }));
+  return FinishPathLaunch(h, 0u, n, n_pixels, target, producer, false);
+}
+
 }  // namespace
 
 extern "C" {
@@ -371,6 +386,59 @@ int amber_hip_kat_lt_accumulate(amber_hip_pt* h, const AmberSplat* records, uint
   HIP_TRY(hipMemsetAsync(h->lt.longest.p, 0, sizeof(unsigned int), h->stream));
   AMBER_TRY(LtAccumulate(h, n, 32u));
   HIP_TRY(hipStreamSynchronize(h->stream));
+  return AMBER_OK;
+}); }
+
+int amber_hip_kat_accumulate(amber_hip_pt* h, uint32_t n_samples, const uint32_t* q, const float* rgb, uint32_t n_items, uint32_t n_waves, uint32_t rec_capacity,
+                             uint64_t rays, AmberAccumulateInfo* info) { return Guarded("amber_hip_kat_accumulate", [&]() -> int {
+  if (info) *info = AmberAccumulateInfo{};
+  if (!h || (n_items && (!q || !rgb))) return Fail(AMBER_EINVAL, "null argument");
+  if (n_samples == 0 || n_waves == 0) return Fail(AMBER_EINVAL, "amber_hip_kat_accumulate: n_samples and n_waves must not be zero");
+  if (n_waves > (1u << 20)) return Fail(AMBER_EINVAL, "amber_hip_kat_accumulate: more than 2^20 waves");
+  const uint64_t n_paths = BandPixels(h) * n_samples;
+  if (n_paths >= (1ull << 32)) return Fail(AMBER_EINVAL, "amber_hip_kat_accumulate: n_pixels * n_samples must stay below 2^32");
+  {
+    std::vector<uint32_t> seen;
+    seen.reserve(n_items);
+    for (uint32_t i = 0; i < n_items; i++) {
+      if (q[i] == AMBER_REC_UNUSED) continue;
+      if (q[i] >= n_paths) return Fail(AMBER_EINVAL, "amber_hip_kat_accumulate: item " + std::to_string(i) + ": path index out of range");
+      seen.push_back(q[i]);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return Fail(AMBER_EINVAL, "amber_hip_kat_accumulate: a path index occurs twice");
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  AMBER_TRY(ResolvePending(h));                                  // what is in flight stands first: it uses the record buffer
+  PathLaunchBufs& p = h->paths;
+  if (rec_capacity != 0 && rec_capacity < p.rec_capacity)
+    return Fail(AMBER_EINVAL, "amber_hip_kat_accumulate: rec_capacity " + std::to_string(rec_capacity) + " is below the " + std::to_string(p.rec_capacity) + " slots the handle's record buffer has");
+  const uint32_t n_pixels = static_cast<uint32_t>(BandPixels(h));
+  if (n_pixels == 0) return AMBER_OK;                            // empty band
+  AMBER_TRY(EnsureRecordCapacity(h, rec_capacity ? rec_capacity : static_cast<uint64_t>(n_items) + RecordSlack(h)));
+  DevBuf<uint32_t> d_q; DevBuf<float> d_rgb;                     // live until the launch stands (ResolvePending below repeats it from them)
+  HIP_TRY(d_q.alloc(n_items ? n_items : 1u)); HIP_TRY(d_rgb.alloc(n_items ? 3ull * n_items : 1u));
+  if (n_items) {
+    HIP_TRY(hipMemcpy(d_q.p, q, 4ull * n_items, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_rgb.p, rgb, 12ull * n_items, hipMemcpyHostToDevice));
+  }
+  RecordProducer producer;
+  producer.lab = true; producer.q = d_q.p; producer.rgb = d_rgb.p; producer.n_items = n_items; producer.n_waves = n_waves; producer.rays = rays;
+  const uint64_t launches0 = p.n_launches, repeats0 = p.n_repeats;
+  AMBER_TRY(LaunchLabRecords(h, n_samples, n_pixels, h->d_fb, producer));
+  const int rc = ResolvePending(h);
+  p.pending = false; p.pending_producer = RecordProducer{};      // (whatever happened: the device inputs end with this call)
+  AMBER_TRY(rc);
+  const size_t used_words = static_cast<size_t>((n_paths + 31u) / 32u);
+  std::vector<uint32_t> words(used_words);
+  if (used_words) HIP_TRY(hipMemcpyAsync(words.data(), p.flags, used_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (info) {
+    info->n_launches = static_cast<uint32_t>(p.n_launches - launches0); info->n_repeats = static_cast<uint32_t>(p.n_repeats - repeats0);
+    info->rec_count = *p.h_rec_count.v;
+    info->flag_words_set = static_cast<uint32_t>(std::count_if(words.begin(), words.end(), [](uint32_t w) { return w != 0u; }));
+    info->flags_dirty = p.flags_dirty ? 1u : 0u;
+  }
   return AMBER_OK;
 }); }
 

@@ -157,6 +157,28 @@ __global__ void kat_signature_kernel(const DevScene sc, uint64_t hashed_seed, ui
   if (i < n) out[i] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
 }
 
+// The caller's records through the product's own emitters (amber_hip_kat_accumulate).  Wave w of n_waves takes the trips w, w + n_waves, ... of 64
+// consecutive items; lane l of trip t holds item 64 t + l (past n_items: a lane that emits nothing) and the whole wave calls EmitRecords, as a wave of
+// the render kernels does when its paths end; after its last trip it closes its open block.  q[i] = AMBER_REC_UNUSED: item i emits nothing.  The host
+// has checked every other q against the launch's path count, so no store leaves the bitmap, the touched bits or -- EmitRecords' own check -- the
+// record buffer.  One lane adds `rays` to the launch's ray counter.
+__global__ void __launch_bounds__(256) kat_accumulate_kernel(const RenderArgs a, const uint32_t* __restrict__ q, const float* __restrict__ rgb, uint32_t n_items,
+                                                             uint32_t n_waves, unsigned long long rays) {
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+  if (wave >= n_waves) return;                                              // (whole waves)
+  const uint32_t n_trips = n_items / 64u + (n_items % 64u != 0u);
+  uint32_t rec_next = 0u, rec_end = 0u;
+  for (uint32_t t = wave; t < n_trips; t += n_waves) {
+    const uint64_t i = static_cast<uint64_t>(t) * 64u + lane;
+    const uint32_t path = i < n_items ? q[i] : AMBER_REC_UNUSED;
+    const bool emit = path != AMBER_REC_UNUSED;
+    const V3 meas = emit ? ld3(rgb + 3u * i) : v3(0.f, 0.f, 0.f);
+    EmitRecords(a, emit, path, meas, rec_next, rec_end);
+  }
+  CloseRecords(a, rec_next, rec_end);
+  if (wave == 0u && lane == 0u) atomicAdd(a.ray_count, rays);
+}
+
 __global__ void kat_math_kernel(int mode, uint32_t n, const float* x, float* out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -189,6 +189,15 @@ struct RayQueryBufs {
 };
 // Path-granular launches (pt_launch.inc: LaunchPaths, ResolvePending): bitmap, records in arrival order, measurements in path order, ranks -- and
 // the launch whose record counter the host has not looked at yet
+// What fills a launch's record buffer: the product's render kernel, or (lab build, amber_hip_kat_accumulate) the kernel that emits the caller's records
+// -- then with its device inputs, so that a repeat of the launch finds them again.
+struct RecordProducer {
+  bool lab = false;
+  const uint32_t* q = nullptr;              // device, n_items: the path of every item, AMBER_REC_UNUSED = the lane emits nothing
+  const float* rgb = nullptr;               // device, n_items * 3
+  uint32_t n_items = 0, n_waves = 0;
+  unsigned long long rays = 0;              // what the launch adds to its ray counter
+};
 struct PathLaunchBufs {
   DevBuf<uint32_t> flags;  bool flags_dirty = true;   // dirty: must be cleared before the next launch
   DevBuf<uint32_t> touched;
@@ -202,6 +211,8 @@ struct PathLaunchBufs {
   bool pending = false, pending_checked = true;   // a launch whose record counter has not been looked at yet; checked = it cannot have run out of slots
   uint32_t pending_first = 0, pending_n = 0;
   float* pending_target = nullptr;          // where that launch adds its sums (the framebuffer, a batch buffer): a repeat adds to the same buffer
+  RecordProducer pending_producer;          // ... and what produced its records: a repeat runs the same producer
+  uint64_t n_launches = 0, n_repeats = 0;   // launches reduced so far, and how many of them were repeats (amber_hip_kat_accumulate reports the difference)
   bool density_known = false;
   double rec_density = 0;                   // record slots used per path, as the last launch measured it
   DevBuf<float> carried;                    // measurements carried across bounces (degenerate paths only)

@@ -3,7 +3,7 @@
 // Part of the one translation unit pt_host.hip (the handle is defined there); see its header comment.
 //
 // Where a pass adds its sums is an argument (`target`): the framebuffer, or amber_hip_pt_render_batch's batch buffer.  Only two launches write it,
-// reduce_flagged_kernel (LaunchPaths) and reduce_partials_kernel (RenderPassBvhItems).
+// reduce_flagged_kernel (FinishPathLaunch: LaunchPaths, and the lab build's LaunchLabRecords) and reduce_partials_kernel (RenderPassBvhItems).
 
 namespace {
 using amber_plan::kMaxPathsPerLaunch;
@@ -204,17 +204,14 @@ int LaunchPathKernel(const amber_hip_pt* h, bool pool, uint32_t n_blocks, const 
   });
 }
 
-// Enqueues one launch over samples [first, first + n) of the band, its sums added to `target`.  `sig` != nullptr: the signature variant of the same
-// kernel; nothing is reduced (amber_hip_pt_signatures).
-int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, float* target, unsigned long long* sig) {
+// A path launch in three parts, so that the reduction serves whatever produced the records: BeginPathLaunch (buffers, counters and bitmap ready),
+// the producer's kernel, FinishPathLaunch (rank / scan / place / reduce, the launch becomes the pending one).
+
+// Before the kernel: the bitmap, the touched bits and the ranks sized for n samples of n_pixels pixels, the control block zeroed, the bitmap cleared
+// if the previous launch left it dirty, the touched bits cleared.  `sig`: a signature launch (nothing is reduced, so its bits stay).
+int BeginPathLaunch(amber_hip_pt* h, uint32_t n, uint32_t n_pixels, bool sig) {
   PathLaunchBufs& p = h->paths;
   const uint64_t n_paths = static_cast<uint64_t>(n_pixels) * n;
-#ifdef AMBER_LAB
-  const bool bvh = h->hit_engine == AMBER_ENGINE_BVH && !h->bvh_paths;       // pt_bvh_pool_kernel (bvh_paths: pt_megakernel<ENGINE_BVH>)
-#else
-  const bool bvh = false;
-  if (sig) return Fail(AMBER_EINVAL, "path signatures are part of the lab build");
-#endif
   const size_t need_words = static_cast<size_t>((n_paths + 31u) / 32u) + 4u;
   if (need_words > p.flags.n) {
     AMBER_TRY(Grow(h, p.flags, need_words, "path bitmap"));
@@ -227,6 +224,53 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
   AMBER_TRY(EnsureLaunchCtl(h));
   if (!p.h_rec_count.v) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p.h_rec_count.v), sizeof(unsigned int), hipHostMallocDefault));
   if (!p.pending_event.v) HIP_TRY(hipEventCreateWithFlags(&p.pending_event.v, hipEventDisableTiming));
+  HIP_TRY(hipMemsetAsync(p.launch_ctl, 0, 4 * sizeof(unsigned int), h->stream));
+  // The bitmap is cleared by the reduction itself where it can be (whole words per pixel); the host clears all of it only when a
+  // launch left it dirty: the first use, sample counts that are not multiples of 32, signature launches, a launch that ran out of slots.
+  if (p.flags_dirty) HIP_TRY(hipMemsetAsync(p.flags, 0, p.flags.n * sizeof(uint32_t), h->stream));
+  p.flags_dirty = sig || (n & 31u) != 0u;
+  HIP_TRY(hipMemsetAsync(p.touched, 0, touched_words * sizeof(uint32_t), h->stream));
+  return AMBER_OK;
+}
+
+// What the record producers are handed: the buffers BeginPathLaunch prepared, in the kernels' argument block
+void SetRecordArgs(const amber_hip_pt* h, RenderArgs& a) {
+  const PathLaunchBufs& p = h->paths;
+  a.flags = p.flags; a.touched = p.touched; a.records = p.records; a.rec_count = p.rec_count; a.rec_capacity = p.rec_capacity;
+  a.ray_count = p.rays_launch; a.next_item = p.launch_ctl;
+}
+
+// After the kernel: the records of samples [first, first + n) ranked, placed and summed into `target`, the record counter on its way to the host, and
+// the launch remembered as the one in flight.  `cannot_run_out`: it had a slot for every record it can produce.
+int FinishPathLaunch(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, float* target, const RecordProducer& producer, bool cannot_run_out) {
+  PathLaunchBufs& p = h->paths;
+  const uint32_t n_rank_blocks = (n_pixels + 255u) / 256u;
+  hipLaunchKernelGGL(rec_rank_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, p.flags, p.touched, n_pixels, n, p.excl, p.block_sum);
+  hipLaunchKernelGGL(rec_scan_blocks_kernel, dim3(1), dim3(1024), 0, h->stream, p.block_sum, n_rank_blocks, p.rec_count, p.rec_capacity, h->d_rays, p.rays_launch);
+  hipLaunchKernelGGL(rec_place_kernel, dim3(static_cast<uint32_t>(h->n_cus) * 8u), dim3(256), 0, h->stream, p.records, p.rec_count, p.rec_capacity, p.flags,
+                     p.excl, p.block_sum, n, MakeExactDiv(n), p.sorted);
+  hipLaunchKernelGGL(reduce_flagged_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, target, p.flags, p.touched, p.sorted, p.excl, p.block_sum,
+                     p.rec_count, p.rec_capacity, n_pixels, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(p.h_rec_count.v, p.rec_count, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipEventRecord(p.pending_event.v, h->stream));
+  p.pending = true; p.pending_first = first; p.pending_n = n; p.pending_target = target; p.pending_producer = producer;
+  p.pending_checked = cannot_run_out;
+  ++p.n_launches;
+  return AMBER_OK;
+}
+
+// Enqueues one launch over samples [first, first + n) of the band, its sums added to `target`.  `sig` != nullptr: the signature variant of the same
+// kernel; nothing is reduced (amber_hip_pt_signatures).
+int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, float* target, unsigned long long* sig) {
+  PathLaunchBufs& p = h->paths;
+  const uint64_t n_paths = static_cast<uint64_t>(n_pixels) * n;
+#ifdef AMBER_LAB
+  const bool bvh = h->hit_engine == AMBER_ENGINE_BVH && !h->bvh_paths;       // pt_bvh_pool_kernel (bvh_paths: pt_megakernel<ENGINE_BVH>)
+#else
+  const bool bvh = false;
+  if (sig) return Fail(AMBER_EINVAL, "path signatures are part of the lab build");
+#endif
   const uint32_t n_blocks = PersistentBlocks(h, n_paths, bvh);
   AMBER_TRY(CheckRefStack(h, n_blocks));
   {
@@ -240,17 +284,12 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
 #ifdef AMBER_LAB
   if (bvh) AMBER_TRY(Grow(h, h->d_bvh_stack, static_cast<size_t>(h->n_cus) * AMBER_BVH_POOL_WGS * 256u * AMBER_BVH_POOL_GLOBAL_LEVELS, "traversal stacks"));
 #endif
+  AMBER_TRY(BeginPathLaunch(h, n, n_pixels, sig != nullptr));
   RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first, n);
   a.pixel_mask = h->pixel_mask_ready ? h->d_pixel_mask : nullptr;
-  a.flags = p.flags; a.touched = p.touched; a.records = p.records; a.rec_count = p.rec_count; a.rec_capacity = p.rec_capacity;
-  a.ray_count = p.rays_launch; a.next_item = p.launch_ctl; a.stamps = h->d_stamps;
+  SetRecordArgs(h, a);
+  a.stamps = h->d_stamps;
   a.bvh_stack = h->d_bvh_stack; a.carried = p.carried; a.sig = sig; a.n_items = static_cast<uint32_t>(n_paths);
-  HIP_TRY(hipMemsetAsync(p.launch_ctl, 0, 4 * sizeof(unsigned int), h->stream));
-  // The bitmap is cleared by the reduction itself where it can be (whole words per pixel); the host clears all of it only when a
-  // launch left it dirty: the first use, sample counts that are not multiples of 32, signature launches, a launch that ran out of slots.
-  if (p.flags_dirty) HIP_TRY(hipMemsetAsync(p.flags, 0, p.flags.n * sizeof(uint32_t), h->stream));
-  p.flags_dirty = sig != nullptr || (n & 31u) != 0u;
-  HIP_TRY(hipMemsetAsync(p.touched, 0, touched_words * sizeof(uint32_t), h->stream));
   AMBER_TRY(TimedLaunch(h, true, [&]() -> int {
 #ifdef AMBER_LAB
     if (sig) return LaunchPathKernel<true>(h, bvh, n_blocks, a);
@@ -258,23 +297,16 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
     return LaunchPathKernel<false>(h, bvh, n_blocks, a);
   }));
   if (sig) return AMBER_OK;
-  const uint32_t n_rank_blocks = (n_pixels + 255u) / 256u;
-  hipLaunchKernelGGL(rec_rank_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, p.flags, p.touched, n_pixels, n, p.excl, p.block_sum);
-  hipLaunchKernelGGL(rec_scan_blocks_kernel, dim3(1), dim3(1024), 0, h->stream, p.block_sum, n_rank_blocks, p.rec_count, p.rec_capacity, h->d_rays, p.rays_launch);
-  hipLaunchKernelGGL(rec_place_kernel, dim3(static_cast<uint32_t>(h->n_cus) * 8u), dim3(256), 0, h->stream, p.records, p.rec_count, p.rec_capacity, p.flags,
-                     p.excl, p.block_sum, n, MakeExactDiv(n), p.sorted);
-  hipLaunchKernelGGL(reduce_flagged_kernel, dim3(n_rank_blocks), dim3(256), 0, h->stream, target, p.flags, p.touched, p.sorted, p.excl, p.block_sum,
-                     p.rec_count, p.rec_capacity, n_pixels, n);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(p.h_rec_count.v, p.rec_count, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipEventRecord(p.pending_event.v, h->stream));
-  p.pending = true; p.pending_first = first; p.pending_n = n; p.pending_target = target;
-  p.pending_checked = n_paths + RecordSlack(h) <= p.rec_capacity;      // a slot for every path: cannot run out
-  return AMBER_OK;
+  return FinishPathLaunch(h, first, n, n_pixels, target, RecordProducer{}, n_paths + RecordSlack(h) <= p.rec_capacity);   // a slot for every path: cannot run out
 }
 
+#ifdef AMBER_LAB
+int LaunchLabRecords(amber_hip_pt* h, uint32_t n, uint32_t n_pixels, float* target, const RecordProducer& producer);   // lab_api.inc
+#endif
+
 // The host is about to read results or to enqueue work whose order matters: looks at the record counter of the launch in flight (waits for it),
-// remembers the density, and repeats the launch -- exactly that one, into the target it had -- with a larger buffer if it ran out of slots.
+// remembers the density, and repeats the launch -- exactly that one, from the producer it had, into the target it had -- with a larger buffer if it
+// ran out of slots.
 int ResolvePending(amber_hip_pt* h) {
   PathLaunchBufs& p = h->paths;
   while (p.pending) {
@@ -287,7 +319,15 @@ int ResolvePending(amber_hip_pt* h) {
     if (used <= p.rec_capacity) break;
     // out of slots: nothing of that launch reached its target or the ray total (and its bits are still set)
     p.flags_dirty = true;
+    ++p.n_repeats;
     AMBER_TRY(EnsureRecordCapacity(h, used + used / 4u + RecordSlack(h)));
+#ifdef AMBER_LAB
+    if (p.pending_producer.lab) {
+      const RecordProducer producer = p.pending_producer;
+      AMBER_TRY(LaunchLabRecords(h, p.pending_n, static_cast<uint32_t>(BandPixels(h)), p.pending_target, producer));
+      continue;
+    }
+#endif
     AMBER_TRY(LaunchPaths(h, p.pending_first, p.pending_n, static_cast<uint32_t>(BandPixels(h)), p.pending_target, nullptr));
   }
   return AMBER_OK;

@@ -87,6 +87,25 @@ int amber_hip_kat_bvh_dump(amber_hip_pt*, uint32_t* nodes, uint32_t node_capacit
  * framebuffer; `path` is sorted with all its 32 bits.  Real scenes splat rarely (the aperture catches about 1e-4 of the light paths): only this hook
  * puts the sort and the sum under load.  Synchronous.  AMBER_EINVAL for a pixel >= width * height or a banded handle; n == 0 changes nothing. */
 int amber_hip_kat_lt_accumulate(amber_hip_pt*, const AmberSplat* records /* host */, uint32_t n);
+/* "Accumulation without owners"  on the caller's records: ONE path launch over n_samples samples of the handle's band pixels, added
+ * to the handle's framebuffer, exactly as amber_hip_pt_render_pass enqueues it -- the same bitmap, rank / scan / place / reduce kernels, the same host
+ * state (the bitmap that is cleared only when a launch left it dirty, the record buffer, the repeat of a launch that ran out of slots) -- except that
+ * the records come from a kernel that feeds q[i], rgb[i] (host arrays, n_items entries) to the product's EmitRecords: wave w of n_waves takes the trips
+ * w, w + n_waves, ... of 64 consecutive items (the last trip padded with lanes that emit nothing) and calls CloseRecords after its last one, so the caller
+ * decides how many lanes emit per trip.  q[i] = path index = band pixel * n_samples + sample; 0xffffffff: lane i emits nothing (its path ended with
+ * +0).  Real scenes leave most branches of the reduction cold (the Cornell box sets one or two bits per touched pixel); only this hook puts chosen bit
+ * patterns, record counts and slot boundaries under them.  tests/path_accumulate_reference.py restates the sum it must give.
+ * rec_capacity: the record slots the launch sees -- 0: a slot per item plus the slack every render launch has; otherwise exactly this many (the buffer
+ * grows to it; a value below what the handle's buffer already holds is refused, so use a fresh handle for a small one).  A launch that runs out is
+ * repeated with a larger buffer by the product's own code.  `rays` is what the launch adds to its ray counter: it reaches the handle's total once,
+ * with the launch that stands.
+ * AMBER_EINVAL, before anything is enqueued: n_samples == 0, n_waves == 0, band pixels * n_samples >= 2^32, a q other than the marker that is
+ * >= band pixels * n_samples or occurs twice, a non-zero rec_capacity below the buffer's.  n_items == 0 is a launch without records.  Any engine.
+ * Synchronous: the launch has been settled and the stream waited for.  info (may be NULL): launches and repeats of this call, the record counter of the
+ * launch that stood, the non-zero words in the bitmap's used range afterwards, and whether the host holds the bitmap for dirty. */
+typedef struct { uint32_t n_launches, n_repeats, rec_count, flag_words_set, flags_dirty; } AmberAccumulateInfo;
+int amber_hip_kat_accumulate(amber_hip_pt*, uint32_t n_samples, const uint32_t* q /* host, n_items */, const float* rgb /* host, n_items * 3 */, uint32_t n_items,
+                             uint32_t n_waves, uint32_t rec_capacity, uint64_t rays, AmberAccumulateInfo* info);
 /* Measurement: the first call switches on the timing of that device path with events (every accumulation then waits for the stream); every call
  * returns the milliseconds spent ordering (keys, sorts, gather) and summing since the previous call.  Either pointer may be NULL. */
 int amber_hip_kat_lt_stage_ms(amber_hip_pt*, double* sort_ms, double* sum_ms);
