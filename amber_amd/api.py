@@ -103,6 +103,17 @@ class RayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("object", C.c_int32), ("pos", C.c_float * 3), ("normal", C.c_float * 3)]
 
 
+class PathRay(C.Structure):
+    """AmberPathRay: origin, dir, weight (each padded to 16 bytes), rng_state, pad -- 64 bytes (amber_hip_pt_trace_paths)."""
+    _fields_ = [("origin", C.c_float * 3), ("pad0", C.c_uint32), ("dir", C.c_float * 3), ("pad1", C.c_uint32),
+                ("weight", C.c_float * 3), ("pad2", C.c_uint32), ("rng_state", C.c_uint64), ("pad3", C.c_uint64)]
+
+
+class PathResult(C.Structure):
+    """AmberPathResult: the sum of the samples' measurements, the casts, the sampler state after the last sample -- 32 bytes."""
+    _fields_ = [("rgb", C.c_float * 3), ("casts", C.c_uint32), ("rng_state", C.c_uint64), ("pad", C.c_uint32 * 2)]
+
+
 class AovPixel(C.Structure):
     """AmberAovPixel: the sums of albedo, depth, normal and coverage of a pixel's first hits -- 32 bytes (amber_hip_pt_aov_pass)."""
     _fields_ = [("albedo", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("coverage", C.c_float)]
@@ -157,6 +168,9 @@ BUILD_REASON_NONE, BUILD_REASON_DEPTH, BUILD_REASON_WIDE, BUILD_REASON_BOUNDS = 
 RAYS_HOST = 1                # amber_hip_pt_cast_rays / amber_hip_pt_occluded: rays and output are host pointers
 _RAY = np.dtype([("origin", np.float32, (3,)), ("t_max", np.float32), ("dir", np.float32, (3,)), ("pad", np.uint32)])       # AmberRay
 _RAY_HIT = np.dtype([("t", np.float32), ("object", np.int32), ("pos", np.float32, (3,)), ("normal", np.float32, (3,))])    # AmberRayHit
+_PATH_RAY = np.dtype([("origin", np.float32, (3,)), ("pad0", np.uint32), ("dir", np.float32, (3,)), ("pad1", np.uint32),
+                      ("weight", np.float32, (3,)), ("pad2", np.uint32), ("rng_state", np.uint64), ("pad3", np.uint64)])                 # AmberPathRay
+_PATH_RESULT = np.dtype([("rgb", np.float32, (3,)), ("casts", np.uint32), ("rng_state", np.uint64), ("pad", np.uint32, (2,))])          # AmberPathResult
 RESOLVE_MEAN_F32, RESOLVE_RGB8, RESOLVE_RGBA8 = 0, 1, 2     # amber_hip_pt_resolve: format
 RESOLVE_HOST, RESOLVE_MIRROR_X = 1, 2                        # ... and flags: out is a host pointer / columns written right to left
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1     # amber_hip_pt_update_objects: keep the tree's topology and recompute its boxes / build the Morton tree again
@@ -166,6 +180,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_create", "amber_hip_pt_render_pass", "amber_hip_pt_clear", "amber_hip_pt_sync",
     "amber_hip_pt_download", "amber_hip_pt_device_framebuffer", "amber_hip_pt_stream", "amber_hip_pt_local_rows", "amber_hip_pt_kernel_time", "amber_hip_pt_build_info", "amber_hip_pt_update_objects", "amber_hip_pt_update_lens",
     "amber_hip_pt_cast_rays", "amber_hip_pt_occluded", "amber_hip_pt_resolve", "amber_hip_pt_destroy",
+    "amber_hip_pt_trace_paths", "amber_hip_sampler_state",
     "amber_hip_pt_aov_pass", "amber_hip_pt_aov_clear", "amber_hip_pt_aov_download", "amber_hip_pt_device_aov", "amber_hip_pt_denoise",
     "amber_hip_pt_render_batch", "amber_hip_pt_moments_clear", "amber_hip_pt_moments_download", "amber_hip_pt_device_moments", "amber_hip_pt_denoise_variance",
     "amber_hip_pt_temporal", "amber_hip_pt_temporal_reset", "amber_hip_pt_history_download", "amber_hip_pt_device_history",
@@ -235,6 +250,10 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "amber_hip_pt_cast_rays"):
         lib.amber_hip_pt_cast_rays.argtypes = [vp, u64, vp, vp, u32]
         lib.amber_hip_pt_occluded.argtypes = [vp, u64, vp, vp, u32]
+    if hasattr(lib, "amber_hip_pt_trace_paths"):
+        lib.amber_hip_pt_trace_paths.argtypes = [vp, u64, vp, vp, u32, u32, u32]
+        lib.amber_hip_sampler_state.argtypes = [u64, u32, u32]
+        lib.amber_hip_sampler_state.restype = u64
     if hasattr(lib, "amber_hip_pt_resolve"):
         lib.amber_hip_pt_resolve.argtypes = [vp, u32, u32, vp, u64, u32]
     if hasattr(lib, "amber_hip_pt_aov_pass"):
@@ -419,6 +438,29 @@ class HostScene:
             pass
 
 
+def sampler_state(seed: int, pixel: int, sample: int) -> int:
+    """amber_hip_sampler_state: the state the render kernels' sampler starts (pixel, sample) with under `seed` -- XorShiftSeed(SplitMix64(seed), pixel,
+    sample), never 0.  The eye-ray generator then draws 5 times (thin lens) or twice (pinhole) before the first cast.  No device is touched."""
+    return int(load_library().amber_hip_sampler_state(seed & 0xffffffffffffffff, pixel, sample))
+
+
+def _splitmix64(z):
+    """SplitMix64 on a numpy uint64 array (wrapping arithmetic)"""
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def sampler_states(seed: int, pixels, samples) -> np.ndarray:
+    """sampler_state for arrays of pixels and samples at once: (n,) uint64, equal to amber_hip_sampler_state element by element."""
+    pixels, samples = np.asarray(pixels, np.uint64), np.asarray(samples, np.uint64)
+    hashed = _splitmix64(np.array([seed & 0xffffffffffffffff], np.uint64))[0]
+    s = _splitmix64(hashed ^ ((pixels << np.uint64(32)) | samples))
+    return np.where(s == 0, np.uint64(0x9E3779B97F4A7C15), s).astype(np.uint64)
+
+
 class PathTracer:
     """amber_hip_pt handle: the device-side engine for one band of the framebuffer on one GPU."""
 
@@ -427,7 +469,7 @@ class PathTracer:
         """rows = (y0, y1) contiguous band; stripe = (S, period) keeps only rows with (y - y0) % period < S;
         flags = AMBER_PT_FLAG_* bits (PT_FLAG_BVH_POOL: engine BVH with the per-wave ray pool scheduler; PT_FLAG_DEVICE_BUILD: engine BVH's tree
         built on the device at create)."""
-        self.sensor = sensor
+        self.sensor, self.seed = sensor, seed
         self._scene, self._resident = scene, None     # update_objects: the scene's flattened kinds and materials (an update never changes them)
         rb, re = rows if rows is not None else (0, sensor.height)
         s_rows, s_period = stripe if stripe else (0, 0)
@@ -629,6 +671,54 @@ class PathTracer:
         _check(lib.amber_hip_pt_occluded(self._h, n, packed.data_ptr(), out.data_ptr(), 0))
         self._torch_leave(same)
         return out.to(torch.bool)
+
+    def trace_paths(self, origins, dirs, weights=None, states=None, n_samples: int = 1, max_depth: int = 0):
+        """amber_hip_pt_trace_paths: the radiance that comes back along every ray (origins, dirs: (n, 3)) -- n_samples paths per ray through the
+        render kernels' bounce loop, each started at (origin, dir, weight) with the ray's sampler stream as the previous sample left it, their
+        measurements summed in order.  weights: (n, 3), None = 1.  states: (n,) uint64 sampler states (torch: int64 holding the same bits), None =
+        sampler_state(the handle's seed, i, 0); a state of 0 is replaced by 0x9E3779B97F4A7C15.  max_depth: 0 = the handle's, else it replaces
+        the handle's for this call.  Returns (rgb, casts, states_after): rgb (n, 3) float32 SUMS over the samples (divide by n_samples for the
+        estimate), casts (n,) uint32 (torch: int32, the same bits), states_after (n,) uint64 (torch: int64) to continue the streams with.
+
+        Memory and ordering as cast_rays: numpy arrays go through AMBER_RAYS_HOST and come back as numpy arrays; torch tensors on the handle's
+        device go zero-copy (packed into an (n, 16) float32 tensor) and torch tensors come back, ordered on the handle's stream -- call it under
+        `with torch.cuda.stream(torch.cuda.ExternalStream(pt.stream()))` to avoid the two waits."""
+        lib = load_library()
+        if self._is_torch(origins) or self._is_torch(dirs):
+            import torch
+            if not (self._is_torch(origins) and self._is_torch(dirs)) or not origins.is_cuda or origins.device != dirs.device:
+                raise AmberError("trace_paths: origins and dirs must both be numpy arrays or both be torch tensors on the handle's device")
+            o, d = origins.reshape(-1, 3).to(torch.float32), dirs.reshape(-1, 3).to(torch.float32)
+            n = len(o)
+            if len(d) != n:
+                raise AmberError("trace_paths: origins and dirs differ in length")
+            packed = torch.zeros((n, 16), dtype=torch.float32, device=o.device)
+            packed[:, 0:3], packed[:, 4:7] = o, d
+            if weights is None:
+                packed[:, 8:11] = 1.0
+            else:
+                packed[:, 8:11] = torch.as_tensor(weights, device=o.device).to(torch.float32).reshape(-1, 3)
+            if states is None:
+                states = sampler_states(self.seed, np.arange(n), np.zeros(n))
+            if not self._is_torch(states):
+                states = torch.from_numpy(np.ascontiguousarray(states, np.uint64).view(np.int64))
+            packed.view(torch.int64)[:, 6] = states.to(device=o.device, dtype=torch.int64).reshape(-1)
+            out = torch.empty((n, 8), dtype=torch.float32, device=o.device)
+            same = self._torch_enter(torch, o.device)
+            _check(lib.amber_hip_pt_trace_paths(self._h, n, packed.data_ptr(), out.data_ptr(), n_samples, max_depth, 0))
+            self._torch_leave(same)
+            return out[:, 0:3].contiguous(), out[:, 3].contiguous().view(torch.int32), out.view(torch.int64)[:, 2].contiguous()
+        o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
+        n = len(o)
+        if len(d) != n:
+            raise AmberError("trace_paths: origins and dirs differ in length")
+        packed = np.zeros(n, _PATH_RAY)
+        packed["origin"], packed["dir"] = o, d
+        packed["weight"] = 1.0 if weights is None else _f32(weights).reshape(-1, 3)
+        packed["rng_state"] = sampler_states(self.seed, np.arange(n), np.zeros(n)) if states is None else np.asarray(states, np.uint64).reshape(-1)
+        res = np.zeros(n, _PATH_RESULT)
+        _check(lib.amber_hip_pt_trace_paths(self._h, n, packed.ctypes.data, res.ctypes.data, n_samples, max_depth, RAYS_HOST))
+        return res["rgb"].copy(), res["casts"].copy(), res["rng_state"].copy()
 
     def _torch_enter(self, torch, device) -> bool:
         """True when torch's current stream IS the handle's stream (everything is ordered already); otherwise torch's stream is waited for."""

@@ -21,6 +21,8 @@
 //   ray_query.inc          amber_hip_pt_cast_rays / amber_hip_pt_occluded: the caller's rays through the handle's engine -- engine BVH in a persistent refill
 //                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>;
 //                          LaunchPerItem, the launch of every kernel with a thread per item (its engine front end: dev_closest_hit.h).
+//   path_query.inc         amber_hip_pt_trace_paths: radiance along the caller's rays -- the bounce loop of the render kernels from (origin, dir, weight, sampler
+//                          state) records, a lane per ray with its samples in sequence, idle lanes refilled per ray from one counter; every engine.
 //   image_stage.inc        what the five files below share, the stage that runs on the band after accumulation: BandPixels, the zero-on-first-use band
 //                          buffer (AOV sums, moments, history) with its clear / download / device pointer, the check of the output arguments and the
 //                          output tail, the check of the filters' parameters, the device helpers of the filters' kernels (stops, luminance, guide record).
@@ -513,6 +515,7 @@ int amber_hip_pt_create(const AmberFlatScene* s, const AmberSensor* sensor, cons
 #include "pt_launch.inc"
 
 #include "ray_query.inc"
+#include "path_query.inc"
 #include "image_stage.inc"
 #include "resolve.inc"
 #include "aov.inc"
@@ -693,6 +696,12 @@ int amber_hip_pt_cast_rays(amber_hip_pt* h, uint64_t n, const AmberRay* rays, Am
 int amber_hip_pt_occluded(amber_hip_pt* h, uint64_t n, const AmberRay* rays, uint8_t* occluded, uint32_t flags) {
   return Guarded("amber_hip_pt_occluded", [&] { return RayQuery(h, n, rays, occluded, flags, true, "amber_hip_pt_occluded"); });
 }
+
+int amber_hip_pt_trace_paths(amber_hip_pt* h, uint64_t n, const AmberPathRay* rays, AmberPathResult* out, uint32_t n_samples, uint32_t max_depth, uint32_t flags) {
+  return Guarded("amber_hip_pt_trace_paths", [&] { return TracePaths(h, n, rays, out, n_samples, max_depth, flags); });
+}
+
+uint64_t amber_hip_sampler_state(uint64_t seed, uint32_t pixel, uint32_t sample) { return HostXorShiftSeed(HostSplitMix64(seed), pixel, sample); }
 
 int amber_hip_pt_resolve(amber_hip_pt* h, uint32_t n_samples, uint32_t format, void* out, uint64_t out_bytes, uint32_t flags) {
   return Guarded("amber_hip_pt_resolve", [&] { return Resolve(h, n_samples, format, out, out_bytes, flags); });

@@ -34,7 +34,8 @@ extern "C" {
                                     a new function; nothing that existed changed its layout or meaning.  Still 3 with amber_hip_pt_update_objects(): a new function.
                                     Still 3 with amber_hip_pt_cast_rays() / amber_hip_pt_occluded(): two new functions and their two structs.
                                     Still 3 with amber_hip_pt_update_lens(): a new function.  Still 3 with amber_hip_pt_resolve(): a new function.
-                                    Still 3 with amber_hip_pt_aov_pass() / _aov_clear() / _aov_download() / amber_hip_pt_device_aov(): four new functions and their struct */
+                                    Still 3 with amber_hip_pt_aov_pass() / _aov_clear() / _aov_download() / amber_hip_pt_device_aov(): four new functions and their struct.
+                                    Still 3 with amber_hip_pt_trace_paths() / amber_hip_sampler_state(): two new functions and their two structs */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -303,6 +304,41 @@ typedef struct { float t; int32_t object; float pos[3]; float normal[3]; } Amber
 enum { AMBER_RAYS_HOST = 1u };   /* rays / out are host pointers: the call stages them and waits */
 int  amber_hip_pt_cast_rays(amber_hip_pt*, uint64_t n, const AmberRay* rays, AmberRayHit* hits, uint32_t flags);
 int  amber_hip_pt_occluded(amber_hip_pt*, uint64_t n, const AmberRay* rays, uint8_t* occluded, uint32_t flags);
+/* Radiance along the caller's own rays: the render kernels' bounce loop (PathTracing::Thread::Render, algorithm_pt.cc:137-157: closest hit, Radiance,
+ * SampleLight, Russian roulette) started from rays of the caller's choosing instead of a camera pixel -- irradiance probes, light maps, shading a hit
+ * found with cast_rays, paths started elsewhere.  Still ABI version 3: two new functions and their two structs.
+ * Definition.  Every operation is binary32 and rounded alone; the arithmetic is the render kernels' own device functions.  For ray i:
+ *   r = rays[i].rng_state; r == 0 is replaced by 0x9E3779B97F4A7C15 (a zero xorshift state draws 0 forever, and Russian roulette would never end a path)
+ *   sum = (+0, +0, +0), casts = 0
+ *   for k = 0 .. n_samples - 1, in this order: one path starts at (origin, dir, weight) with measurement +0, no origin object, and the sampler stream r
+ *     as the previous sample left it; it takes bounces (one Scene::Cast each, then Radiance, SampleLight, Russian roulette with the handle's
+ *     max_depth) until one ends it; then sum = sum + measurement per channel, casts += the path's casts
+ *   out[i] = {sum, casts (mod 2^32), r after the last sample, 0, 0}
+ * A ray with a NaN component in origin or dir misses at its first cast, as in cast_rays: the cast is counted and nothing is drawn.  dir is used as
+ * given and never normalised.  The pads of a ray are ignored.
+ * Consequences.  A path whose first hit is a light seen from its front gives 0 + weight * rho with 1 cast and one draw (the light's scatter weight is
+ * 0, so roulette ends it).  A miss gives +0 with 1 cast and no draw.  A call with n_samples = a + b equals a call with a followed by a call with b
+ * started from the returned states, the two sums added in that order.  The result for ray i does not depend on n, on its position in the batch or on
+ * the other rays.  With rng_state = amber_hip_sampler_state(seed, pixel, s) advanced by the draws of the eye-ray generator (5 for a thin lens, 2 for
+ * a pinhole), the eye ray of (pixel, s) and its weight, one sample reproduces the measurement and the cast count of that path of
+ * amber_hip_pt_render_pass.
+ * max_depth: 0 = the handle's own (AmberPtParams.max_depth); any other value replaces it for this call only.
+ * amber_hip_sampler_state(seed, pixel, sample): the state the render kernels' sampler starts (pixel, sample) with, XorShiftSeed(SplitMix64(seed),
+ * pixel, sample), never 0 -- for decorrelated streams of one's own, or to reproduce a rendered path.  Host arithmetic only; no device, no handle.
+ * Memory, order and errors as amber_hip_pt_cast_rays: DEVICE pointers by default, asynchronous and stream-ordered on the handle's stream (a query
+ * enqueued before amber_hip_pt_update_objects / amber_hip_pt_update_lens sees the old scene, one enqueued after it the new one); with AMBER_RAYS_HOST
+ * HOST pointers staged through buffers the handle owns (half a million rays at a time), returning after the copy back.  The call never touches the
+ * framebuffer, the ray counter or amber_hip_pt_kernel_time.  n == 0 or n_samples == 0: AMBER_OK, nothing written.  AMBER_EINVAL, the handle left
+ * working: a NULL handle, a NULL pointer with work to do, n > 2^31, n_samples > 65536, unknown flag bits, an AMBER_BVH_WIDE measurement build.
+ * Engines: every product engine in both builds, AMBER_PT_FLAG_DEVICE_BUILD and AMBER_PT_FLAG_BVH_ITEMS handles included; a handle of the lab engine
+ * WAVEFRONT answers as engine AUTO does.  On engine BVH an origin outside the scene's bounding sphere takes the scan of every object on that first
+ * cast, as in amber_hip_pt_aov_pass.  The work is one lane per ray, the samples of a ray in sequence: few rays with many samples keep few lanes busy. */
+typedef struct { float origin[3]; uint32_t pad0; float dir[3]; uint32_t pad1;
+                 float weight[3]; uint32_t pad2; uint64_t rng_state; uint64_t pad3; } AmberPathRay;     /* 64 bytes: four float4 */
+typedef struct { float rgb[3]; uint32_t casts; uint64_t rng_state; uint32_t pad[2]; } AmberPathResult;  /* 32 bytes: two float4 */
+int  amber_hip_pt_trace_paths(amber_hip_pt*, uint64_t n, const AmberPathRay* rays, AmberPathResult* out,
+                              uint32_t n_samples, uint32_t max_depth /* 0: the handle's */, uint32_t flags /* AMBER_RAYS_HOST */);
+uint64_t amber_hip_sampler_state(uint64_t seed, uint32_t pixel, uint32_t sample);
 /* The output stage on the device: the framebuffer's sums as the mean image or as the 8-bit image the reference's command line writes
  * (postprocess::Filmic, then postprocess::Gamma(2.2): filmic.cc:30-66, gamma.cc:36-52), without the round trip amber_hip_pt_download + a host tone
  * map.  Covers every pixel of the handle's band in amber_hip_pt_download's layout: amber_hip_pt_local_rows rows in increasing y, compact, width
