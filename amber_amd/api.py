@@ -83,6 +83,17 @@ class LtPassInfo(C.Structure):
                 ("longest_run", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class Photon(C.Structure):
+    """AmberPhoton: a light-path vertex -- pos, object | dir_out, path | weight, sample | normal, bounce: 64 bytes, four float4 (amber_hip_lt_trace_photons)."""
+    _fields_ = [("pos", C.c_float * 3), ("object", C.c_int32), ("dir_out", C.c_float * 3), ("path", C.c_uint32),
+                ("weight", C.c_float * 3), ("sample", C.c_uint32), ("normal", C.c_float * 3), ("bounce", C.c_uint32)]
+
+
+class PhotonInfo(C.Structure):
+    """AmberPhotonInfo: the totals of one amber_hip_lt_trace_photons call -- 32 bytes."""
+    _fields_ = [("n_photons", C.c_uint64), ("n_written", C.c_uint64), ("n_rays", C.c_uint64), ("n_launches", C.c_uint32), ("n_repeats", C.c_uint32)]
+
+
 class AccumulateInfo(C.Structure):
     """AmberAccumulateInfo (lab build): what one amber_hip_kat_accumulate call did."""
     _fields_ = [("n_launches", C.c_uint32), ("n_repeats", C.c_uint32), ("rec_count", C.c_uint32), ("flag_words_set", C.c_uint32),
@@ -91,6 +102,11 @@ class AccumulateInfo(C.Structure):
 
 LT_SPLAT_CAPACITY0 = 65536   # AMBER_LT_SPLAT_CAPACITY0: records the handle's splat buffer holds before the first growth
 SPLAT_DTYPE = np.dtype([("path", np.uint32), ("sample", np.uint32), ("bounce", np.uint32), ("pixel", np.uint32), ("rgb", np.float32, (3,)), ("pad", np.uint32)])   # AmberSplat
+PHOTON_DIFFUSE, PHOTON_SPECULAR, PHOTON_LIGHT, PHOTON_EYE, PHOTON_ALL = 1, 2, 4, 8, 15   # AMBER_PHOTON_*: the surface kinds whose vertices are recorded
+PHOTONS_HOST = 1             # AMBER_PHOTONS_HOST: out is a host pointer
+PHOTON_CAPACITY0 = 65536     # AMBER_PHOTON_CAPACITY0: records the handle's photon staging buffer holds before the first growth
+PHOTON_DTYPE = np.dtype([("pos", np.float32, (3,)), ("object", np.int32), ("dir_out", np.float32, (3,)), ("path", np.uint32),
+                         ("weight", np.float32, (3,)), ("sample", np.uint32), ("normal", np.float32, (3,)), ("bounce", np.uint32)])   # AmberPhoton
 
 
 class Ray(C.Structure):
@@ -185,6 +201,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_render_batch", "amber_hip_pt_moments_clear", "amber_hip_pt_moments_download", "amber_hip_pt_device_moments", "amber_hip_pt_denoise_variance",
     "amber_hip_pt_temporal", "amber_hip_pt_temporal_reset", "amber_hip_pt_history_download", "amber_hip_pt_device_history",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range", "amber_hip_lt_render_pass",
+    "amber_hip_lt_trace_photons",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
 ]
@@ -193,6 +210,7 @@ LAB_SYMBOLS = [
     "amber_hip_kat_cast", "amber_hip_kat_sample", "amber_hip_kat_eye", "amber_hip_kat_trace", "amber_hip_kat_math", "amber_hip_kat_signatures", "amber_hip_pt_signatures",
     "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump", "amber_hip_kat_division",
     "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep", "amber_hip_kat_lt_accumulate", "amber_hip_kat_lt_stage_ms",
+    "amber_hip_kat_photon_stage_ms",
     "amber_hip_kat_light_ray", "amber_hip_kat_lens_response", "amber_hip_kat_radiance", "amber_host_kat_scene_lights",
     "amber_hip_kat_accumulate",
 ]
@@ -280,6 +298,10 @@ def load_library() -> C.CDLL:
         lib.amber_hip_lt_trace_range.argtypes = [vp, u32, u32, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(lib, "amber_hip_lt_render_pass"):
         lib.amber_hip_lt_render_pass.argtypes = [vp, u32, u32, C.POINTER(LtPassInfo)]
+        if hasattr(lib, "amber_hip_lt_trace_photons"):      # (a library built before it has no such symbol)
+            lib.amber_hip_lt_trace_photons.argtypes = [vp, u32, u32, u32, u32, u32, vp, u64, C.POINTER(PhotonInfo), u32]
+        if hasattr(lib, "amber_hip_kat_photon_stage_ms"):   # lab build
+            lib.amber_hip_kat_photon_stage_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(lib, "amber_hip_kat_cast"):         # the lab build (include/amber_hip_lab.h); the product exports none of these
         lib.amber_hip_kat_cast.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         lib.amber_hip_kat_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
@@ -920,7 +942,63 @@ class PathTracer:
         _check(load_library().amber_hip_lt_render_pass(self._h, first_sample, n_samples, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in LtPassInfo._fields_ if k != "pad"}
 
+    def lt_trace_photons(self, first_sample: int, n_samples: int, surfaces: int = PHOTON_DIFFUSE, paths=None, out=None):
+        """amber_hip_lt_trace_photons: the vertices of the light paths lt_trace traces -- passes [first_sample, first_sample + n_samples) of the light paths
+        [paths[0], paths[1]) (None: all W*H) -- on the surfaces `surfaces` selects (PHOTON_* bits), as AmberPhoton records (PHOTON_DTYPE) in ascending
+        (sample, path, bounce) order: pos, normal and object of the hit, dir_out = -ray direction, weight = the path weight on arrival (divide by the
+        number of paths for PhotonMap::Build's photons), bounce counted from 1.  include/amber_hip.h states it; tests/photon_reference.py restates it.
+        Returns (records, info): info is AmberPhotonInfo as a dict (n_photons, n_written, n_rays, n_launches, n_repeats).
+        out=None: a counting call, then a filling call into a numpy structured array of exactly that size, which is returned.
+        out = a numpy array of PHOTON_DTYPE: filled through AMBER_PHOTONS_HOST; its first n_written records are returned (a view).
+        out = a torch tensor on the handle's device (contiguous, rows of 64 bytes, e.g. (capacity, 16) float32), or (device pointer, capacity): written
+        zero-copy on the handle's stream (ORDERING as cast_rays; the call waits for the handle's stream before it returns); the tensor's first n_written
+        rows, or n_written, are returned.  A buffer that is too small raises AmberError with .code == -4 and .info["n_photons"] = the records needed."""
+        lib = load_library()
+        begin, end = (0, self.sensor.width * self.sensor.height) if paths is None else (int(paths[0]), int(paths[1]))
+        info = PhotonInfo()
+
+        def call(ptr, capacity, flags):
+            rc = lib.amber_hip_lt_trace_photons(self._h, first_sample, n_samples, begin, end, surfaces, ptr, capacity, C.byref(info), flags)
+            d = {k: int(getattr(info, k)) for k, _ in PhotonInfo._fields_}
+            if rc != 0:
+                try:
+                    _check(rc)
+                except AmberError as e:
+                    e.code, e.info = rc, d
+                    raise
+            return d
+
+        if out is None:
+            need = call(None, 0, PHOTONS_HOST)["n_photons"]
+            out = np.zeros(need, PHOTON_DTYPE)
+            d = call(out.ctypes.data if need else None, need, PHOTONS_HOST)
+            return out, d
+        if isinstance(out, np.ndarray):
+            if out.dtype != PHOTON_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
+                raise AmberError("lt_trace_photons: out must be a contiguous one-dimensional numpy array of PHOTON_DTYPE")
+            d = call(out.ctypes.data if len(out) else None, len(out), PHOTONS_HOST)
+            return out[: d["n_written"]], d
+        if self._is_torch(out):
+            import torch
+            if not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] * out.element_size() != 64:
+                raise AmberError("lt_trace_photons: out must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
+            same = self._torch_enter(torch, out.device)
+            try:
+                d = call(out.data_ptr() if out.shape[0] else None, out.shape[0], 0)
+            finally:
+                self._torch_leave(same)
+            return out[: d["n_written"]], d
+        ptr, capacity = out
+        d = call(ptr, capacity, 0)
+        return d["n_written"], d
+
     # ---- known-answer entry points -----------------------------------------------------------
+    def kat_photon_stage_ms(self):
+        """Lab build: (trace ms, sort ms, gather ms) of lt_trace_photons by hipEvents since the previous call; the first call switches the timing on."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(load_library().amber_hip_kat_photon_stage_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def kat_lt_accumulate(self, records) -> None:
         """Lab build: lt_render_pass's device path (order by (pixel, pass, path, bounce), ordered sum) on the caller's records -- a structured array of
         lt_trace's dtype, in any order -- into the framebuffer."""

@@ -284,23 +284,34 @@ struct Bounce { int object; float t; V3 pos; V3 weight_before; };
 // emitted radiance, and the material is sampled with SampleImportance.
 struct SplatSink { DevSplat* records; unsigned int* count; uint32_t capacity; uint32_t path, sample; float size_f; };
 
-template <bool kTrace, int kEngine, bool kLight, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u>
+// kSink (kLight only): what a light path leaves behind.  SINK_SPLATS: the splat of a hit on an Eye surface (amber_hip_lt_trace,
+// amber_hip_lt_render_pass).  SINK_PHOTONS: the vertex of every hit on a surface whose kind sink->surfaces selects (amber_hip_lt_trace_photons,
+// PhotonMap::Build photon_map.h:108-153) -- (position, -ray.Direction(), weight on arrival), recorded before the material is sampled, four float4
+// at photons[4 * slot] in AmberPhoton's layout; no splat.  The sink handed over is then a PhotonSink, `count` and `capacity` the photon buffer's.
+enum { SINK_SPLATS = 0, SINK_PHOTONS = 1 };
+struct PhotonSink : SplatSink { float4* photons; uint32_t surfaces; };
+// AMBER_PHOTON_CLAIM_PER_LANE=1 (measurement builds, EXPERIMENTS.md): every recording lane claims its slot with an atomic of its own.
+#ifndef AMBER_PHOTON_CLAIM_PER_LANE
+#define AMBER_PHOTON_CLAIM_PER_LANE 0
+#endif
+
+template <bool kTrace, int kEngine, bool kLight, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u, int kSink = SINK_SPLATS>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
                                           uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink);
 
-template <bool kTrace, int kEngine, bool kLight = false, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u>
+template <bool kTrace, int kEngine, bool kLight = false, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u, int kSink = SINK_SPLATS>
 __device__ __forceinline__ bool PathStep(const DevScene& sc, const DevObject* lds_objects, int32_t* lds_stack, V3& o, V3& d, V3& weight, V3& measurement,
                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink = nullptr,
                                          const bool use_premask = false, const uint32_t premask = 0u, const int bvh_stack_cap = AMBER_BVH_STACK) {
   HitRec h;
   ClosestHit<kEngine, (kSqrtMask & 8u) ? SQRT_EXACT : SQRT_PLAIN>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG, use_premask, premask, bvh_stack_cap);
-  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit, kSqrtMask>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink);
+  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit, kSqrtMask, kSink>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink);
 }
 
 // Everything of a bounce after the closest-hit query (algorithm_pt.cc:140-157): h is the result of Scene::Cast.
-template <bool kTrace, int kEngine, bool kLight, bool kDivBasis, bool kDivHit, uint32_t kSqrtMask>
+template <bool kTrace, int kEngine, bool kLight, bool kDivBasis, bool kDivHit, uint32_t kSqrtMask, int kSink>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
-                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink) {
+                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* splat_sink) {
   casts++;
   if (h.idx < 0) {
     if (kTrace) { trace->object = -1; trace->t = __builtin_nanf(""); trace->pos = v3(0, 0, 0); trace->weight_before = v3(0, 0, 0); }
@@ -313,7 +324,35 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
   if (kTrace) { trace->object = h.idx; trace->t = h.t; trace->pos = pos; trace->weight_before = weight; }
   V3 dir_in, sw;
   if (kLight) {
-    if (m.kind == MAT_EYE) {                                                 // algorithm_lt.cc:141-147
+    if (kSink == SINK_PHOTONS) {
+      const PhotonSink* const sink = static_cast<const PhotonSink*>(splat_sink);
+      // Lambertian, Phong -> AMBER_PHOTON_DIFFUSE; Specular, Refraction -> _SPECULAR; DiffuseLight -> _LIGHT; Eye -> _EYE: a nibble per kind
+      const bool rec = ((0x842211u >> (m.kind * 4u)) & sink->surfaces) != 0u;
+      // Slots are claimed once per WAVE: a path makes several records and a launch millions, all on one counter (the L2 retires ~88 returning
+      // atomics per microsecond on one word, MI355X_MICROARCH.md).  The lanes that record vote, the first of them adds their number, every one
+      // takes the base from that lane's register (readlane names the lane: whatever lanes are active here, it is the one that holds the answer).
+#if !AMBER_PHOTON_CLAIM_PER_LANE
+      const unsigned long long voters = __ballot(rec);
+#endif
+      if (rec) {
+#if AMBER_PHOTON_CLAIM_PER_LANE
+        const unsigned int k = atomicAdd(sink->count, 1u);
+#else
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(voters >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(voters), 0u));
+        unsigned int base = 0u;
+        if (rank == 0u) base = atomicAdd(sink->count, static_cast<unsigned int>(__popcll(voters)));
+        const unsigned int k = static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(base), __builtin_ctzll(voters))) + rank;
+#endif
+        if (k < sink->capacity) {                                            // a slot beyond the buffer is not written: the counter tells the host to repeat the launch
+          float4* const r = sink->photons + static_cast<size_t>(k) * 4u;     // AmberPhoton: four 16-byte stores
+          r[0] = make_float4(pos.x, pos.y, pos.z, __int_as_float(h.idx));
+          r[1] = make_float4(dir_out.x, dir_out.y, dir_out.z, __uint_as_float(sink->path));
+          r[2] = make_float4(weight.x, weight.y, weight.z, __uint_as_float(sink->sample));
+          r[3] = make_float4(normal.x, normal.y, normal.z, __uint_as_float(casts));
+        }
+      }
+    } else if (m.kind == MAT_EYE) {                                          // algorithm_lt.cc:141-147
+      const SplatSink* const sink = splat_sink;
       uint32_t pixel; float value;
       if (LensResponse(sc, pos, dir_out, pixel, value)) {
         const V3 add = (weight * value) / sink->size_f;

@@ -451,6 +451,17 @@ int amber_hip_kat_lt_stage_ms(amber_hip_pt* h, double* sort_ms, double* sum_ms) 
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_photon_stage_ms(amber_hip_pt* h, double* trace_ms, double* sort_ms, double* gather_ms) { return Guarded("amber_hip_kat_photon_stage_ms", [&]() -> int {
+  if (!h) return Fail(AMBER_EINVAL, "null handle");
+  PhotonBufs& s = h->photons;
+  s.stage_timing = true;
+  if (trace_ms) *trace_ms = s.trace_ms;
+  if (sort_ms) *sort_ms = s.sort_ms;
+  if (gather_ms) *gather_ms = s.gather_ms;
+  s.trace_ms = s.sort_ms = s.gather_ms = 0;
+  return AMBER_OK;
+}); }
+
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out) { return Guarded("amber_hip_kat_math", [&]() -> int {
   if (!x || !out || mode < 0 || mode > 3) return Fail(AMBER_EINVAL, "bad argument");
   if (n == 0) return AMBER_OK;

@@ -167,7 +167,7 @@ int LtRenderPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, Amb
   AmberLtPassInfo total{};
   unsigned long long rays_begin = 0, rays_kept = 0;
   bool have_begin = false, repeated = false;
-  const int rc = LtTraceLaunches(h, first_sample, n_samples, 0u, n_paths, true, s.capacity,
+  const int rc = LtTraceLaunches(h, first_sample, n_samples, 0u, n_paths, true, s.capacity, SplatLtSink(h),
                                  [&](uint32_t, uint32_t, unsigned int produced, unsigned long long rays_before, unsigned long long rays_now, bool* again) -> int {
     if (!have_begin) { rays_begin = rays_kept = rays_before; have_begin = true; }
     total.n_launches++;

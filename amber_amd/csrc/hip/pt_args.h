@@ -16,6 +16,7 @@ struct RenderArgs {
   DevSplat* splats;          // light tracing: splat records, their counter and capacity
   unsigned int* splat_count;
   uint32_t splat_capacity;
+  uint32_t photon_surfaces;  // amber_hip_lt_trace_photons: the AMBER_PHOTON_* mask; `splats` then holds AmberPhoton records (64 B), counter and capacity are theirs
   int32_t* bvh_stack;        // pt_bvh_pool_kernel: traversal-stack levels beyond the LDS part, [level][thread of the grid]
   float* carried;            // pt_bvh_pool_kernel: measurements of the (degenerate) paths that carry a non-zero one across bounces, [thread of the grid * kRays/64 ...]
   const uint32_t* pixel_mask; // pt_megakernel, two-phase engine: candidate mask of every band pixel's primary rays (pixel_mask_kernel); null = off
@@ -41,6 +42,15 @@ struct RenderArgs {
   }
   void SetSamples(uint32_t first_sample_, uint32_t n_samples_) { first_sample = first_sample_; n_samples = n_samples_; div_samples = MakeExactDiv(n_samples_); }
 };
+
+// What a bounce of a light path is handed for its records: the splat sink, or (kPhotons) the vertex sink of amber_hip_lt_trace_photons over the same
+// three arguments
+template <bool kPhotons>
+__device__ __forceinline__ typename std::conditional<kPhotons, PhotonSink, SplatSink>::type MakeLightSink(const RenderArgs& a, uint32_t path, uint32_t sample) {
+  const SplatSink splat{a.splats, a.splat_count, a.splat_capacity, path, sample, a.scene.sensor.size_f};
+  if constexpr (kPhotons) return PhotonSink{splat, reinterpret_cast<float4*>(a.splats), a.photon_surfaces};
+  else return splat;
+}
 
 // Local row of a band -> row of the frame: contiguous rows from row_begin (stripe_rows == 0: the divider is not used), or stripes of stripe_rows rows
 // every stripe_period rows.  The kernels that read these fields as plain arguments share it; pt_megakernel reads them cold, one by one (pt_megakernel.inc).

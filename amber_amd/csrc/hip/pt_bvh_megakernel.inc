@@ -19,7 +19,8 @@
 #endif
 // kSig (tests only, amber_hip_pt_signatures): the same kernel also hashes every cast's hit object and hit distance and stores the pair
 // at the path's end -- config 3's PRODUCT kernel compared with the oracle path by path, like pt_megakernel's signature instantiation.
-template <bool kLight, int kStack, bool kSig = false>
+// kPhotons (with kLight, amber_hip_lt_trace_photons): a vertex record per selected hit instead of the splats (PathShade, SINK_PHOTONS).
+template <bool kLight, int kStack, bool kSig = false, bool kPhotons = false>
 __global__ void __launch_bounds__(256, kStack <= 24 && !kSig ? AMBER_BVH_WGS : 4) pt_bvh_megakernel(const RenderArgs a) {
   const DevScene& sc = a.scene;
   const uint32_t lane = threadIdx.x & 63u;
@@ -136,8 +137,9 @@ __global__ void __launch_bounds__(256, kStack <= 24 && !kSig ? AMBER_BVH_WGS : 4
     if (alive && !traversing) {                             // shade the lanes whose closest hit is known
       V3 meas = v3(my_sum[768], my_sum[1024], my_sum[1280]);  // the measurement is read and written once per bounce: LDS, not registers held across the traversal
       if (kLight) {
-        const SplatSink sink{a.splats, a.splat_count, a.splat_capacity, pixel, s - 1u, sc.sensor.size_f};
-        alive = PathShade<false, ENGINE_BVH, true>(sc, nullptr, hit, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_SHADE_STAMP_ARG, &sink);
+        if (kPhotons) BvhResolveIndex(sc, hit);               // a vertex names its object
+        const typename std::conditional<kPhotons, PhotonSink, SplatSink>::type sink = MakeLightSink<kPhotons>(a, pixel, s - 1u);
+        alive = PathShade<false, ENGINE_BVH, true, false, false, 0u, kPhotons ? SINK_PHOTONS : SINK_SPLATS>(sc, nullptr, hit, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_SHADE_STAMP_ARG, &sink);
       } else if (kSig) {
         BvhResolveIndex(sc, hit);                             // only the signature variant reports object indices
         Bounce b;

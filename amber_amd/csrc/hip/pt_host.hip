@@ -38,6 +38,8 @@
 //                          through the previous lens, validates it against the previous guide records, blends and writes; then denoise.inc's levels.
 //   lt_accumulate.inc      amber_hip_lt_render_pass: the splat records of a light-tracing launch into the framebuffer in the reference's order -- an index
 //                          permutation sorted by (pixel, pass, path, bounce) with two stable radix sorts, then one thread per pixel run.
+//   lt_photons.inc         amber_hip_lt_trace_photons: the vertex records of a light-tracing launch (PathShade's second sink) into the caller's buffer in
+//                          (sample, path, bounce) order -- two stable radix sorts of an index permutation, one gather of the 64-byte records.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -166,6 +168,19 @@ struct LtAccumBufs {
   Event ev[3];
 #endif
 };
+// amber_hip_lt_trace_photons (lt_photons.inc): nothing of it exists before the first call; the sorts borrow LtAccumBufs' keys, permutations and scratch
+struct PhotonBufs {
+  DevBuf<float4> staging;                   // the records of the launch in flight in arrival order, four float4 each
+  uint32_t capacity = 0;                    // records it holds: AMBER_PHOTON_CAPACITY0, or what a launch made it grow to
+  DevBuf<unsigned int> count;               // slots claimed by the launch in flight
+  DevBuf<unsigned long long> rays;          // casts of the call in flight: a counter of its own, the handle's is not touched
+  DevBuf<float4> sorted;                    // AMBER_PHOTONS_HOST: a launch's records in key order, on their way to the host
+#ifdef AMBER_LAB
+  bool stage_timing = false;                // amber_hip_kat_photon_stage_ms: trace, sort and gather timed with events (waits for the stream after every launch's gather)
+  double trace_ms = 0, sort_ms = 0, gather_ms = 0;
+  Event ev[5];
+#endif
+};
 // The image stage -- everything that runs on the band after accumulation (image_stage.inc and the five files behind it): its buffers, per band pixel
 struct ImageStageBufs {
   DevBuf<uint8_t> resolve_out;              // AMBER_RESOLVE_HOST: staging of the output (WriteBandOutput), grown on first use and reused
@@ -272,6 +287,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<unsigned int> d_splat_count;
   uint64_t hashed_seed_lt = 0;
   LtAccumBufs lt;                           // amber_hip_lt_render_pass
+  PhotonBufs photons;                       // amber_hip_lt_trace_photons
   DevBuf<float> d_partial;                  // pt_bvh_megakernel: per-item sums
   PathLaunchBufs paths;                     // the path-granular launches and the one in flight
   DevBuf<int32_t> d_bvh_stack;              // pt_bvh_pool_kernel (lab build): deep traversal-stack levels
@@ -523,6 +539,7 @@ int amber_hip_pt_create(const AmberFlatScene* s, const AmberSensor* sensor, cons
 #include "denoise_variance.inc"
 #include "temporal.inc"
 #include "lt_accumulate.inc"
+#include "lt_photons.inc"
 
 namespace {
 #ifdef AMBER_LAB
@@ -589,7 +606,7 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   uint64_t total = 0;                                         // splats produced (also beyond the caller's capacity)
   unsigned long long rays_first = 0, rays_last = 0;
   bool any = false;
-  const int rc = LtTraceLaunches(h, first_sample, n_samples, path_begin, n_paths, false, dev_capacity,
+  const int rc = LtTraceLaunches(h, first_sample, n_samples, path_begin, n_paths, false, dev_capacity, SplatLtSink(h),
                                  [&](uint32_t, uint32_t, unsigned int produced, unsigned long long rays_before, unsigned long long rays_now, bool*) -> int {
     if (!any) { rays_first = rays_before; any = true; }
     rays_last = rays_now;
@@ -619,6 +636,11 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
 
 int amber_hip_lt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, AmberLtPassInfo* info) {
   return Guarded("amber_hip_lt_render_pass", [&] { return LtRenderPass(h, first_sample, n_samples, info); });
+}
+
+int amber_hip_lt_trace_photons(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end, uint32_t surfaces,
+                               AmberPhoton* out, uint64_t capacity, AmberPhotonInfo* info, uint32_t flags) {
+  return Guarded("amber_hip_lt_trace_photons", [&] { return TracePhotons(h, first_sample, n_samples, path_begin, path_end, surfaces, out, capacity, info, flags); });
 }
 
 int amber_hip_lt_trace(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, AmberSplat* out, uint32_t capacity,

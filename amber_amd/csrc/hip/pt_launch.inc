@@ -402,21 +402,32 @@ int RenderSamples(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels
   return RenderPassBvhItems(h, first, n, n_pixels, target, sig);
 }
 
+// What the launches of light tracing write and count into (`sink`): the splat records of amber_hip_lt_trace_range / amber_hip_lt_render_pass with the
+// handle's ray counter (SplatLtSink), or the vertex records of amber_hip_lt_trace_photons with a counter of that call's own (records of float4: the
+// kernels' kPhotons instantiations, photon_surfaces their mask).  The buffer is named, not pointed to: the callback may grow it between two launches.
+template <typename T>
+struct LtSink {
+  const DevBuf<T>& records; unsigned int* count; unsigned long long* rays; uint32_t photon_surfaces;
+  hipEvent_t ev_begin = nullptr, ev_end = nullptr;          // measurements: recorded around the kernel of every launch
+};
+LtSink<DevSplat> SplatLtSink(const amber_hip_pt* h) { return LtSink<DevSplat>{h->d_splats, h->d_splat_count.p, h->d_rays.p, 0u}; }
+
 // The launches of light tracing over the passes [first_sample, first_sample + n_samples) of the light paths [path_begin, path_begin + n_paths): what
-// amber_hip_lt_trace_range and amber_hip_lt_render_pass share.  Each launch leaves its splat records at h->d_splats in arrival order (at most
-// `capacity` of them, read again before every launch: the callback may have grown the buffer) and is waited for; then
+// amber_hip_lt_trace_range, amber_hip_lt_render_pass and amber_hip_lt_trace_photons share.  Each launch leaves its records at sink.records in arrival
+// order (at most `capacity` of them, read again before every launch: the callback may have grown the buffer) and is waited for; then
 //   after_launch(first, n, produced, rays_before, rays_now, &again)
-// sees the passes of the launch, the records it produced (also beyond the capacity) and the handle's ray counter before the first launch and now.
+// sees the passes of the launch, the records it produced (also beyond the capacity) and the sink's ray counter before the first launch and now.
 // It returns a status other than AMBER_OK to stop, or sets `again` to have exactly this launch repeated.  `timed`: amber_hip_pt_kernel_time counts
 // the launches.  n_samples and n_paths are not zero.
-// Launches run in pass order and each one's splats are sorted, so the concatenation is in (pass, path, bounce) order.
-template <typename F>
-int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t n_paths, bool timed, const uint32_t& capacity, F&& after_launch) {
+// Launches run in pass order and each one's records are sorted, so the concatenation is in (pass, path, bounce) order.
+template <typename T, typename F>
+int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t n_paths, bool timed, const uint32_t& capacity, const LtSink<T>& sink,
+                    F&& after_launch) {
   const bool bvh = h->hit_engine == AMBER_ENGINE_BVH;
   const char* const too_many = "too many light paths for one launch";
   if (amber_plan::LightLaunch(n_paths, bvh, n_samples).n == 0) return Fail(AMBER_EINVAL, too_many);      // (before anything is enqueued)
   unsigned long long rays_before = 0, rays_now = 0;
-  HIP_TRY(hipMemcpyAsync(&rays_before, h->d_rays, sizeof rays_before, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&rays_before, sink.rays, sizeof rays_before, hipMemcpyDeviceToHost, h->stream));
   return SplitSamples(first_sample, n_samples, too_many, [&](uint32_t left, amber_plan::Launch* l) -> int {
     *l = amber_plan::LightLaunch(n_paths, bvh, left);
     return AMBER_OK;
@@ -425,24 +436,29 @@ int LtTraceLaunches(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, 
     const uint64_t n_work = bvh ? static_cast<uint64_t>(n_paths) * n_chunks : static_cast<uint64_t>(n_paths) * l.n;
     RenderArgs a = MakeRenderArgs(h, h->hashed_seed_lt, n_paths, first, l.n);
     a.SetBand(0u, 0u, 0u);                                    // light paths have no band; every divider of the launch is a valid record all the same
-    a.ray_count = h->d_rays; a.next_item = h->d_next;
-    a.splats = h->d_splats; a.splat_count = h->d_splat_count; a.splat_capacity = capacity;
+    a.ray_count = sink.rays; a.next_item = h->d_next;
+    a.splats = reinterpret_cast<DevSplat*>(sink.records.p); a.splat_count = sink.count; a.splat_capacity = capacity; a.photon_surfaces = sink.photon_surfaces;
     a.path_offset = path_begin; a.n_items = static_cast<uint32_t>(n_work); a.shade_batch = h->bvh_shade_batch;
     const uint32_t n_blocks = PersistentBlocks(h, a.n_items);
     AMBER_TRY(CheckRefStack(h, n_blocks));
-    HIP_TRY(hipMemsetAsync(h->d_splat_count, 0, sizeof(unsigned int), h->stream));
+    HIP_TRY(hipMemsetAsync(sink.count, 0, sizeof(unsigned int), h->stream));
     HIP_TRY(hipMemsetAsync(h->d_next, 0, sizeof(unsigned int), h->stream));
+    if (sink.ev_begin) HIP_TRY(hipEventRecord(sink.ev_begin, h->stream));
     AMBER_TRY(TimedLaunch(h, timed, [&]() -> int {
       return WithHitEngine(h->hit_engine, [&](auto engine) -> int {
         constexpr int kEngine = decltype(engine)::value;
-        if constexpr (kEngine == ENGINE_BVH) hipLaunchKernelGGL((pt_bvh_megakernel<true, 24>), dim3(n_blocks), dim3(256), 0, h->stream, a);   // light tracing on engine BVH: always the item kernel
+        constexpr bool kPhotons = std::is_same<T, float4>::value;            // the vertex sink's records
+        if constexpr (kEngine == ENGINE_BVH && kPhotons) hipLaunchKernelGGL((pt_bvh_megakernel<true, 24, false, true>), dim3(n_blocks), dim3(256), 0, h->stream, a);
+        else if constexpr (kEngine == ENGINE_BVH) hipLaunchKernelGGL((pt_bvh_megakernel<true, 24>), dim3(n_blocks), dim3(256), 0, h->stream, a);   // light tracing on engine BVH: always the item kernel
+        else if constexpr (kPhotons) hipLaunchKernelGGL((pt_megakernel<kEngine | AMBER_KERNEL_PHOTONS, true>), dim3(n_blocks), dim3(256), 0, h->stream, a);
         else hipLaunchKernelGGL((pt_megakernel<kEngine, true>), dim3(n_blocks), dim3(256), 0, h->stream, a);
         return AMBER_OK;
       });
     }));
+    if (sink.ev_end) HIP_TRY(hipEventRecord(sink.ev_end, h->stream));
     unsigned int produced = 0;
-    HIP_TRY(hipMemcpyAsync(&produced, h->d_splat_count, sizeof produced, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(&rays_now, h->d_rays, sizeof rays_now, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&produced, sink.count, sizeof produced, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&rays_now, sink.rays, sizeof rays_now, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return after_launch(first, l.n, produced, rays_before, rays_now, again);
   });

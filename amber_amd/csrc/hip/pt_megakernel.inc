@@ -19,6 +19,8 @@
 //    other x.  HBM per launch: the bitmap (n_paths / 8 bytes, cleared and read once) and 16 B per record.
 //  * kLight: the same worker loop traces LIGHT paths (algorithm_lt.cc:112-163): path q = (light path index, pass),
 //    nothing is stored at a path's end, Eye hits append splat records instead.
+//  * kPhotons (with kLight, amber_hip_lt_trace_photons; kEngineSink = engine | AMBER_KERNEL_PHOTONS): the same light paths append a vertex record per
+//    selected hit instead (PathShade, SINK_PHOTONS).
 //  * kSig (tests only, amber_hip_pt_signatures): the same kernel also hashes every cast's hit object and hit distance and
 //    stores the pair at the path's end -- the PRODUCT kernel's paths, compared with the oracle's one by one.
 #define AMBER_WAVE_TIME_SLOTS 8192u          /* diagnostic build: per-wave timestamps behind the 8 section sums of RenderArgs.stamps */
@@ -49,8 +51,14 @@ template <bool kLight> struct PoolLayout { static constexpr int kChunks = 4; };
 #ifndef AMBER_PATH_BVH_STACK
 #define AMBER_PATH_BVH_STACK 12
 #endif
-template <int kEngine, bool kLight = false, bool kSig = false>
-__global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKERNEL_WAVES_PER_SIMD) pt_megakernel(const RenderArgs a) {
+// The vertex sink is selected by a bit of the engine argument, not by a fourth parameter: the symbols of the instantiations that exist are what tests
+// and tools find the headline kernel's ISA by, and a parameter more, defaulted or not, renames every one of them.
+#define AMBER_KERNEL_PHOTONS 0x100
+template <int kEngineSink, bool kLight = false, bool kSig = false>
+__global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == ENGINE_BVH ? 5 : AMBER_MEGAKERNEL_WAVES_PER_SIMD) pt_megakernel(const RenderArgs a) {
+  constexpr int kEngine = kEngineSink & ~AMBER_KERNEL_PHOTONS;
+  constexpr bool kPhotons = (kEngineSink & AMBER_KERNEL_PHOTONS) != 0;
+  static_assert(kLight || !kPhotons, "vertices are recorded along light paths");
   const DevScene& sc = a.scene;
   const uint32_t lane = threadIdx.x & 63u;
   constexpr bool kTwoPhase = EngineTraits<kEngine>::kTwoPhase;
@@ -227,8 +235,8 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? 5 : AMBER_MEGAKER
       if (!kLight && carries) meas = ld3(AMBER_CARRIED());
       if (kLight) {
         const uint32_t plocal = Quotient(a.div_samples, q);
-        const SplatSink sink{a.splats, a.splat_count, a.splat_capacity, a.path_offset + plocal, a.first_sample + (q - plocal * a.n_samples), sc.sensor.size_f};
-        alive = PathStep<false, kEngine, true>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
+        const typename std::conditional<kPhotons, PhotonSink, SplatSink>::type sink = MakeLightSink<kPhotons>(a, a.path_offset + plocal, a.first_sample + (q - plocal * a.n_samples));
+        alive = PathStep<false, kEngine, true, false, false, 0u, kPhotons ? SINK_PHOTONS : SINK_SPLATS>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
       } else if (kSig) {
         Bounce b;
         alive = PathStep<true, kEngine, false, kDivBasis, kDivHit, kSqrtMask>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);

@@ -35,7 +35,8 @@ extern "C" {
                                     Still 3 with amber_hip_pt_cast_rays() / amber_hip_pt_occluded(): two new functions and their two structs.
                                     Still 3 with amber_hip_pt_update_lens(): a new function.  Still 3 with amber_hip_pt_resolve(): a new function.
                                     Still 3 with amber_hip_pt_aov_pass() / _aov_clear() / _aov_download() / amber_hip_pt_device_aov(): four new functions and their struct.
-                                    Still 3 with amber_hip_pt_trace_paths() / amber_hip_sampler_state(): two new functions and their two structs */
+                                    Still 3 with amber_hip_pt_trace_paths() / amber_hip_sampler_state(): two new functions and their two structs.
+                                    Still 3 with amber_hip_lt_trace_photons(): one function, two structs, constants */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -626,6 +627,54 @@ int amber_hip_lt_trace_range(amber_hip_pt*, uint32_t first_sample, uint32_t n_sa
 #define AMBER_LT_SPLAT_CAPACITY0 65536u   /* records the handle's splat buffer holds before the first growth */
 typedef struct { uint64_t n_splats, n_rays; uint32_t n_launches, n_repeats, longest_run, pad; } AmberLtPassInfo;  /* 32 bytes */
 int amber_hip_lt_render_pass(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples, AmberLtPassInfo* info /* may be NULL */);
+
+/* ---- light-path vertices: photons ------------------------------------------------------------------------------------------------------------
+ * amber_hip_lt_trace_photons returns the vertices of the light paths amber_hip_lt_trace traces, instead of the splats they make: the list the
+ * reference's photon family starts from (PhotonMap::Build, photon_map.h:108-153: the loop of LightTracing::Thread::Render, which stores
+ * (position, -ray.Direction(), weight) where that one splats), and the light subpaths of the bidirectional family (GenerateLightSubpath).
+ * Definition.  Every operation is binary32 and rounded alone; the arithmetic is the light-tracing kernel's own device functions.  Light path i of
+ * pass s is the one amber_hip_lt_trace traces: its sampler starts at amber_hip_sampler_state(seed + 0x6C74, i, s), then GenerateLightRay and the
+ * loop of algorithm_lt.cc:135-162 with the handle's max_depth.  At the k-th cast of the path (k counts from 1, as AmberSplat.bounce does), if the
+ * cast hits an object whose material kind `surfaces` selects, one record is made, before the material is sampled: pos and normal are the
+ * reference's Intersect() output (as in AmberRayHit), object is the scene index (never a leaf slot), dir_out the negated ray direction, weight the
+ * path weight on arrival (PhotonMap::Build divides it by its n_photons: the caller's job, one division), path = i (the absolute light-path
+ * index), sample = s, bounce = k.  A vertex at k == max_depth is recorded, then the path ends.
+ * The call covers the passes [first_sample, first_sample + n_samples) of the light paths [path_begin, path_end).  The records are written in
+ * ascending (sample, path, bounce) order; that key names a record completely, so the output does not depend on scheduling, on the engine (except
+ * REFERENCE_BVH, which follows the reference's tree on ties, as everywhere), or on how the call splits its passes into launches.  Hence, bit for
+ * bit: one call over [a, a + m + n) equals the call over [a, a + m) followed by the call over [a + m, a + m + n); two calls over adjacent path
+ * ranges, merged by key, equal one call over the union; a call with mask m equals the call with AMBER_PHOTON_ALL filtered by material kind.
+ * Sizing.  The handle owns an arrival-order staging buffer that starts at AMBER_PHOTON_CAPACITY0 records and keeps what it grew to.  A launch that
+ * produces more records than fit is deterministic: the buffer grows to the count the launch reported and the launch is repeated once (n_repeats
+ * counts these), the protocol of amber_hip_lt_render_pass.  `out` is the caller's buffer, `capacity` its size in records.  When the call needs
+ * more than `capacity` records it answers AMBER_ENOMEM, info->n_photons holds the number the whole call needs, `out` is unspecified and the handle
+ * stays working.  out == NULL with capacity == 0 is a counting call: AMBER_OK, n_photons set, n_written == 0.  Otherwise AMBER_OK with
+ * n_written == n_photons; records beyond n_written are untouched.  n_rays is the number of casts: for [0, W*H) the ray_count amber_hip_lt_trace
+ * reports for the same passes.  info (may be NULL) is zeroed first, whatever the call then answers.
+ * Memory and order.  `out` is a device pointer, 16-byte aligned, and the call is stream-ordered on the handle's stream; it waits for the stream
+ * before it returns, because it reads a count per launch, as amber_hip_lt_trace does.  With AMBER_PHOTONS_HOST `out` is a host pointer, staged
+ * through a buffer the handle owns.  The call never touches the framebuffer, the handle's ray counter or amber_hip_pt_kernel_time.  What it
+ * allocates it allocates on first use (a handle that never calls it pays nothing); destroy releases it.  A call after amber_hip_pt_update_lens
+ * sees the new blades.
+ * AMBER_EINVAL, with no effect: a NULL handle; first_sample + n_samples > 2^32 - 1; path_begin > path_end or path_end > W*H; surfaces == 0 or
+ * unknown bits in it; unknown flag bits; out == NULL with capacity > 0; a misaligned device pointer; stale lights; the lab engine WAVEFRONT; an
+ * AMBER_BVH_WIDE build.  AMBER_OK with zero photons: n_samples == 0, an empty path range, a scene without lights.
+ * Banded and striped handles are accepted: light paths do not know the band, and the path range is how several devices share the work, as with
+ * amber_hip_lt_trace_range.  Every engine on which amber_hip_lt_trace works, AMBER_PT_FLAG_BVH_ITEMS and AMBER_PT_FLAG_DEVICE_BUILD included.
+ * Not here: the k-d tree, nearest-neighbour search and any density estimate; eye subpaths; the pdf and geometry-factor fields of SubpathEvent;
+ * the command line and the C++ adapter.  Still ABI version 3: one function, two structs, constants. */
+enum { AMBER_PHOTON_DIFFUSE = 1u,   /* AMBER_MAT_LAMBERTIAN, AMBER_MAT_PHONG   (SurfaceType::Diffuse)  */
+       AMBER_PHOTON_SPECULAR = 2u,  /* AMBER_MAT_SPECULAR, AMBER_MAT_REFRACTION (SurfaceType::Specular) */
+       AMBER_PHOTON_LIGHT = 4u,     /* AMBER_MAT_DIFFUSE_LIGHT */
+       AMBER_PHOTON_EYE = 8u,       /* AMBER_MAT_EYE: the aperture blades */
+       AMBER_PHOTON_ALL = 15u };
+enum { AMBER_PHOTONS_HOST = 1u };   /* out is a host pointer: the call stages the records and copies them back */
+#define AMBER_PHOTON_CAPACITY0 65536u   /* records the handle's photon staging buffer holds before the first growth */
+typedef struct { float pos[3]; int32_t object; float dir_out[3]; uint32_t path;
+                 float weight[3]; uint32_t sample; float normal[3]; uint32_t bounce; } AmberPhoton;      /* 64 bytes: four float4 */
+typedef struct { uint64_t n_photons, n_written, n_rays; uint32_t n_launches, n_repeats; } AmberPhotonInfo; /* 32 bytes */
+int amber_hip_lt_trace_photons(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end,
+                               uint32_t surfaces, AmberPhoton* out, uint64_t capacity, AmberPhotonInfo* info /* may be NULL */, uint32_t flags);
 
 const char* amber_hip_last_error(void);
 int         amber_hip_abi_version(void);

@@ -109,6 +109,9 @@ int amber_hip_kat_accumulate(amber_hip_pt*, uint32_t n_samples, const uint32_t* 
 /* Measurement: the first call switches on the timing of that device path with events (every accumulation then waits for the stream); every call
  * returns the milliseconds spent ordering (keys, sorts, gather) and summing since the previous call.  Either pointer may be NULL. */
 int amber_hip_kat_lt_stage_ms(amber_hip_pt*, double* sort_ms, double* sum_ms);
+/* the same for amber_hip_lt_trace_photons: hipEvent milliseconds of its trace kernels, its sorts (keys included) and its gathers since the previous call;
+ * the first call switches the timing on (every launch's gather is then waited for) */
+int amber_hip_kat_photon_stage_ms(amber_hip_pt*, double* trace_ms, double* sort_ms, double* gather_ms);
 /* the engine's sin/cos/pow on device: mode 0 = sincos(x[i]) -> out[2i], out[2i+1] ; mode 1 = pow(x[2i], x[2i+1]) -> out[i] ;
  * mode 2 / 3 = x[i]^4 / x[i]^5 in binary64 -> out[2i], out[2i+1] = low, high word of the double */
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out);
