@@ -212,7 +212,7 @@ LAB_SYMBOLS = [
     "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep", "amber_hip_kat_lt_accumulate", "amber_hip_kat_lt_stage_ms",
     "amber_hip_kat_photon_stage_ms",
     "amber_hip_kat_light_ray", "amber_hip_kat_lens_response", "amber_hip_kat_radiance", "amber_host_kat_scene_lights",
-    "amber_hip_kat_accumulate",
+    "amber_hip_kat_accumulate", "amber_hip_kat_phase_a",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -303,6 +303,8 @@ def load_library() -> C.CDLL:
         if hasattr(lib, "amber_hip_kat_photon_stage_ms"):   # lab build
             lib.amber_hip_kat_photon_stage_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(lib, "amber_hip_kat_cast"):         # the lab build (include/amber_hip_lab.h); the product exports none of these
+        if hasattr(lib, "amber_hip_kat_phase_a"):      # (a library built before it has no such symbol)
+            lib.amber_hip_kat_phase_a.argtypes = [vp, u32, vp, vp, i32, vp, u64, C.POINTER(C.c_uint32)]
         lib.amber_hip_kat_cast.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         lib.amber_hip_kat_sample.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         lib.amber_hip_kat_eye.argtypes = [vp, u32, vp, vp, vp]
@@ -1031,6 +1033,14 @@ class PathTracer:
         _check(load_library().amber_hip_kat_cast(self._h, n, o.ctypes.data, d.ctypes.data, obj.ctypes.data, t.ctypes.data,
                                                  pos.ctypes.data, nrm.ctypes.data))
         return obj, t, pos, nrm
+
+    def kat_phase_a(self, origins, dirs, axis_loops: bool = True):
+        """Lab build: Phase A's candidate masks of the rays, uint32 [n, n_groups] (amber_hip_lab.h); axis_loops False: the general slab loop."""
+        o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
+        n = len(o)
+        out, groups = np.zeros(4 * n, np.uint32), C.c_uint32()
+        _check(load_library().amber_hip_kat_phase_a(self._h, n, o.ctypes.data, d.ctypes.data, int(bool(axis_loops)), out.ctypes.data, out.size, C.byref(groups)))
+        return out[:n * groups.value].reshape(n, groups.value)
 
     def kat_sample(self, material, normals, dirs_out, rng_state, importance: bool = False):
         """SampleLight of material[i], or (importance) SampleImportance, the light-tracing side: bit 31 of the index (amber_hip_lab.h)."""

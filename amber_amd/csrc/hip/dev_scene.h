@@ -97,7 +97,7 @@ struct alignas(16) DevSphereFilter { // 32 B
 // shared record arrays; the closest hit runs group after group (the (t, index) rule makes the order irrelevant).  Group g's objects occupy the
 // LDS slots [32 g, 32 g + n_objects).  Group 0 is described by DevScene's own fields as well (pixel_mask_kernel and the 32-object engine read those).
 struct alignas(16) DevFilterGroup {  // 48 B, scalar-loaded
-  uint32_t plane_first, n_planes, n_simple_planes, tri_first;      // offsets into DevScene.planes / tri_filters (records)
+  uint32_t plane_first, n_planes, slab_ends, tri_first;            // offsets into DevScene.planes / tri_filters (records); slab_ends: as DevScene's, of this group's program
   uint32_t sphere_first, n_sphere_filters, always_mask, n_prog_tris;
   uint32_t n_objects, pad[3];
 };
@@ -175,7 +175,8 @@ struct DevScene {
   const DevTriFilter* __restrict__ tri_filters;
   const DevSphereFilter* __restrict__ sphere_filters;
   uint32_t n_planes, n_sphere_filters;
-  uint32_t n_simple_planes;    // the first planes of the program, an even number: slabs of two parallel planes with one pair record each
+  uint32_t slab_ends;          // the first planes of the program form slabs of two parallel planes with one pair record each: axis slabs of normal +x, +y, +z
+                               // (filter_build.h), then the other slabs.  Byte k = 0, 1, 2: the first plane past the slabs of axis k; byte 3: past all slabs
   uint32_t always_mask;        // program slots that are always candidates (disks, cylinders, degenerate triangles)
   uint32_t blade_mask;         // program slots of the aperture blades (primary rays: decided per ray, not per pixel)
   uint32_t n_prog_tris;        // program slots [0, n_prog_tris) are filtered triangles, then spheres, then the rest

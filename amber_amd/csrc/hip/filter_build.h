@@ -32,7 +32,29 @@ struct FilterProgram {
   std::vector<uint32_t> order;          // program slot -> scene object index
   uint32_t n_prog_tris = 0, always_mask = 0;
   uint32_t n_simple_planes = 0;         // the first planes of the program (an even number) form slabs: two parallel planes of one parallelogram pair each
+  uint32_t n_axis_slabs[3] = {0, 0, 0}; // the first of these slabs are axis slabs (below), per axis x, y, z; they stand in the order AxisSlabOrder(0), (1), (2)
 };
+// The axis of the k-th axis loop of the device (dev_two_phase.h: AMBER_AXIS_FIRST)
+inline int AxisSlabOrder(int k) { return (AMBER_AXIS_FIRST + k) % 3; }
+
+// DevScene::slab_ends / DevFilterGroup::slab_ends of a program (at most 32 objects, so at most 16 slab planes: a byte each)
+inline uint32_t SlabEnds(const FilterProgram& fp) {
+  const uint32_t e0 = 2u * fp.n_axis_slabs[AxisSlabOrder(0)], e1 = e0 + 2u * fp.n_axis_slabs[AxisSlabOrder(1)], e2 = e1 + 2u * fp.n_axis_slabs[AxisSlabOrder(2)];
+  return e0 | e1 << 8 | e2 << 16 | fp.n_simple_planes << 24;
+}
+// The two in-plane axes (u < v) of an axis slab of axis c: row `a` of its pair records depends on P_u alone, row `b` on P_u and P_v.
+inline void AxisSlabInPlane(int c, int& u, int& v) { u = c == 0 ? 1 : 0; v = c == 2 ? 1 : 2; }
+// The axis c of which a plane of ONE pair record is an axis-slab plane, judged on the binary32 values the device reads, or -1: the normal is
+// +-1 in component c and +-0 elsewhere, both rows of the record have a +-0 coefficient for coordinate c, and row `a` has exactly one non-zero
+// gradient coefficient, that of the first in-plane axis.  The device's axis loops leave out exactly these zero terms (dev_two_phase.h).
+inline int AxisSlabClass(const DevPlane& p, const DevTriFilter& f) {
+  for (int c = 0; c < 3; c++) {
+    int u, v; AxisSlabInPlane(c, u, v);
+    if (std::fabs(p.n[c]) == 1.0f && p.n[u] == 0.0f && p.n[v] == 0.0f)
+      return (f.c[c][0] == 0.0f && f.c[c][1] == 0.0f && f.c[u][1] != 0.0f && f.c[v][1] == 0.0f) ? c : -1;
+  }
+  return -1;
+}
 
 // `center`: the filter works in coordinates relative to this point (the device subtracts it from the ray origin), so its
 // affine maps see magnitudes of the order of the scene size however far the scene lies from the world origin; in
@@ -190,6 +212,7 @@ inline void BuildFilterProgram(const std::vector<DevObject>& objs, const float c
     }
     groups.swap(sorted);
   }
+  std::vector<DevTriFilter> other_corner;   // per record of fp.tris: a pair's record with row `a` taken at the OTHER shared corner (a single triangle's: itself)
   for (const Group& g : groups) {
     // Parallelogram pairs: triangle j shares two corners with triangle i and its third corner is D = A + C - B
     // (B = i's unshared corner), everything up to 1e-6 of the scene diameter; the actual mismatch (corners are
@@ -236,12 +259,14 @@ inline void BuildFilterProgram(const std::vector<DevObject>& objs, const float c
       if (partner[i] < 0 || static_cast<size_t>(partner[i]) < i) continue;
       const int bi = unshared[i], ai = (bi + 1) % 3;
       fp.tris.push_back(record(g.tris[i], bi, ai));
+      other_corner.push_back(record(g.tris[i], bi, (bi + 2) % 3));
       fp.order.push_back(g.tris[i].index); fp.order.push_back(g.tris[static_cast<size_t>(partner[i])].index);
       p.n_pairs++;
     }
     for (size_t i = 0; i < nt; i++) {
       if (partner[i] >= 0) continue;
       fp.tris.push_back(record(g.tris[i], 1, 2));                  // u, v = coordinates of v1, v2
+      other_corner.push_back(fp.tris.back());
       fp.order.push_back(g.tris[i].index);
       p.n_tris++;
     }
@@ -254,6 +279,12 @@ inline void BuildFilterProgram(const std::vector<DevObject>& objs, const float c
   // "same normal?" branch (ClosestHitTwoPhase: that code is bound by instruction delivery, and every scalar branch of the
   // nested loops costs about as much as four VALU instructions).  Everything else follows in the general form; "same
   // normal as the previous plane" is re-derived for the new order.
+  // Axis slabs.  A slab both of whose planes are axis-slab planes of axis c (AxisSlabClass) is stored in a reduced form that the device
+  // evaluates without the terms that are zero: the normal as +e_c (a plane of normal -e_c with n and d0 negated: the same plane, and the device
+  // uses only |1 / n.d|, the distance and |n.d|), and row `a` of the pair record at that shared corner whose coordinate depends on the FIRST
+  // in-plane axis (the pair test is symmetric in the two shared corners: both minima are taken over the same three quantities).  The form is
+  // chosen by WHERE a slab stands -- the slabs of one axis, of the next, of the third (AxisSlabOrder), the other slabs, then the general planes -- not by a branch per record; the
+  // records keep their layout, and the general slab loop computes the same values from them (the dropped terms are exact zeros).
   {
     struct Span { size_t rec, slot; };
     std::vector<Span> span(fp.planes.size());
@@ -264,13 +295,31 @@ inline void BuildFilterProgram(const std::vector<DevObject>& objs, const float c
         rec += np + nt; slot += 2 * np + nt;
       } }
     auto simple = [&](size_t i) { return fp.planes[i].n_pairs == 1 && (fp.planes[i].n_tris & 0x7fffffffu) == 0; };
-    std::vector<char> in_slab(fp.planes.size(), 0);
-    for (size_t i = 0; i + 1 < fp.planes.size(); i++)
-      if (!in_slab[i] && simple(i) && simple(i + 1) && std::memcmp(fp.planes[i].n, fp.planes[i + 1].n, sizeof fp.planes[i].n) == 0) { in_slab[i] = in_slab[i + 1] = 1; i++; }
+    enum { kSlabOther = 3, kGeneral = 4 };                          // 0, 1, 2: axis slab of that axis
+    std::vector<int> kind(fp.planes.size(), kGeneral);
+    for (size_t i = 0; i + 1 < fp.planes.size(); i++) {
+      if (!(simple(i) && simple(i + 1) && std::memcmp(fp.planes[i].n, fp.planes[i + 1].n, sizeof fp.planes[i].n) == 0)) continue;
+      int axis[2]; bool other[2];
+      for (size_t k = 0; k < 2; k++) {
+        axis[k] = AxisSlabClass(fp.planes[i + k], fp.tris[span[i + k].rec]);
+        other[k] = axis[k] < 0;                                      // row `a` at the other shared corner?
+        if (other[k]) axis[k] = AxisSlabClass(fp.planes[i + k], other_corner[span[i + k].rec]);
+      }
+      if (axis[0] >= 0 && axis[0] == axis[1]) {
+        for (size_t k = 0; k < 2; k++) {
+          DevPlane& q = fp.planes[i + k];
+          if (other[k]) fp.tris[span[i + k].rec] = other_corner[span[i + k].rec];
+          if (q.n[axis[0]] < 0.0f) q.d0 = -q.d0;
+          for (int c2 = 0; c2 < 3; c2++) q.n[c2] = c2 == axis[0] ? 1.0f : 0.0f;
+        }
+        kind[i] = kind[i + 1] = axis[0];
+      } else kind[i] = kind[i + 1] = kSlabOther;
+      i++;
+    }
     std::vector<DevPlane> planes; std::vector<DevTriFilter> tris; std::vector<uint32_t> order;
-    for (int pass = 0; pass < 2; pass++)
+    for (int pass = 0; pass <= kGeneral; pass++)
       for (size_t i = 0; i < fp.planes.size(); i++) {
-        if ((in_slab[i] != 0) != (pass == 0)) continue;
+        if (kind[i] != (pass < kSlabOther ? AxisSlabOrder(pass) : pass)) continue;
         DevPlane q = fp.planes[i];
         const uint32_t nt = q.n_tris & 0x7fffffffu, np = q.n_pairs;
         q.n_tris = nt;
@@ -278,7 +327,8 @@ inline void BuildFilterProgram(const std::vector<DevObject>& objs, const float c
         planes.push_back(q);
         for (uint32_t k = 0; k < np + nt; k++) tris.push_back(fp.tris[span[i].rec + k]);
         for (uint32_t k = 0; k < 2 * np + nt; k++) order.push_back(fp.order[span[i].slot + k]);
-        if (pass == 0) fp.n_simple_planes++;
+        if (pass < kGeneral) fp.n_simple_planes++;
+        if (pass < kSlabOther && (fp.n_simple_planes & 1u) == 0u) fp.n_axis_slabs[AxisSlabOrder(pass)]++;
       }
     fp.planes.swap(planes); fp.tris.swap(tris); fp.order.swap(order);
   }

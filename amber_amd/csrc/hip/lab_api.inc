@@ -118,6 +118,32 @@ int amber_hip_kat_cast(amber_hip_pt* h, uint32_t n, const float* origins, const 
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_phase_a(amber_hip_pt* h, uint32_t n, const float* origins, const float* dirs, int axis_loops, uint32_t* out_mask, uint64_t mask_capacity, uint32_t* out_n_groups) { return Guarded("amber_hip_kat_phase_a", [&]() -> int {
+  if (!h || !origins || !dirs || !out_mask) return Fail(AMBER_EINVAL, "null argument");
+  if (!h->two_phase) return Fail(AMBER_EINVAL, "amber_hip_kat_phase_a: the handle's engine has no Phase A (two-phase engines only)");
+  const uint32_t n_groups = h->hit_engine == kHitTwoPhaseN ? h->scene.n_groups : 1u;
+  if (out_n_groups) *out_n_groups = n_groups;
+  if (static_cast<uint64_t>(n) * n_groups > mask_capacity) return Fail(AMBER_EINVAL, "amber_hip_kat_phase_a: out_mask holds fewer than n * n_groups words (at most four groups)");
+  if (n == 0) return AMBER_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  DevBuf<float> d_o, d_d; DevBuf<uint32_t> d_m;
+  HIP_TRY(d_o.alloc(3ull * n)); HIP_TRY(d_d.alloc(3ull * n)); HIP_TRY(d_m.alloc(static_cast<size_t>(n) * n_groups));
+  HIP_TRY(hipMemcpy(d_o.p, origins, 12ull * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_d.p, dirs, 12ull * n, hipMemcpyHostToDevice));
+  const dim3 grid((n + 255) / 256), block(256);
+  if (h->hit_engine == kHitTwoPhaseN) {
+    if (axis_loops) hipLaunchKernelGGL((kat_phase_a_kernel<true, true>), grid, block, 0, h->stream, h->scene, n, d_o.p, d_d.p, d_m.p);
+    else hipLaunchKernelGGL((kat_phase_a_kernel<true, false>), grid, block, 0, h->stream, h->scene, n, d_o.p, d_d.p, d_m.p);
+  } else {
+    if (axis_loops) hipLaunchKernelGGL((kat_phase_a_kernel<false, true>), grid, block, 0, h->stream, h->scene, n, d_o.p, d_d.p, d_m.p);
+    else hipLaunchKernelGGL((kat_phase_a_kernel<false, false>), grid, block, 0, h->stream, h->scene, n, d_o.p, d_d.p, d_m.p);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(out_mask, d_m.p, 4ull * n * n_groups, hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
+
 int amber_hip_kat_sample(amber_hip_pt* h, uint32_t n, const uint32_t* material, const float* normals,
                          const float* dirs_out, uint64_t* rng_state, float* out_dir_in, float* out_weight) { return Guarded("amber_hip_kat_sample", [&]() -> int {
   if (!h || !material || !normals || !dirs_out || !rng_state || !out_dir_in || !out_weight) return Fail(AMBER_EINVAL, "null argument");

@@ -30,6 +30,21 @@ __global__ void kat_cast_kernel(const DevScene sc, uint32_t n, const float* org,
   out_n[3 * i] = nrm.x; out_n[3 * i + 1] = nrm.y; out_n[3 * i + 2] = nrm.z;
 }
 
+// Phase A on its own (amber_hip_kat_phase_a): the candidate mask of every ray in every group of the filter program, out[i * n_groups + g], through the
+// function the closest hit calls; kAxis: with the axis-slab loops, or with the general slab loop on the same records.  No exact test runs.
+template <bool kMulti, bool kAxis>
+__global__ void kat_phase_a_kernel(const DevScene sc, uint32_t n, const float* org, const float* dir, uint32_t* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t k = ClampToLastItem(i, n);
+  const V3 o = ld3(org + 3 * k), d = ld3(dir + 3 * k);
+  const uint32_t n_groups = kMulti ? sc.n_groups : 1u;
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    const FilterView fv = g == 0u ? SceneView(sc) : GroupView(sc, static_cast<int>(g));
+    const uint32_t cand = PhaseA<kMulti, kAxis>(sc, fv, o, d, kMulti ? fv.always_mask : sc.always_mask);
+    if (i < n) out[static_cast<size_t>(i) * n_groups + g] = cand;
+  }
+}
+
 __global__ void kat_sample_kernel(const DevScene sc, uint32_t n, const uint32_t* material, const float* normals,
                                   const float* dirs_out, uint64_t* rng_state, float* out_dir, float* out_w) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -432,7 +432,7 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
   if (!more_progs.empty()) {
     auto record = [&](const amber_filter::FilterProgram& fp, size_t plane_first, size_t tri_first, size_t sphere_first) {
       DevFilterGroup g{};
-      g.plane_first = static_cast<uint32_t>(plane_first); g.n_planes = static_cast<uint32_t>(fp.planes.size()); g.n_simple_planes = fp.n_simple_planes;
+      g.plane_first = static_cast<uint32_t>(plane_first); g.n_planes = static_cast<uint32_t>(fp.planes.size()); g.slab_ends = amber_filter::SlabEnds(fp);
       g.tri_first = static_cast<uint32_t>(tri_first); g.sphere_first = static_cast<uint32_t>(sphere_first); g.n_sphere_filters = static_cast<uint32_t>(fp.spheres.size());
       g.always_mask = fp.always_mask; g.n_prog_tris = fp.n_prog_tris; g.n_objects = static_cast<uint32_t>(fp.order.size());
       p.groups.push_back(g);
@@ -453,7 +453,7 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
   p.ref_leaves = std::move(ref_tree.leaves);
 
   DevScene& sc = p.scene;
-  sc.n_planes = static_cast<uint32_t>(fprog.planes.size()); sc.n_simple_planes = fprog.n_simple_planes; sc.n_sphere_filters = static_cast<uint32_t>(fprog.spheres.size());
+  sc.n_planes = static_cast<uint32_t>(fprog.planes.size()); sc.slab_ends = amber_filter::SlabEnds(fprog); sc.n_sphere_filters = static_cast<uint32_t>(fprog.spheres.size());
   if (p.hit_engine == AMBER_ENGINE_REFERENCE_BVH) sc.bvh_root = ref_tree.root;
   for (int c = 0; c < 3; c++) sc.fp_center[c] = fp_center[c];
   sc.fp_reach = fp_reach;

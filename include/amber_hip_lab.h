@@ -23,6 +23,14 @@ extern "C" {
 /* closest hit: out_object = object index or -1 */
 int amber_hip_kat_cast(amber_hip_pt*, uint32_t n, const float* origins /*n*3*/, const float* dirs /*n*3*/,
                        int32_t* out_object, float* out_t, float* out_pos /*n*3*/, float* out_normal /*n*3*/);
+/* Phase A of the two-phase closest hit on its own: the candidate mask of every ray in every group of the handle's filter program (one group for
+ * up to 32 objects, else up to four), out_mask[i * n_groups + g], bit k = program slot k of group g, through the function the render kernels call;
+ * no exact test runs.  axis_loops != 0: the axis slabs run in their reduced form (the product's default); 0: the general slab loop runs the same
+ * records.  The two masks are equal bit for bit.  Phase A does not read a ray's origin slot (the self trip that follows it does), so none is
+ * passed.  mask_capacity: words behind out_mask, at least n * n_groups (4 n always suffices); *out_n_groups (may be null) is set either way.
+ * AMBER_EINVAL for a handle of another engine. */
+int amber_hip_kat_phase_a(amber_hip_pt*, uint32_t n, const float* origins /*n*3*/, const float* dirs /*n*3*/, int axis_loops,
+                          uint32_t* out_mask, uint64_t mask_capacity, uint32_t* out_n_groups);
 /* material sampling with a per-item XorShift state; returns dir_in, weight and the advanced state.
  * material[i]: the material index, | 0x80000000 for SampleImportance (the light-tracing side) instead of SampleLight */
 int amber_hip_kat_sample(amber_hip_pt*, uint32_t n, const uint32_t* material /*n*/, const float* normals,
