@@ -179,6 +179,7 @@ ENGINE_AUTO, ENGINE_LIST, ENGINE_TWO_PHASE, ENGINE_BVH, ENGINE_WAVEFRONT = 0, 1,
 ENGINE_REFERENCE_BVH = 6     # the reference's own tree and traversal order: every ray gets the hit the reference's BVH gives it (include/amber_hip.h)
 PT_FLAG_NULL_STREAM, PT_FLAG_BVH_POOL, PT_FLAG_BVH_ITEMS = 1, 2, 4
 PT_FLAG_DEVICE_BUILD = 8     # engine BVH: create builds the tree on the device (include/amber_hip.h)
+PT_FLAG_NO_SCOUT = 16        # the 32-object two-phase engine: every path carries its weight (no scout + replay); same bits (include/amber_hip.h)
 BUILD_NONE, BUILD_HOST, BUILD_DEVICE, BUILD_HOST_FALLBACK = 0, 1, 2, 3
 BUILD_REASON_NONE, BUILD_REASON_DEPTH, BUILD_REASON_WIDE, BUILD_REASON_BOUNDS = 0, 1, 2, 3
 RAYS_HOST = 1                # amber_hip_pt_cast_rays / amber_hip_pt_occluded: rays and output are host pointers
@@ -212,7 +213,7 @@ LAB_SYMBOLS = [
     "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep", "amber_hip_kat_lt_accumulate", "amber_hip_kat_lt_stage_ms",
     "amber_hip_kat_photon_stage_ms",
     "amber_hip_kat_light_ray", "amber_hip_kat_lens_response", "amber_hip_kat_radiance", "amber_host_kat_scene_lights",
-    "amber_hip_kat_accumulate", "amber_hip_kat_phase_a",
+    "amber_hip_kat_accumulate", "amber_hip_kat_phase_a", "amber_hip_kat_scout_flags",
 ]
 PRODUCT_LIB, LAB_LIB = "libamber_hip.so", "libamber_hip_lab.so"
 
@@ -328,6 +329,8 @@ def load_library() -> C.CDLL:
             lib.amber_hip_kat_lens_response.argtypes = [vp, u32, vp, vp, vp, vp, vp]
             lib.amber_hip_kat_radiance.argtypes = [vp, u32, vp, vp, vp, vp]
             lib.amber_host_kat_scene_lights.argtypes = [vp, C.POINTER(FlatLight), C.POINTER(u32)]
+        if hasattr(lib, "amber_hip_kat_scout_flags"):      # (a measurement build of an older tree may lack it)
+            lib.amber_hip_kat_scout_flags.argtypes = [vp, u32, u32, vp, u64, C.POINTER(u32), C.POINTER(u32)]
         if hasattr(lib, "amber_hip_kat_accumulate"):       # the same
             lib.amber_hip_kat_accumulate.argtypes = [vp, u32, vp, vp, u32, u32, u32, u64, C.POINTER(AccumulateInfo)]
     lib.amber_host_cornell_box.restype = vp
@@ -1018,6 +1021,16 @@ class PathTracer:
         _check(load_library().amber_hip_kat_accumulate(self._h, n_samples, qq.ctypes.data if len(qq) else None, cc.ctypes.data if len(qq) else None,
                                                        len(qq), n_waves, rec_capacity, rays, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in AccumulateInfo._fields_}
+
+    def kat_scout_flags(self, first_sample: int, n_samples: int):
+        """Lab build: (flagged, scouts) -- a bool per path q = band pixel * n_samples + sample offset of one launch: the scout flagged it (it ends on a
+        light, or it is suspect), taken after the scout and before the replay; scouts False: the handle renders with the full kernel, nothing is flagged."""
+        n_paths = len(self.row_index) * self.sensor.width * n_samples
+        words = np.zeros((n_paths + 31) // 32 + 1, np.uint32)
+        scouts, bound0 = C.c_uint32(), C.c_uint32()
+        _check(load_library().amber_hip_kat_scout_flags(self._h, first_sample, n_samples, words.ctypes.data, len(words), C.byref(scouts), C.byref(bound0)))
+        self.scout_bound0 = int(bound0.value)           # the host's bound of log2 |eye weight|, sixteenths of a bit (scout_bound.h)
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n_paths].astype(bool), bool(scouts.value)
 
     def kat_lt_stage_ms(self):
         """Lab build: (sort ms, sum ms) of lt_render_pass's device path since the previous call; the first call switches the timing on."""

@@ -226,7 +226,11 @@ __device__ __forceinline__ bool LensResponse(const DevScene& sc, V3 position, V3
 // near_edge (optional): the aperture sample lies within DevLens.edge_tol (barycentric) of its blade's boundary -- only then can the exact
 // test of ANOTHER blade accept the ray's own origin (pt_megakernel's primary rounds: which blades are candidates).
 struct EyeRayScene { const DevLens* lens; const DevBlade* blades; DevSensor sensor; };
-template <bool kSharedDiv = false, int kSqrt = SQRT_PLAIN, typename Scene>
+// kScout (pt_megakernel's weight-free instantiation, scout_bound.h): the ray is formed by the same operations in the same order, its weight is not --
+// neither factor, dloc and pdf_dir of the thin lens nor the pinhole's PDF arithmetic.  `weight` receives the guard quantity of scout_bound.h instead, what the
+// host's bound of the weight cannot know of a single ray: direction.z (thin lens; NaN if the ray is not sound) or the local z of the ray (pinhole), which the
+// caller holds against amber_scout::kMinZ.
+template <bool kSharedDiv = false, int kSqrt = SQRT_PLAIN, bool kScout = false, typename Scene>
 __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uint32_t py, uint64_t& rng,
                                                V3& origin, V3& dir, float& weight, int& origin_slot, bool* near_edge = nullptr) {
   const DevLens L = LoadLens(sc.lens);
@@ -237,13 +241,17 @@ __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uin
     const float uvy = (static_cast<float>(py) + jy) / sc.sensor.hf;
     const V3 sensor_point = v3((uvx - 0.5f) * sc.sensor.sw, (uvy - 0.5f) * sc.sensor.sh, L.sensor_distance);
     const V3 ray_dir = Normalize<kSharedDiv, kSqrt>(MatMul(L.global_, -sensor_point));
-    // PDFDirection lens_pinhole.cc:93-106 (binary32 throughout; no sensor.Size() factor, unlike the thin lens)
-    const V3 dl = MatMul(L.local_, ray_dir);
-    const V3 point = (L.sensor_distance / dl.z) * dl;
-    const float geometry_factor = dl.z * dl.z / SquaredLength(point);
-    const float pdf_dir = L.inv_scene_area / geometry_factor;
     origin = ld3(L.origin); dir = ray_dir;
-    weight = 1.0f / 1.0f / pdf_dir;                        // 1 / PDFArea (= kDiracDelta) / PDFDirection
+    if (kScout) {
+      weight = L.local_[6] * ray_dir.x + L.local_[7] * ray_dir.y + L.local_[8] * ray_dir.z;     // dl.z below
+    } else {
+      // PDFDirection lens_pinhole.cc:93-106 (binary32 throughout; no sensor.Size() factor, unlike the thin lens)
+      const V3 dl = MatMul(L.local_, ray_dir);
+      const V3 point = (L.sensor_distance / dl.z) * dl;
+      const float geometry_factor = dl.z * dl.z / SquaredLength(point);
+      const float pdf_dir = L.inv_scene_area / geometry_factor;
+      weight = 1.0f / 1.0f / pdf_dir;                        // 1 / PDFArea (= kDiracDelta) / PDFDirection
+    }
     origin_slot = -1;
     if (near_edge) *near_edge = true;                      // (the pinhole's degenerate blade: keep every blade bit)
     return;
@@ -264,6 +272,14 @@ __device__ __forceinline__ void GenerateEyeRay(const Scene& sc, uint32_t px, uin
   const float uvy = (static_cast<float>(py) + jy) / sc.sensor.hf;
   const V3 sensor_point = v3((uvx - 0.5f) * sc.sensor.sw, (uvy - 0.5f) * sc.sensor.sh, L.sensor_distance);
   const V3 direction = Normalize<kSharedDiv, kSqrt>(L.neg_fd_over_sd * sensor_point - aperture_point);
+  if (kScout) {
+    origin = ap_origin; dir = Normalize<kSharedDiv, kSqrt>(MatMul(L.global_, direction));
+    origin_slot = bl->slot;
+    // (what the bound assumes of this ray beyond its constants: a finite direction, and a sensor point that does not coincide with the aperture point)
+    const bool sound = IsFinite(direction.x) && IsFinite(direction.y) && Abs(L.sensor_distance - aperture_point.z) >= amber_scout::kMinGap;
+    weight = sound ? direction.z : __builtin_nanf("");
+    return;
+  }
   const double factor = Pow4(Normalize<false, kSqrt>(sensor_point - aperture_point).z / direction.z);      // one component: the plain form divides once
   const V3 ray_dir = Normalize<kSharedDiv, kSqrt>(MatMul(L.global_, direction));
   const V3 dloc = MatMul(L.local_, ray_dir);
@@ -288,7 +304,10 @@ struct SplatSink { DevSplat* records; unsigned int* count; uint32_t capacity; ui
 // amber_hip_lt_render_pass).  SINK_PHOTONS: the vertex of every hit on a surface whose kind sink->surfaces selects (amber_hip_lt_trace_photons,
 // PhotonMap::Build photon_map.h:108-153) -- (position, -ray.Direction(), weight on arrival), recorded before the material is sampled, four float4
 // at photons[4 * slot] in AmberPhoton's layout; no splat.  The sink handed over is then a PhotonSink, `count` and `capacity` the photon buffer's.
-enum { SINK_SPLATS = 0, SINK_PHOTONS = 1 };
+// SINK_SCOUT (eye paths, kLight = false; pt_megakernel's AMBER_KERNEL_SCOUT instantiation): the bounce without the path weight.  `weight` is not touched and
+// nothing is accumulated: `measurement` receives the hit's emitted radiance itself (anything but (+0, +0, +0) only on a light seen from its front, which ends the
+// path), *scout_bound the bound of scout_bound.h in place of the weight update.  Every draw, every test and everything a later bounce reads are as without it.
+enum { SINK_SPLATS = 0, SINK_PHOTONS = 1, SINK_SCOUT = 2 };
 struct PhotonSink : SplatSink { float4* photons; uint32_t surfaces; };
 // AMBER_PHOTON_CLAIM_PER_LANE=1 (measurement builds, EXPERIMENTS.md): every recording lane claims its slot with an atomic of its own.
 #ifndef AMBER_PHOTON_CLAIM_PER_LANE
@@ -297,21 +316,22 @@ struct PhotonSink : SplatSink { float4* photons; uint32_t surfaces; };
 
 template <bool kTrace, int kEngine, bool kLight, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u, int kSink = SINK_SPLATS>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
-                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink);
+                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink, uint32_t* scout_bound = nullptr);
 
 template <bool kTrace, int kEngine, bool kLight = false, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u, int kSink = SINK_SPLATS>
 __device__ __forceinline__ bool PathStep(const DevScene& sc, const DevObject* lds_objects, int32_t* lds_stack, V3& o, V3& d, V3& weight, V3& measurement,
                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink = nullptr,
-                                         const bool use_premask = false, const uint32_t premask = 0u, const int bvh_stack_cap = AMBER_BVH_STACK) {
+                                         const bool use_premask = false, const uint32_t premask = 0u, const int bvh_stack_cap = AMBER_BVH_STACK, uint32_t* scout_bound = nullptr) {
   HitRec h;
   ClosestHit<kEngine, (kSqrtMask & 8u) ? SQRT_EXACT : SQRT_PLAIN>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG, use_premask, premask, bvh_stack_cap);
-  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit, kSqrtMask, kSink>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink);
+  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit, kSqrtMask, kSink>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink, scout_bound);
 }
 
 // Everything of a bounce after the closest-hit query (algorithm_pt.cc:140-157): h is the result of Scene::Cast.
 template <bool kTrace, int kEngine, bool kLight, bool kDivBasis, bool kDivHit, uint32_t kSqrtMask, int kSink>
 __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
-                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* splat_sink) {
+                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* splat_sink, uint32_t* scout_bound) {
+  constexpr bool kScout = !kLight && kSink == SINK_SCOUT;
   casts++;
   if (h.idx < 0) {
     if (kTrace) { trace->object = -1; trace->t = __builtin_nanf(""); trace->pos = v3(0, 0, 0); trace->weight_before = v3(0, 0, 0); }
@@ -367,7 +387,8 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
     AMBER_STAMP(4);
     SampleImportance(m, normal, dir_out, rng, dir_in, sw);
   } else {
-    measurement = measurement + weight * Radiance(m, normal, dir_out);      // algorithm_pt.cc:144
+    if (kScout) measurement = Radiance(m, normal, dir_out);
+    else measurement = measurement + weight * Radiance(m, normal, dir_out);      // algorithm_pt.cc:144
     AMBER_STAMP(4);
     SampleLight<kDivBasis, kSqrtMask>(m, normal, dir_out, rng, dir_in, sw);             // :145-146
   }
@@ -380,6 +401,10 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
   o = pos; d = dir_in;                                                       // :155 Ray(pos, UnitVector3) -- no renormalisation
   if (kEngine == ENGINE_TWO_PHASE_N) origin_slot = (lds_objects[h.slot].kind & 0x80u) ? h.slot : -1;      // a filtered triangle of its group (bit 7 of the LDS record)
   else origin_slot = (kEngine == ENGINE_TWO_PHASE && static_cast<uint32_t>(h.slot) < sc.n_prog_tris) ? h.slot : -1;
+  if (kScout) {                                                              // :156 without the quotients and the products: what they can have grown to
+    *scout_bound = amber_scout::BounceBound(*scout_bound, __float_as_uint(sw.x), __float_as_uint(sw.y), __float_as_uint(sw.z), __float_as_uint(p_rr));
+    return true;
+  }
 #if AMBER_SHARED_WEIGHT_QUOTIENT
   {
     // :156  weight *= scatter.Weight() / p -- three binary32 divisions by the same p.  A component of the scatter weight that has the

@@ -468,6 +468,25 @@ int amber_hip_kat_accumulate(amber_hip_pt* h, uint32_t n_samples, const uint32_t
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_scout_flags(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t* out_flags, uint64_t n_words, uint32_t* out_scouts, uint32_t* out_bound0) {
+  return Guarded("amber_hip_kat_scout_flags", [&]() -> int {
+  if (!h || !out_flags) return Fail(AMBER_EINVAL, "null argument");
+  if (out_scouts) *out_scouts = h->scout ? 1u : 0u;
+  if (out_bound0) *out_bound0 = h->scout_bound0;
+  const uint64_t n_paths = BandPixels(h) * n_samples, need_words = (n_paths + 31u) / 32u;
+  if (n_samples == 0 || n_paths > kMaxPathsPerLaunch || static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "amber_hip_kat_scout_flags: no samples, or more paths than one launch takes");
+  if (n_words < need_words) return Fail(AMBER_EINVAL, "amber_hip_kat_scout_flags: the bitmap of this launch has " + std::to_string(need_words) + " words");
+  std::memset(out_flags, 0, n_words * sizeof(uint32_t));
+  if (!h->scout || n_paths == 0) return AMBER_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  AMBER_TRY(ResolvePending(h));
+  AMBER_TRY(EnsureRecordCapacity(h, n_paths + RecordSlack(h)));            // a slot for every path: the scout's records are not looked at, but none is written out of bounds either way
+  AMBER_TRY(LaunchPaths(h, first_sample, n_samples, static_cast<uint32_t>(BandPixels(h)), nullptr, nullptr, true));
+  HIP_TRY(hipMemcpyAsync(out_flags, h->paths.flags, need_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return AMBER_OK;
+}); }
+
 int amber_hip_kat_lt_stage_ms(amber_hip_pt* h, double* sort_ms, double* sum_ms) { return Guarded("amber_hip_kat_lt_stage_ms", [&]() -> int {
   if (!h) return Fail(AMBER_EINVAL, "null handle");
   h->lt.stage_timing = true;

@@ -10,6 +10,9 @@ struct RenderArgs {
   uint4* records;            // ... appended as {q, r, g, b}; q = 0xffffffff marks a reserved slot that was never used
   unsigned int* rec_count;   // slots handed out so far (waves reserve AMBER_REC_BLOCK at a time)
   uint32_t rec_capacity;     // slots of `records`; a launch that needs more is repeated by the host with a larger buffer
+  uint32_t scout_bound0;     // pt_megakernel's scout: the host's bound of log2 |eye weight| for this lens, sixteenths of a bit (scout_bound.h).  It fills the four
+                             // bytes of padding in front of the next pointer: no offset moves and the record keeps its size, so the instantiations that were there
+                             // before it read their cold arguments where they did
   unsigned long long* ray_count;
   unsigned int* next_item;   // work-queue head (zeroed before every launch)
   unsigned long long* stamps; // diagnostic build only (AMBER_STAMPS): 8 section sums
@@ -42,6 +45,8 @@ struct RenderArgs {
   }
   void SetSamples(uint32_t first_sample_, uint32_t n_samples_) { first_sample = first_sample_; n_samples = n_samples_; div_samples = MakeExactDiv(n_samples_); }
 };
+
+static_assert(offsetof(RenderArgs, scout_bound0) + 4 == offsetof(RenderArgs, ray_count), "scout_bound0 sits in what was padding");
 
 // What a bounce of a light path is handed for its records: the splat sink, or (kPhotons) the vertex sink of amber_hip_lt_trace_photons over the same
 // three arguments

@@ -34,4 +34,5 @@
 #include "dev_two_phase.h"
 #include "dev_bvh.h"
 #include "dev_closest_hit.h"
+#include "scout_bound.h"
 #include "dev_shading.h"

@@ -40,6 +40,8 @@
 //                          permutation sorted by (pixel, pass, path, bounce) with two stable radix sorts, then one thread per pixel run.
 //   lt_photons.inc         amber_hip_lt_trace_photons: the vertex records of a light-tracing launch (PathShade's second sink) into the caller's buffer in
 //                          (sample, path, bounce) order -- two stable radix sorts of an index permutation, one gather of the 64-byte records.
+//   pt_replay.inc          replay_records_kernel: the paths a scouted launch flagged (pt_megakernel's AMBER_KERNEL_SCOUT instantiation), traced again with
+//                          their weights, one lane per record; scout_bound.h: the rule that flags them and the host's bound of the eye weight.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
@@ -86,6 +88,7 @@ namespace {
 #include "pt_args.h"
 #include "pt_megakernel.inc"
 #include "pt_records.inc"
+#include "pt_replay.inc"
 #include "pt_bvh_megakernel.inc"
 #ifdef AMBER_LAB
 #include "bvh_pool.inc"
@@ -296,6 +299,8 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   // pixel_mask_kernel is enqueued on the render stream by create (0.07 ms since the masks are per 4 x 4 block of pixels: it no longer pays to
   // overlap it -- a second stream costs a millisecond of host time to create, more than the kernel it would hide)
   bool pixel_mask_ready = false;            // the kernel has been enqueued in front of everything that reads d_pixel_mask
+  bool scout = false;                       // path launches run the weight-free scout + replay_records_kernel (DecideScout); false: the full kernel
+  uint32_t scout_bound0 = 0;                // ... and the bound of this lens's eye weight that the scout starts every path with (scout_bound.h)
   int n_cus = 256;
   uint32_t row_begin = 0, row_end = 0, stripe_rows = 0, stripe_period = 0, local_rows = 0;
   uint64_t seed = 0, hashed_seed = 0;
@@ -421,6 +426,9 @@ int Create(const AmberFlatScene* s, const AmberSensor* sensor, const AmberPtPara
   DevScene& sc = h->scene;
   HIP_TRY(UploadTo(h->objects_buf, p.objects, 0, sc.objects));
   h->create_flags = params->reserved;
+#if AMBER_SCOUT
+  h->scout = amber_prep::DecideScout(h->engine, h->hit_engine, params->reserved, h->lens, p.blades, p.materials, sensor->scene_width, sensor->scene_height, &h->scout_bound0);
+#endif
   h->n_triangles = amber_prep::CountTriangles(p.objects);
   for (size_t i = 0; i < p.objects.size(); i++) {
     h->has_spheres = h->has_spheres || (p.objects[i].kind & 0xffu) == AMBER_PRIM_SPHERE;

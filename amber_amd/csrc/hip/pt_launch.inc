@@ -204,6 +204,20 @@ int LaunchPathKernel(const amber_hip_pt* h, bool pool, uint32_t n_blocks, const 
   });
 }
 
+// A scouted launch (the handle's choice, amber_prep::DecideScout): pt_megakernel's weight-free instantiation leaves a placeholder record for every path that
+// ends on a light or is suspect, replay_records_kernel traces those again with their weights and overwrites the placeholders (pt_replay.inc) -- the record
+// buffer then holds what the full kernel would have written, plus +0 terms.  Stream order is all that joins the two; `replay` false: the scout alone
+// (amber_hip_kat_scout_flags reads its bitmap).
+int LaunchScoutedPaths(const amber_hip_pt* h, uint32_t n_blocks, const RenderArgs& a, bool replay) {
+#if AMBER_SCOUT
+  hipLaunchKernelGGL((pt_megakernel<ENGINE_TWO_PHASE | AMBER_KERNEL_SCOUT>), dim3(n_blocks), dim3(256), 0, h->stream, a);
+  if (replay) hipLaunchKernelGGL((replay_records_kernel<ENGINE_TWO_PHASE>), dim3(static_cast<uint32_t>(h->n_cus) * 8u), dim3(256), 0, h->stream, a);
+  return AMBER_OK;
+#else
+  return Fail(AMBER_EINVAL, "this build has no scout (AMBER_SCOUT=0)");
+#endif
+}
+
 // A path launch in three parts, so that the reduction serves whatever produced the records: BeginPathLaunch (buffers, counters and bitmap ready),
 // the producer's kernel, FinishPathLaunch (rank / scan / place / reduce, the launch becomes the pending one).
 
@@ -261,8 +275,9 @@ int FinishPathLaunch(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pix
 }
 
 // Enqueues one launch over samples [first, first + n) of the band, its sums added to `target`.  `sig` != nullptr: the signature variant of the same
-// kernel; nothing is reduced (amber_hip_pt_signatures).
-int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, float* target, unsigned long long* sig) {
+// kernel; nothing is reduced (amber_hip_pt_signatures).  `scout_only` (amber_hip_kat_scout_flags): the scout of a scouting handle without its replay; nothing is
+// reduced either, the bitmap stays as the scout left it.
+int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, float* target, unsigned long long* sig, bool scout_only = false) {
   PathLaunchBufs& p = h->paths;
   const uint64_t n_paths = static_cast<uint64_t>(n_pixels) * n;
 #ifdef AMBER_LAB
@@ -284,19 +299,21 @@ int LaunchPaths(amber_hip_pt* h, uint32_t first, uint32_t n, uint32_t n_pixels, 
 #ifdef AMBER_LAB
   if (bvh) AMBER_TRY(Grow(h, h->d_bvh_stack, static_cast<size_t>(h->n_cus) * AMBER_BVH_POOL_WGS * 256u * AMBER_BVH_POOL_GLOBAL_LEVELS, "traversal stacks"));
 #endif
-  AMBER_TRY(BeginPathLaunch(h, n, n_pixels, sig != nullptr));
+  AMBER_TRY(BeginPathLaunch(h, n, n_pixels, sig != nullptr || scout_only));
   RenderArgs a = MakeRenderArgs(h, h->hashed_seed, n_pixels, first, n);
+  a.scout_bound0 = h->scout_bound0;
   a.pixel_mask = h->pixel_mask_ready ? h->d_pixel_mask : nullptr;
   SetRecordArgs(h, a);
   a.stamps = h->d_stamps;
   a.bvh_stack = h->d_bvh_stack; a.carried = p.carried; a.sig = sig; a.n_items = static_cast<uint32_t>(n_paths);
-  AMBER_TRY(TimedLaunch(h, true, [&]() -> int {
+  AMBER_TRY(TimedLaunch(h, !scout_only, [&]() -> int {                    // (the lab's look at the scout's flags is not a render launch: kernel_time() does not count it)
 #ifdef AMBER_LAB
     if (sig) return LaunchPathKernel<true>(h, bvh, n_blocks, a);
 #endif
+    if (h->scout) return LaunchScoutedPaths(h, n_blocks, a, !scout_only);
     return LaunchPathKernel<false>(h, bvh, n_blocks, a);
   }));
-  if (sig) return AMBER_OK;
+  if (sig || scout_only) return AMBER_OK;
   return FinishPathLaunch(h, first, n, n_pixels, target, RecordProducer{}, n_paths + RecordSlack(h) <= p.rec_capacity);   // a slot for every path: cannot run out
 }
 

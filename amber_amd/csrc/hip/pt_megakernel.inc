@@ -41,8 +41,8 @@
 #define AMBER_CLAIM_PATHS 1024u
 #endif
 // Pool slot: the whole state of a path between two bounces in four 16-byte chunks {o.xyz d.x} {d.yz w.xy} {w.z rng q}
-// {casts | carried-flag, origin slot, signature hashes}.
-template <bool kLight> struct PoolLayout { static constexpr int kChunks = 4; };
+// {casts | carried-flag, origin slot, signature hashes}.  kScout: three chunks {o.xyz d.x} {d.yz rng} {q casts origin-slot bound} -- no weight, nothing carried.
+template <bool kLight, bool kScout = false> struct PoolLayout { static constexpr int kChunks = kScout ? 3 : 4; };
 
 // Traversal-stack entries of pt_megakernel<ENGINE_BVH> (a deeper tree renders with pt_bvh_megakernel): 12 KB of LDS next to the 16-KB
 // pool, five workgroups per CU (16 entries: four).  Where the two schedulers cross over (tools/mesh_workloads.py, 1024^2 @ 256 spp, a room
@@ -54,15 +54,29 @@ template <bool kLight> struct PoolLayout { static constexpr int kChunks = 4; };
 // The vertex sink is selected by a bit of the engine argument, not by a fourth parameter: the symbols of the instantiations that exist are what tests
 // and tools find the headline kernel's ISA by, and a parameter more, defaulted or not, renames every one of them.
 #define AMBER_KERNEL_PHOTONS 0x100
+// AMBER_KERNEL_SCOUT, another bit of the engine argument for the same reason: THE SCOUT, the eye-path loop without the path weight.  A path's weight reaches the
+// image only through measurement += weight * Radiance, which is not +0 only where the path ends on a light (2e-5 of the Cornell paths) or after a weight has
+// become inf or NaN; Russian roulette reads the scatter weight, never the accumulated one.  So the scout traces every path with the same rays, draws and tests
+// but forms no eye weight (GenerateEyeRay<.., kScout>), no weight quotients and products (PathShade, SINK_SCOUT) and carries neither the weight nor a
+// measurement (three pool chunks); in the weight's place a lane keeps an integer bound of what the weight can have grown to (scout_bound.h).  A path that ends
+// on a light whose Radiance is not (+0, +0, +0), or whose bound says a weight may have overflowed (`suspect`), leaves a placeholder record {q, 0, 0, 0};
+// replay_records_kernel (pt_replay.inc) then traces exactly those paths again with the full bounce and overwrites the placeholders.  Instantiated for
+// ENGINE_TWO_PHASE eye paths without signatures; -DAMBER_SCOUT=0 compiles the feature out (A/B builds), AMBER_PT_FLAG_NO_SCOUT selects the full kernel per handle.
+#define AMBER_KERNEL_SCOUT 0x200
+#ifndef AMBER_SCOUT
+#define AMBER_SCOUT 1
+#endif
 template <int kEngineSink, bool kLight = false, bool kSig = false>
-__global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == ENGINE_BVH ? 5 : AMBER_MEGAKERNEL_WAVES_PER_SIMD) pt_megakernel(const RenderArgs a) {
-  constexpr int kEngine = kEngineSink & ~AMBER_KERNEL_PHOTONS;
+__global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | AMBER_KERNEL_SCOUT)) == ENGINE_BVH ? 5 : AMBER_MEGAKERNEL_WAVES_PER_SIMD) pt_megakernel(const RenderArgs a) {
+  constexpr int kEngine = kEngineSink & ~(AMBER_KERNEL_PHOTONS | AMBER_KERNEL_SCOUT);
   constexpr bool kPhotons = (kEngineSink & AMBER_KERNEL_PHOTONS) != 0;
+  constexpr bool kScout = (kEngineSink & AMBER_KERNEL_SCOUT) != 0;
   static_assert(kLight || !kPhotons, "vertices are recorded along light paths");
+  static_assert(!kScout || (kEngine == ENGINE_TWO_PHASE && !kLight && !kSig), "the scout is the headline kernel's loop");
   const DevScene& sc = a.scene;
   const uint32_t lane = threadIdx.x & 63u;
   constexpr bool kTwoPhase = EngineTraits<kEngine>::kTwoPhase;
-  constexpr int kChunks = PoolLayout<kLight>::kChunks;
+  constexpr int kChunks = PoolLayout<kLight, kScout>::kChunks;
   constexpr bool kCold = !kLight && kEngine != ENGINE_BVH;    // cold kernel arguments are read next to their use (AMBER_ARG below)
   // a cold argument, read next to its use (pt_args.h).  Two families keep the plain form: the light tracer (its bounces read n_samples and
   // first_sample themselves, and with these reads the kernel reserved scratch) and engine BVH's one-shot traversal (measured: Cornell through
@@ -111,6 +125,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == 
   V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f), w = v3(0.f, 0.f, 0.f);
   uint64_t rng = 1;
   uint32_t casts = 0;
+  uint32_t scout_bound = 0;                  // kScout: scout_bound.h's bound of log2 |weight|, sixteenths of a bit; above kLimit: `suspect`
   uint32_t rays_wave = 0;                    // wave-uniform (SGPR): rays cast by this wave
   int origin_slot = -1;                      // filter-program slot of the triangle the current ray starts on
   uint32_t sig_obj = 2166136261u, sig_t = 2166136261u;   // kSig only
@@ -132,7 +147,17 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == 
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
       // (1) the parked rays first
       const uint32_t take = pool_count < n_need ? pool_count : n_need;
-      if (need && rank < take) {                              // pop
+      if (kScout) {
+        if (need && rank < take) {                            // pop
+          const uint32_t sl = pool_count - 1u - rank;
+          const uint4 c0 = pool[sl * kChunks + 0], c1 = pool[sl * kChunks + 1], c2 = pool[sl * kChunks + 2];
+          o = v3(__uint_as_float(c0.x), __uint_as_float(c0.y), __uint_as_float(c0.z));
+          d = v3(__uint_as_float(c0.w), __uint_as_float(c1.x), __uint_as_float(c1.y));
+          rng = static_cast<uint64_t>(c1.z) | (static_cast<uint64_t>(c1.w) << 32);
+          q = c2.x; casts = c2.y; origin_slot = static_cast<int>(c2.z); scout_bound = c2.w;
+          alive = true;
+        }
+      } else if (need && rank < take) {                       // pop
         const uint32_t sl = pool_count - 1u - rank;
         const uint4 c0 = pool[sl * kChunks + 0], c1 = pool[sl * kChunks + 1], c2 = pool[sl * kChunks + 2], c3 = pool[sl * kChunks + 3];
         o = v3(__uint_as_float(c0.x), __uint_as_float(c0.y), __uint_as_float(c0.z));
@@ -171,7 +196,14 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == 
           const uint32_t gbase = claim_next;
           claim_next += n_new;
           const unsigned long long m_alive = __ballot(alive);
-          if (alive) {                                        // park (pool_count is 0 here)
+          if (kScout) {
+            if (alive) {                                      // park (pool_count is 0 here)
+              const uint32_t sl = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m_alive >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m_alive), 0u));
+              pool[sl * kChunks + 0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
+              pool[sl * kChunks + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), static_cast<uint32_t>(rng), static_cast<uint32_t>(rng >> 32));
+              pool[sl * kChunks + 2] = make_uint4(q, casts, static_cast<uint32_t>(origin_slot), scout_bound);
+            }
+          } else if (alive) {                                 // park (pool_count is 0 here)
             const uint32_t sl = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m_alive >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m_alive), 0u));
             pool[sl * kChunks + 0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
             pool[sl * kChunks + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(w.x), __float_as_uint(w.y));
@@ -205,8 +237,10 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == 
               rng = XorShiftSeed(AMBER_ARG(cold, hashed_seed), px + py * eye.sensor.w, sample);   // Image index x + y*W (image.h:116-124)
               float ew;
               bool near_edge = false;
-              GenerateEyeRay<kDivEye, SqrtModeOf(kSqrtMask, 4u)>(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
-              w = v3(ew, ew, ew);                             // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
+              GenerateEyeRay<kDivEye, SqrtModeOf(kSqrtMask, 4u), kScout>(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
+              if (kScout) {                                   // ew: the guard quantity, not a weight; NaN fails the guard
+                scout_bound = (Abs(ew) >= amber_scout::kMinZ && Abs(ew) < __builtin_inff()) ? AMBER_ARG(cold, scout_bound0) : amber_scout::kSuspect;
+              } else w = v3(ew, ew, ew);                      // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
               // (the pointer is read here and once more below, not held across the bookkeeping above: the two scalar registers it would occupy
               //  there are what the dividers need, and the loop has none to spare -- tests/test_headline_kernel_spills.py)
               const uint32_t* const pixel_mask = kTwoPhase ? AMBER_ARG(cold, pixel_mask) : nullptr;
@@ -232,7 +266,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == 
     bool emit = false;
     V3 meas = v3(0.f, 0.f, 0.f);
     if (alive) {
-      if (!kLight && carries) meas = ld3(AMBER_CARRIED());
+      if (!kLight && !kScout && carries) meas = ld3(AMBER_CARRIED());
       if (kLight) {
         const uint32_t plocal = Quotient(a.div_samples, q);
         const typename std::conditional<kPhotons, PhotonSink, SplatSink>::type sink = MakeLightSink<kPhotons>(a, a.path_offset + plocal, a.first_sample + (q - plocal * a.n_samples));
@@ -243,10 +277,15 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~AMBER_KERNEL_PHOTONS) == 
         sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
         if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
         if (!alive) AMBER_ARG(AMBER_COLD_OPEN(), sig)[q] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
+      } else if (kScout) {
+        alive = PathStep<false, kEngine, false, kDivBasis, kDivHit, kSqrtMask, SINK_SCOUT>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK, &scout_bound);
+        // meas: the last hit's own Radiance.  The placeholder is what the record holds until the replay has traced the path with its weight
+        emit = !alive && (((__float_as_uint(meas.x) | __float_as_uint(meas.y) | __float_as_uint(meas.z)) != 0u) || scout_bound > amber_scout::kLimit);
+        meas = v3(0.f, 0.f, 0.f);
       } else {
         alive = PathStep<false, kEngine, false, kDivBasis, kDivHit, kSqrtMask>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
       }
-      if (!kLight) {
+      if (!kLight && !kScout) {
         const bool nz = (__float_as_uint(meas.x) | __float_as_uint(meas.y) | __float_as_uint(meas.z)) != 0u;   // anything but +0 (RGB)
         emit = !alive && nz;
         if (alive && nz) { float* c = AMBER_CARRIED(); c[0] = meas.x; c[1] = meas.y; c[2] = meas.z; carries = true; }

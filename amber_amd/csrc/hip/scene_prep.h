@@ -17,6 +17,7 @@
 #include "bvh_build.h"
 #include "filter_build.h"
 #include "ref_bvh_build.h"
+#include "scout_bound.h"
 
 namespace amber_prep {
 
@@ -199,6 +200,27 @@ inline void DeriveLens(const AmberFlatThinLens& L, const AmberFlatObject* blade_
     const double tol = min_edge > 0 ? std::max(1e-3, 64.0 * 5.9604644775390625e-08 * world_mag / min_edge) : 1.0;
     lens.edge_tol = static_cast<float>(std::min(1.0, tol));
   }
+}
+
+// Does this handle scout (pt_megakernel's AMBER_KERNEL_SCOUT instantiation + replay_records_kernel) -- and from which bound of the eye weight?  Only the
+// 32-object two-phase engine has the instantiation; AMBER_PT_FLAG_NO_SCOUT asks for the full kernel; and the host must be able to bound the eye weight of this
+// lens (scout_bound.h: a thin lens or a pinhole with finite constants in range).  A non-finite material constant sends the handle to the full kernel as well:
+// the per-lane rule would flag those paths one by one, and a scene like that is no place to save arithmetic.  Decided once, at create: the handles that take
+// amber_hip_pt_update_lens and amber_hip_pt_update_objects are engine BVH's, which never scout.
+inline bool DecideScout(uint32_t engine, uint32_t hit_engine, uint32_t flags, const DevLens& lens, const std::vector<DevBlade>& blades, const std::vector<DevMaterial>& materials,
+                        float sensor_w, float sensor_h, uint32_t* bound0) {
+  *bound0 = 0;
+  if (engine == AMBER_ENGINE_WAVEFRONT || hit_engine != AMBER_ENGINE_TWO_PHASE || (flags & AMBER_PT_FLAG_NO_SCOUT)) return false;   // (the lab's WAVEFRONT only borrows the hit engine)
+  for (const DevMaterial& m : materials)
+    for (float x : {m.rho[0], m.rho[1], m.rho[2], m.param, m.r0, m.aux0, m.aux1}) if (!std::isfinite(x)) return false;
+  std::vector<float> vertices;
+  for (const DevBlade& bl : blades) for (const float* v : {bl.v0, bl.v1, bl.v2}) vertices.insert(vertices.end(), v, v + 3);
+  amber_scout::LensFacts f{};
+  f.kind = lens.kind; f.local_ = lens.local_; f.global_ = lens.global_; f.origin = lens.origin;
+  f.sensor_distance = lens.sensor_distance; f.focus_distance = lens.focus_distance; f.p_area = lens.p_area; f.size_over_area = lens.size_over_area;
+  f.inv_scene_area = lens.inv_scene_area; f.sensor_w = sensor_w; f.sensor_h = sensor_h;
+  f.blade_vertices = vertices.data(); f.n_vertices = static_cast<uint32_t>(vertices.size() / 3u);
+  return amber_scout::EyeWeightBound(f, bound0);
 }
 
 // The same records for a new lens on a resident scene (amber_hip_pt_update_lens): the sensor is the handle's, and so is the two-phase model box --

@@ -150,12 +150,18 @@ enum {
   AMBER_PT_FLAG_BVH_ITEMS = 4u,   /* engine BVH: always pt_bvh_megakernel.  By default a tree of depth <= 12 (scenes of a few hundred
                                      objects) renders with the path-granular kernel and a one-shot per-lane traversal
                                      (pt_megakernel<ENGINE_BVH>): same results bit for bit, faster on shallow trees. */
-  AMBER_PT_FLAG_DEVICE_BUILD = 8u /* engine BVH (AUTO past 80 objects, AMBER_ENGINE_BVH, WAVEFRONT over either): create builds the tree on the
+  AMBER_PT_FLAG_DEVICE_BUILD = 8u,/* engine BVH (AUTO past 80 objects, AMBER_ENGINE_BVH, WAVEFRONT over either): create builds the tree on the
                                      device -- Morton order, radix-tree hierarchy, the host builder's bounds, padding and outward binary16
                                      planes -- instead of the host's binned-SAH build: a much shorter create, a tree that renders somewhat slower
                                      (INTEGRATION.md gives the break-even), the same image bit for bit (the answer never depends on the tree).
                                      A Morton tree deeper than the traversal's limit is replaced by the host's (amber_hip_pt_build_info says
                                      so).  Any other engine: accepted, no effect. */
+  AMBER_PT_FLAG_NO_SCOUT = 16u  /* the 32-object two-phase engine (AUTO up to 32 objects, AMBER_ENGINE_TWO_PHASE): by default a pass traces every path
+                                     WITHOUT its weight (the weight reaches the image only where a path ends on a light: 2e-5 of the Cornell paths) and
+                                     traces again, with weights, the paths that end on a light or whose weight may have overflowed; with this bit
+                                     every path carries its weight.  Same image and ray count bit for bit; a measurement switch.  A lens whose eye
+                                     weight the host cannot bound (constants that are not finite, or beyond 2^+-20) renders as with the bit set.
+                                     Older libraries ignore the bit, so the ABI version stays.  Any other engine: accepted, no effect. */
 };
 
 /* All engines are the same persistent work-queue kernel; they differ in how a lane finds its closest hit.

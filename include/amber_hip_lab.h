@@ -114,6 +114,14 @@ int amber_hip_kat_lt_accumulate(amber_hip_pt*, const AmberSplat* records /* host
 typedef struct { uint32_t n_launches, n_repeats, rec_count, flag_words_set, flags_dirty; } AmberAccumulateInfo;
 int amber_hip_kat_accumulate(amber_hip_pt*, uint32_t n_samples, const uint32_t* q /* host, n_items */, const float* rgb /* host, n_items * 3 */, uint32_t n_items,
                              uint32_t n_waves, uint32_t rec_capacity, uint64_t rays, AmberAccumulateInfo* info);
+/* The scout's verdict (csrc/hip/pt_megakernel.inc, AMBER_KERNEL_SCOUT; scout_bound.h): one launch of the handle's weight-free kernel over samples
+ * [first_sample, first_sample + n_samples) of the band, WITHOUT the replay and without the reduction, and the launch's bitmap as the scout left it --
+ * bit q = band pixel * n_samples + sample offset is set iff the scout flagged path q (it ends on a light whose Radiance is not +0, or it is suspect).
+ * out_flags: host, n_words >= ceil(band pixels * n_samples / 32) words.  Nothing reaches the framebuffer or the ray total.  out_scouts (may be NULL):
+ * 1 if the handle scouts, 0 if it renders with the full kernel (then nothing is launched and out_flags is zeroed); out_bound0 (may be NULL): the host's bound of
+ * log2 |eye weight| for the handle's lens in sixteenths of a bit, the value every path's bound starts from.  AMBER_EINVAL: n_samples == 0, more
+ * paths than one launch takes, too few words.  Synchronous. */
+int amber_hip_kat_scout_flags(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples, uint32_t* out_flags, uint64_t n_words, uint32_t* out_scouts, uint32_t* out_bound0);
 /* Measurement: the first call switches on the timing of that device path with events (every accumulation then waits for the stream); every call
  * returns the milliseconds spent ordering (keys, sorts, gather) and summing since the previous call.  Either pointer may be NULL. */
 int amber_hip_kat_lt_stage_ms(amber_hip_pt*, double* sort_ms, double* sum_ms);
