@@ -107,6 +107,18 @@ PHOTONS_HOST = 1             # AMBER_PHOTONS_HOST: out is a host pointer
 PHOTON_CAPACITY0 = 65536     # AMBER_PHOTON_CAPACITY0: records the handle's photon staging buffer holds before the first growth
 PHOTON_DTYPE = np.dtype([("pos", np.float32, (3,)), ("object", np.int32), ("dir_out", np.float32, (3,)), ("path", np.uint32),
                          ("weight", np.float32, (3,)), ("sample", np.uint32), ("normal", np.float32, (3,)), ("bounce", np.uint32)])   # AmberPhoton
+PM_RAW_SUM = 2               # AMBER_PM_RAW_SUM: amber_hip_pm_gather returns the plain sum S instead of (S * kern) * weight
+GATHER_QUERY_DTYPE = np.dtype([("pos", np.float32, (3,)), ("radius", np.float32), ("normal", np.float32, (3,)), ("object", np.int32),
+                               ("dir_out", np.float32, (3,)), ("pad0", np.uint32), ("weight", np.float32, (3,)), ("pad1", np.uint32)])   # AmberGatherQuery
+GATHER_RESULT_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("n_used", np.uint32), ("r2_used", np.float32), ("n_in_radius", np.uint32),
+                                ("pad", np.uint32, (2,))])                                                                                   # AmberGatherResult
+
+
+class PhotonMapInfo(C.Structure):
+    """AmberPhotonMapInfo: what amber_hip_pm_build made -- counts, the grid (dims, the cell size used and how often it doubled, bounds), the largest cell,
+    the host's wall-clock milliseconds: 72 bytes."""
+    _fields_ = [("n_photons", C.c_uint64), ("n_dropped", C.c_uint64), ("dims", C.c_uint32 * 3), ("n_doublings", C.c_uint32), ("cell_size", C.c_float),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("max_cell_count", C.c_uint32), ("build_ms", C.c_double)]
 
 
 class Ray(C.Structure):
@@ -202,7 +214,7 @@ ABI_SYMBOLS = [
     "amber_hip_pt_render_batch", "amber_hip_pt_moments_clear", "amber_hip_pt_moments_download", "amber_hip_pt_device_moments", "amber_hip_pt_denoise_variance",
     "amber_hip_pt_temporal", "amber_hip_pt_temporal_reset", "amber_hip_pt_history_download", "amber_hip_pt_device_history",
     "amber_hip_last_error", "amber_hip_abi_version", "amber_hip_math_mode", "amber_hip_device_count", "amber_hip_lt_trace", "amber_hip_lt_trace_range", "amber_hip_lt_render_pass",
-    "amber_hip_lt_trace_photons",
+    "amber_hip_lt_trace_photons", "amber_hip_pm_build", "amber_hip_pm_gather", "amber_hip_pm_release",
     "amber_host_cornell_box", "amber_host_scene_import", "amber_host_scene_create", "amber_host_scene_destroy", "amber_host_scene_flatten",
     "amber_host_pt_create", "amber_host_render", "amber_host_render_devices", "amber_host_last_error", "amber_host_tonemap", "amber_host_export",
 ]
@@ -211,7 +223,7 @@ LAB_SYMBOLS = [
     "amber_hip_kat_cast", "amber_hip_kat_sample", "amber_hip_kat_eye", "amber_hip_kat_trace", "amber_hip_kat_math", "amber_hip_kat_signatures", "amber_hip_pt_signatures",
     "amber_hip_kat_traversal_rate", "amber_hip_kat_pixel_masks", "amber_hip_kat_bvh_dump", "amber_hip_kat_division",
     "amber_hip_kat_sqrt", "amber_hip_kat_sqrt_sweep", "amber_hip_kat_lt_accumulate", "amber_hip_kat_lt_stage_ms",
-    "amber_hip_kat_photon_stage_ms",
+    "amber_hip_kat_photon_stage_ms", "amber_hip_kat_pm_stage_ms", "amber_hip_kat_bsdf",
     "amber_hip_kat_light_ray", "amber_hip_kat_lens_response", "amber_hip_kat_radiance", "amber_host_kat_scene_lights",
     "amber_hip_kat_accumulate", "amber_hip_kat_phase_a", "amber_hip_kat_scout_flags",
 ]
@@ -303,6 +315,13 @@ def load_library() -> C.CDLL:
             lib.amber_hip_lt_trace_photons.argtypes = [vp, u32, u32, u32, u32, u32, vp, u64, C.POINTER(PhotonInfo), u32]
         if hasattr(lib, "amber_hip_kat_photon_stage_ms"):   # lab build
             lib.amber_hip_kat_photon_stage_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(lib, "amber_hip_pm_build"):             # (a library built before the photon map has no such symbols)
+        lib.amber_hip_pm_build.argtypes = [vp, vp, u64, C.c_float, u32, C.POINTER(PhotonMapInfo)]
+        lib.amber_hip_pm_gather.argtypes = [vp, u64, vp, vp, u32, u32]
+        lib.amber_hip_pm_release.argtypes = [vp]
+    if hasattr(lib, "amber_hip_kat_pm_stage_ms"):      # lab build
+        lib.amber_hip_kat_pm_stage_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        lib.amber_hip_kat_bsdf.argtypes = [vp, u32, vp, vp, vp, vp, vp]
     if hasattr(lib, "amber_hip_kat_cast"):         # the lab build (include/amber_hip_lab.h); the product exports none of these
         if hasattr(lib, "amber_hip_kat_phase_a"):      # (a library built before it has no such symbol)
             lib.amber_hip_kat_phase_a.argtypes = [vp, u32, vp, vp, i32, vp, u64, C.POINTER(C.c_uint32)]
@@ -997,7 +1016,88 @@ class PathTracer:
         d = call(ptr, capacity, 0)
         return d["n_written"], d
 
+    def pm_build(self, photons, cell_size: float) -> dict:
+        """amber_hip_pm_build: the handle's photon map -- a uniform grid of cells of `cell_size` (doubled until the grid fits 1024 cells per axis and
+        2^22 in all) over `photons`, replacing the map before.  Only pos, dir_out and weight of the records are read; photons with a non-finite position
+        are dropped.  include/amber_hip.h states it; tests/photon_map_reference.py restates it.  Returns AmberPhotonMapInfo as a dict.
+        photons = a numpy array of PHOTON_DTYPE (what lt_trace_photons returns): through AMBER_PHOTONS_HOST.
+        photons = a torch tensor on the handle's device (contiguous, rows of 64 bytes), or (device pointer, count): read zero-copy on the handle's stream
+        (ORDERING as cast_rays).  Either way the buffer is free when the call returns: the map keeps its own copy, and the call waits for the stream."""
+        lib = load_library()
+        info = PhotonMapInfo()
+
+        def call(ptr, n, flags):
+            _check(lib.amber_hip_pm_build(self._h, ptr, n, cell_size, flags, C.byref(info)))
+            d = {k: getattr(info, k) for k, _ in PhotonMapInfo._fields_}
+            d["dims"], d["lo"], d["hi"] = tuple(info.dims), tuple(info.lo), tuple(info.hi)
+            return d
+
+        if isinstance(photons, np.ndarray):
+            rec = np.ascontiguousarray(photons, PHOTON_DTYPE).reshape(-1)
+            return call(rec.ctypes.data if len(rec) else None, len(rec), PHOTONS_HOST)
+        if self._is_torch(photons):
+            import torch
+            if not photons.is_cuda or not photons.is_contiguous() or photons.dim() != 2 or photons.shape[1] * photons.element_size() != 64:
+                raise AmberError("pm_build: photons must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
+            same = self._torch_enter(torch, photons.device)
+            try:
+                return call(photons.data_ptr() if photons.shape[0] else None, photons.shape[0], 0)
+            finally:
+                self._torch_leave(same)
+        ptr, n = photons
+        return call(ptr, n, 0)
+
+    def pm_gather(self, queries, k: int = 0, raw: bool = False, out=None):
+        """amber_hip_pm_gather: for every query (GATHER_QUERY_DTYPE: pos, radius | normal, object | dir_out | weight) the photons of the handle's map within
+        `radius` -- the k nearest of them when k > 0 and there are more -- and rgb = (sum(photon.weight * rho * fs) * kern) * weight, kern = 1 / (pi radius^2)
+        (raw=True: the plain sum).  Returns GATHER_RESULT_DTYPE records: rgb, n_used, r2_used, n_in_radius.
+        queries = a numpy array of GATHER_QUERY_DTYPE: through AMBER_RAYS_HOST; `out` (optional) a numpy array of GATHER_RESULT_DTYPE of the same length.
+        queries = a torch tensor on the handle's device (contiguous, rows of 64 bytes, e.g. (n, 16) float32): zero-copy on the handle's stream (ORDERING as
+        cast_rays); `out` (optional) a tensor with rows of 32 bytes; an (n, 8) float32 tensor comes back."""
+        lib = load_library()
+        flags = PM_RAW_SUM if raw else 0
+        if self._is_torch(queries):
+            import torch
+            if not queries.is_cuda or not queries.is_contiguous() or queries.dim() != 2 or queries.shape[1] * queries.element_size() != 64:
+                raise AmberError("pm_gather: queries must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
+            n = queries.shape[0]
+            if out is None:
+                out = torch.empty((n, 8), dtype=torch.float32, device=queries.device)
+            elif not self._is_torch(out) or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[0] != n or out.shape[1] * out.element_size() != 32:
+                raise AmberError("pm_gather: out must be a contiguous torch tensor on the handle's device with a row of 32 bytes per query")
+            same = self._torch_enter(torch, queries.device)
+            try:
+                _check(lib.amber_hip_pm_gather(self._h, n, queries.data_ptr() if n else None, out.data_ptr() if n else None, k, flags))
+            finally:
+                self._torch_leave(same)
+            return out
+        q = np.ascontiguousarray(queries, GATHER_QUERY_DTYPE).reshape(-1)
+        if out is None:
+            out = np.zeros(len(q), GATHER_RESULT_DTYPE)
+        elif not isinstance(out, np.ndarray) or out.dtype != GATHER_RESULT_DTYPE or not out.flags.c_contiguous or out.shape != (len(q),):
+            raise AmberError("pm_gather: out must be a contiguous numpy array of GATHER_RESULT_DTYPE with a record per query")
+        _check(lib.amber_hip_pm_gather(self._h, len(q), q.ctypes.data if len(q) else None, out.ctypes.data if len(q) else None, k, RAYS_HOST | flags))
+        return out
+
+    def pm_release(self) -> None:
+        """amber_hip_pm_release: waits for the handle's stream and frees the photon map and its scratch; pm_gather is an error until the next pm_build."""
+        _check(load_library().amber_hip_pm_release(self._h))
+
     # ---- known-answer entry points -----------------------------------------------------------
+    def kat_pm_stage_ms(self):
+        """Lab build: (build ms, gather ms) of pm_build / pm_gather by hipEvents since the previous call; the first call switches the timing on."""
+        a, b = C.c_double(), C.c_double()
+        _check(load_library().amber_hip_kat_pm_stage_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def kat_bsdf(self, objects, normals, dirs_out, dirs_in):
+        """Lab build: rho * SymmetricBSDF(normal, dir_out, dir_in) of the material of objects[i] (scene object indices), (n, 3) float32."""
+        o = np.ascontiguousarray(objects, np.int32)
+        nn, dd, di = _f32(normals).reshape(-1, 3), _f32(dirs_out).reshape(-1, 3), _f32(dirs_in).reshape(-1, 3)
+        out = np.empty((len(o), 3), np.float32)
+        _check(load_library().amber_hip_kat_bsdf(self._h, len(o), o.ctypes.data, nn.ctypes.data, dd.ctypes.data, di.ctypes.data, out.ctypes.data))
+        return out
+
     def kat_photon_stage_ms(self):
         """Lab build: (trace ms, sort ms, gather ms) of lt_trace_photons by hipEvents since the previous call; the first call switches the timing on."""
         a, b, c = C.c_double(), C.c_double(), C.c_double()

@@ -37,6 +37,24 @@ __device__ __forceinline__ V3 Radiance(const DevMaterial& m, V3 normal, V3 dir_o
   return ld3(m.rho);
 }
 
+// Material::SymmetricBSDF of the two diffuse kinds (material_lambertian.cc:35-49, material_phong.cc:40-61); every other kind answers 0 here: the
+// reference evaluates a BSDF on SurfaceType::Diffuse only.  std::max<real_type>(0, x) keeps 0 unless 0 < x (NaN and -0 give +0).
+__device__ __forceinline__ float SymmetricBSDF(const DevMaterial& m, V3 normal, V3 dir_out, V3 dir_in) {
+  const uint32_t kind = m.kind;
+  if (kind != MAT_LAMBERTIAN && kind != MAT_PHONG) return 0.0f;
+  const float signed_cos_o = Dot(dir_out, normal);
+  const float signed_cos_i = Dot(dir_in, normal);
+  if (signed_cos_o * signed_cos_i <= 0.0f) return 0.0f;
+  if (kind == MAT_LAMBERTIAN) return 1.0f / 3.14159274f;
+  const float d = Dot(PerfectReflection(dir_in, normal, signed_cos_i), dir_out);
+  const float cos_alpha = 0.0f < d ? d : 0.0f;
+  return ((m.param + 2.0f) / (2.0f * 3.14159274f)) * Pow(cos_alpha, m.param);
+}
+// Scene::BSDF -> the symmetric forwarder (material_basic.h:282-289): rho * SymmetricBSDF
+__device__ __forceinline__ V3 BSDF(const DevMaterial& m, V3 normal, V3 dir_out, V3 dir_in) {
+  return ld3(m.rho) * SymmetricBSDF(m, normal, dir_out, dir_in);
+}
+
 // Scene::SampleLight -> Material::SampleLight (+ rho forwarders, material_basic.h:233-245, 327-338)
 // kSqrtMask: the switch bits of AMBER_EXACT_SQRT (dev_math.h) that the calling kernel asks for; 0: every root is __builtin_sqrtf
 template <bool kSharedDiv = false, uint32_t kSqrtMask = 0u>

@@ -507,6 +507,36 @@ int amber_hip_kat_photon_stage_ms(amber_hip_pt* h, double* trace_ms, double* sor
   return AMBER_OK;
 }); }
 
+int amber_hip_kat_pm_stage_ms(amber_hip_pt* h, double* build_ms, double* gather_ms) { return Guarded("amber_hip_kat_pm_stage_ms", [&]() -> int {
+  if (!h) return Fail(AMBER_EINVAL, "null handle");
+  PhotonMapBufs& m = h->pm;
+  m.stage_timing = true;
+  if (build_ms) *build_ms = m.build_ms;
+  if (gather_ms) *gather_ms = m.gather_ms;
+  m.build_ms = m.gather_ms = 0;
+  return AMBER_OK;
+}); }
+
+int amber_hip_kat_bsdf(amber_hip_pt* h, uint32_t n, const int32_t* object, const float* normal, const float* dir_out, const float* dir_in, float* rgb_out) {
+  return Guarded("amber_hip_kat_bsdf", [&]() -> int {
+  if (!h || !object || !normal || !dir_out || !dir_in || !rgb_out) return Fail(AMBER_EINVAL, "null argument");
+  if (n == 0) return AMBER_OK;
+  if (n > 0x3fffffffu) return Fail(AMBER_EINVAL, "too many items for one call");
+  for (uint32_t i = 0; i < n; i++) if (object[i] < 0 || static_cast<uint32_t>(object[i]) >= h->scene.n_objects) return Fail(AMBER_EINVAL, "object index out of range");
+  HIP_TRY(hipSetDevice(h->device));
+  DevBuf<int32_t> d_obj; DevBuf<float> d_n, d_o, d_i, d_rgb;
+  HIP_TRY(d_obj.alloc(n)); HIP_TRY(d_n.alloc(3ull * n)); HIP_TRY(d_o.alloc(3ull * n)); HIP_TRY(d_i.alloc(3ull * n)); HIP_TRY(d_rgb.alloc(3ull * n));
+  HIP_TRY(hipMemcpy(d_obj.p, object, 4ull * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_n.p, normal, 12ull * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_o.p, dir_out, 12ull * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_i.p, dir_in, 12ull * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kat_bsdf_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->scene, n, d_obj.p, d_n.p, d_o.p, d_i.p, d_rgb.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(rgb_out, d_rgb.p, 12ull * n, hipMemcpyDeviceToHost));
+  return AMBER_OK;
+}); }
+
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out) { return Guarded("amber_hip_kat_math", [&]() -> int {
   if (!x || !out || mode < 0 || mode > 3) return Fail(AMBER_EINVAL, "bad argument");
   if (n == 0) return AMBER_OK;

@@ -107,6 +107,13 @@ __global__ void kat_radiance_kernel(const DevScene sc, uint32_t n, const uint32_
   out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
 }
 
+__global__ void kat_bsdf_kernel(const DevScene sc, uint32_t n, const int32_t* object, const float* normals, const float* dirs_out, const float* dirs_in, float* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 r = BSDF(sc.materials[sc.objects[object[i]].material], ld3(normals + 3 * i), ld3(dirs_out + 3 * i), ld3(dirs_in + 3 * i));
+  out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+
 template <int kEngine>
 __global__ void kat_trace_kernel(const DevScene sc, uint64_t hashed_seed, uint32_t n, const uint32_t* pixel,
                                  const uint32_t* sample, uint32_t max_bounces, uint32_t* out_records, uint32_t* out_casts) {

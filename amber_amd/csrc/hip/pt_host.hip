@@ -40,6 +40,10 @@
 //                          permutation sorted by (pixel, pass, path, bounce) with two stable radix sorts, then one thread per pixel run.
 //   lt_photons.inc         amber_hip_lt_trace_photons: the vertex records of a light-tracing launch (PathShade's second sink) into the caller's buffer in
 //                          (sample, path, bounce) order -- two stable radix sorts of an index permutation, one gather of the 64-byte records.
+//   photon_map.inc         amber_hip_pm_build / amber_hip_pm_gather / amber_hip_pm_release: the handle's photon map -- a uniform grid over the caller's photons (bounds
+//                          by a reduction, cell keys, one stable radix sort, cell starts, a packed {position, index} array and a payload array) and the
+//                          k-nearest radiance gather, a lane per query: one sweep over the cells the radius touches; a bisection over the bit patterns of
+//                          the squared distance for the queries that have more than k photons in radius.
 //   pt_replay.inc          replay_records_kernel: the paths a scouted launch flagged (pt_megakernel's AMBER_KERNEL_SCOUT instantiation), traced again with
 //                          their weights, one lane per record; scout_bound.h: the rule that flags them and the host's bound of the eye weight.
 //   pt_records.inc         records {q, rgb} -> path order -> the per-pixel sums of the numerical contract (rec_rank / scan / place, reduce_flagged);
@@ -184,6 +188,23 @@ struct PhotonBufs {
   Event ev[5];
 #endif
 };
+// amber_hip_pm_build / amber_hip_pm_gather (photon_map.inc): the handle's one photon map and the scratch of its build, nothing of it before the first
+// build; the sort borrows LtAccumBufs' keys, permutations and scratch
+struct PhotonMapBufs {
+  bool built = false;                       // a build has succeeded and amber_hip_pm_release has not been called since
+  AmberPhotonMapInfo info{};                // of that build (n_photons - n_dropped photons are in the map)
+  DevBuf<float4> posidx;                    // {x, y, z, input index} of the kept photons in cell order: what the distance test reads
+  DevBuf<float4> payload;                   // {dir_out, 0} {weight, 0} in the same order: read for the photons that pass it
+  DevBuf<uint32_t> start;                   // cells + 1: the first photon of every cell
+  DevBuf<uint32_t> ctl;                     // build: ordered bit patterns of the bounds (3 minima, 3 maxima), the dropped count
+  DevBuf<float4> staged;                    // AMBER_PHOTONS_HOST: the caller's records on their way in
+  DevBuf<float4> queries, results;          // AMBER_RAYS_HOST: staging of a gather, at most kQueryStageRays queries
+#ifdef AMBER_LAB
+  bool stage_timing = false;                // amber_hip_kat_pm_stage_ms: build and gather timed with events (every gather then waits for the stream)
+  double build_ms = 0, gather_ms = 0;
+  Event ev[2];
+#endif
+};
 // The image stage -- everything that runs on the band after accumulation (image_stage.inc and the five files behind it): its buffers, per band pixel
 struct ImageStageBufs {
   DevBuf<uint8_t> resolve_out;              // AMBER_RESOLVE_HOST: staging of the output (WriteBandOutput), grown on first use and reused
@@ -291,6 +312,7 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   uint64_t hashed_seed_lt = 0;
   LtAccumBufs lt;                           // amber_hip_lt_render_pass
   PhotonBufs photons;                       // amber_hip_lt_trace_photons
+  PhotonMapBufs pm;                         // amber_hip_pm_build / amber_hip_pm_gather
   DevBuf<float> d_partial;                  // pt_bvh_megakernel: per-item sums
   PathLaunchBufs paths;                     // the path-granular launches and the one in flight
   DevBuf<int32_t> d_bvh_stack;              // pt_bvh_pool_kernel (lab build): deep traversal-stack levels
@@ -548,6 +570,7 @@ int amber_hip_pt_create(const AmberFlatScene* s, const AmberSensor* sensor, cons
 #include "temporal.inc"
 #include "lt_accumulate.inc"
 #include "lt_photons.inc"
+#include "photon_map.inc"
 
 namespace {
 #ifdef AMBER_LAB
@@ -649,6 +672,18 @@ int amber_hip_lt_render_pass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
 int amber_hip_lt_trace_photons(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end, uint32_t surfaces,
                                AmberPhoton* out, uint64_t capacity, AmberPhotonInfo* info, uint32_t flags) {
   return Guarded("amber_hip_lt_trace_photons", [&] { return TracePhotons(h, first_sample, n_samples, path_begin, path_end, surfaces, out, capacity, info, flags); });
+}
+
+int amber_hip_pm_build(amber_hip_pt* h, const AmberPhoton* photons, uint64_t n, float cell_size, uint32_t flags, AmberPhotonMapInfo* info) {
+  return Guarded("amber_hip_pm_build", [&] { return PmBuild(h, photons, n, cell_size, flags, info); });
+}
+
+int amber_hip_pm_gather(amber_hip_pt* h, uint64_t n, const AmberGatherQuery* q, AmberGatherResult* out, uint32_t k, uint32_t flags) {
+  return Guarded("amber_hip_pm_gather", [&] { return PmGather(h, n, q, out, k, flags); });
+}
+
+int amber_hip_pm_release(amber_hip_pt* h) {
+  return Guarded("amber_hip_pm_release", [&] { return PmRelease(h); });
 }
 
 int amber_hip_lt_trace(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, AmberSplat* out, uint32_t capacity,

@@ -36,7 +36,8 @@ extern "C" {
                                     Still 3 with amber_hip_pt_update_lens(): a new function.  Still 3 with amber_hip_pt_resolve(): a new function.
                                     Still 3 with amber_hip_pt_aov_pass() / _aov_clear() / _aov_download() / amber_hip_pt_device_aov(): four new functions and their struct.
                                     Still 3 with amber_hip_pt_trace_paths() / amber_hip_sampler_state(): two new functions and their two structs.
-                                    Still 3 with amber_hip_lt_trace_photons(): one function, two structs, constants */
+                                    Still 3 with amber_hip_lt_trace_photons(): one function, two structs, constants.
+                                    Still 3 with amber_hip_pm_build() / _pm_gather() / _pm_release(): three functions, three structs, a flag */
 
 /* Accumulation granule: within a render pass the samples of a pixel are summed sequentially in chunks of
  * AMBER_ACCUM_CHUNK consecutive samples (starting at first_sample), and the chunk sums are added to the
@@ -667,7 +668,7 @@ int amber_hip_lt_render_pass(amber_hip_pt*, uint32_t first_sample, uint32_t n_sa
  * AMBER_BVH_WIDE build.  AMBER_OK with zero photons: n_samples == 0, an empty path range, a scene without lights.
  * Banded and striped handles are accepted: light paths do not know the band, and the path range is how several devices share the work, as with
  * amber_hip_lt_trace_range.  Every engine on which amber_hip_lt_trace works, AMBER_PT_FLAG_BVH_ITEMS and AMBER_PT_FLAG_DEVICE_BUILD included.
- * Not here: the k-d tree, nearest-neighbour search and any density estimate; eye subpaths; the pdf and geometry-factor fields of SubpathEvent;
+ * Not here: the nearest-neighbour search and the density estimate (the photon map below has them); eye subpaths; the pdf and geometry-factor fields of SubpathEvent;
  * the command line and the C++ adapter.  Still ABI version 3: one function, two structs, constants. */
 enum { AMBER_PHOTON_DIFFUSE = 1u,   /* AMBER_MAT_LAMBERTIAN, AMBER_MAT_PHONG   (SurfaceType::Diffuse)  */
        AMBER_PHOTON_SPECULAR = 2u,  /* AMBER_MAT_SPECULAR, AMBER_MAT_REFRACTION (SurfaceType::Specular) */
@@ -681,6 +682,63 @@ typedef struct { float pos[3]; int32_t object; float dir_out[3]; uint32_t path;
 typedef struct { uint64_t n_photons, n_written, n_rays; uint32_t n_launches, n_repeats; } AmberPhotonInfo; /* 32 bytes */
 int amber_hip_lt_trace_photons(amber_hip_pt*, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end,
                                uint32_t surfaces, AmberPhoton* out, uint64_t capacity, AmberPhotonInfo* info /* may be NULL */, uint32_t flags);
+
+/* ---- photon map: grid build and k-nearest radiance gather -------------------------------------------------------------------------------------
+ * What the reference's photon family does with the list above: PhotonMap::Search(point, radius, k), then sum(photon.Weight() * BSDF) * kernel()
+ * * weight (algorithm_sppm.cc:200-214, the same loop in algorithm_mppm.cc; algorithm_ups.cc merges the same way).  A handle owns ONE photon map:
+ * amber_hip_pm_build makes it from the caller's AmberPhoton records (only pos, dir_out and weight are read) and replaces the one before,
+ * amber_hip_pm_gather answers queries against it, amber_hip_pm_release or destroy ends it.  A handle that never calls these pays nothing.
+ * Every operation is binary32 and rounded alone, with no contraction; tests/photon_map_reference.py restates all of it in numpy.
+ *
+ * The grid (build).  Photons with a non-finite pos component are dropped (n_dropped).  Over the rest, lo[a] is the minimum and hi[a] the maximum
+ * of pos[a] (order-independent; -0 orders below +0).  c = cell_size, inv = 1.0f / c, dims[a] = (uint32)floorf((hi[a] - lo[a]) * inv) + 1.  The
+ * limits are dims[a] <= 1024 and dims[0] * dims[1] * dims[2] <= 2^22.  While a limit is exceeded, or a product (hi[a] - lo[a]) * inv is not below
+ * 2^31: c = c * 2, inv and dims again, n_doublings counts the step.  info->cell_size is the c used.  (An extent hi[a] - lo[a] that overflows
+ * binary32 has no such c: AMBER_EINVAL, and the map before stays.)  cellf(x, a) = floorf((x - lo[a]) * inv); a photon's cell is
+ * (iz * dims[1] + iy) * dims[0] + ix with i* = cellf(pos[*], *), inside the grid by construction (floorf and the two operations are monotone).
+ * Within a cell photons stand in ascending input index: a stable sort of the input order by cell.  max_cell_count is the largest cell's count.
+ * n == 0, or everything dropped: a valid EMPTY map -- dims, lo, hi and max_cell_count are 0, cell_size is the argument, and gather answers
+ * all-zero results.  The map copies what it needs: the caller's buffer is free when build returns.  Build is stream-ordered after everything
+ * enqueued on the handle and waits for the stream, because it reads the bounds back, as amber_hip_lt_trace_photons reads its counts.  build_ms is
+ * the host's wall-clock time of the call.  info (may be NULL) is zeroed first, whatever the call then answers.
+ *
+ * The gather, for query i.  r2 = radius * radius.  The all-zero result {0, 0, 0, 0, +0, 0} answers: a non-finite pos component; a radius that is
+ * NaN, infinite or <= 0; an object outside [0, n_objects).  Per axis clo = cellf(pos[a] - radius, a), chi = cellf(pos[a] + radius, a), compared AS
+ * FLOATS with 0 and dims[a] - 1 before any conversion (chi < 0 or clo > dims[a] - 1 on some axis: nothing is visited), then clamped to the grid.
+ * Visit order: iz in the outer loop, then iy, then ix, all ascending; within a cell, the cell's order.  A visited photon is in radius iff d2 < r2
+ * with dx = photon.x - pos.x (likewise dy, dz), d2 = (dx * dx + dy * dy) + dz * dz; N = n_in_radius counts them.  The cell range loses none: cellf
+ * is monotone and pos[a] - radius is correctly rounded.
+ * Selection.  k == 0 or N <= k: all of them are used, n_used = N, r2_used = r2.  Otherwise T is the k-th smallest d2, counting multiplicity; used
+ * are the photons with d2 < T plus the first k - #{d2 < T} photons IN VISIT ORDER with d2 == T; n_used = k, r2_used = T.  Whenever no two photons
+ * tie at the k-th distance this is the set KDTree::Search ends with (kdtree.h:235-246: a max-heap of k, the radius shrinking to its top).
+ * Sum.  S = (+0, +0, +0); over the used photons in visit order S[c] = S[c] + photon.weight[c] * (rho[c] * fs), rho that of the material of
+ * objects[object], fs = SymmetricBSDF(normal, dir_out, photon.dir_out): 0 when Dot(dir_out, n) * Dot(dir_in, n) <= 0; Lambertian
+ * (material_lambertian.cc:35-49) 1 / (float)kPI; Phong (material_phong.cc:40-61) ((e + 2) / (2 * (float)kPI)) * powf(max(0, Dot(PerfectReflection(
+ * dir_in, n, cos_i), dir_out)), e) with the library's powf (amber_hip_math_mode); every other material kind 0 (the reference gathers on
+ * SurfaceType::Diffuse only).  rgb[c] = (S[c] * kern) * weight[c], kern = 1 / (((float)kPI * radius) * radius) (kernel.h:52: the QUERY's radius,
+ * also when k shrank the search, as in the reference); with AMBER_PM_RAW_SUM rgb = S.  The order of the sum is this call's own, not the
+ * reference's heap order.
+ * The result for query i does not depend on n, on its position in the batch or on the other queries.
+ * Memory and order as amber_hip_pt_cast_rays: DEVICE pointers (16-byte aligned) by default, asynchronous and stream-ordered on the handle's stream;
+ * with AMBER_RAYS_HOST host pointers, staged through handle-owned buffers, and the call returns after the copy back.  Neither call touches the
+ * framebuffer, the ray counter or amber_hip_pt_kernel_time; amber_hip_pt_update_objects (the gather reads the object's material index as the
+ * update left it) and amber_hip_pt_update_lens leave the map alone.  amber_hip_pm_release waits for the stream and frees the map and its scratch.
+ * AMBER_EINVAL, with no effect and the handle left working: a NULL handle; a NULL pointer with work to do; n > 2^31 for either call; a cell_size
+ * that is NaN, infinite or <= 0; k > 2^31; unknown flag bits; a misaligned device pointer; gather before any build or after release (also with
+ * n == 0).  AMBER_OK with nothing written: gather with n == 0 on a handle that has a map.
+ * Not here: the integrators (sppm, mppm, ups) and their radius statistics; the eye-path walk past specular bounces; the indices of the photons a
+ * query used; maps over several devices.  Still ABI version 3: three functions, three structs, a flag. */
+typedef struct { float pos[3]; float radius; float normal[3]; int32_t object;
+                 float dir_out[3]; uint32_t pad0; float weight[3]; uint32_t pad1; } AmberGatherQuery;   /* 64 bytes: four float4 */
+typedef struct { float rgb[3]; uint32_t n_used; float r2_used; uint32_t n_in_radius; uint32_t pad[2]; } AmberGatherResult; /* 32 bytes */
+typedef struct { uint64_t n_photons, n_dropped; uint32_t dims[3]; uint32_t n_doublings;
+                 float cell_size; float lo[3]; float hi[3]; uint32_t max_cell_count; double build_ms; } AmberPhotonMapInfo; /* 72 bytes */
+enum { AMBER_PM_RAW_SUM = 2u };   /* gather flag, next to AMBER_RAYS_HOST = 1u: rgb is the plain sum S */
+int amber_hip_pm_build(amber_hip_pt*, const AmberPhoton* photons, uint64_t n, float cell_size,
+                       uint32_t flags /* AMBER_PHOTONS_HOST */, AmberPhotonMapInfo* info /* may be NULL */);
+int amber_hip_pm_gather(amber_hip_pt*, uint64_t n, const AmberGatherQuery* q, AmberGatherResult* out,
+                        uint32_t k /* 0: no cap */, uint32_t flags /* AMBER_RAYS_HOST | AMBER_PM_RAW_SUM */);
+int amber_hip_pm_release(amber_hip_pt*);
 
 const char* amber_hip_last_error(void);
 int         amber_hip_abi_version(void);

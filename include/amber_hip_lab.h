@@ -128,6 +128,12 @@ int amber_hip_kat_lt_stage_ms(amber_hip_pt*, double* sort_ms, double* sum_ms);
 /* the same for amber_hip_lt_trace_photons: hipEvent milliseconds of its trace kernels, its sorts (keys included) and its gathers since the previous call;
  * the first call switches the timing on (every launch's gather is then waited for) */
 int amber_hip_kat_photon_stage_ms(amber_hip_pt*, double* trace_ms, double* sort_ms, double* gather_ms);
+/* the same for the photon map: hipEvent milliseconds of amber_hip_pm_build (first kernel to last; the wait for the bounds lies in between) and of
+ * amber_hip_pm_gather's kernels since the previous call; the first call switches the timing on (every gather then waits for its kernel) */
+int amber_hip_kat_pm_stage_ms(amber_hip_pt*, double* build_ms, double* gather_ms);
+/* Scene::BSDF alone (csrc/hip/dev_shading.h): rgb_out[i] = rho * SymmetricBSDF(normal[i], dir_out[i], dir_in[i]) of the material of objects[object[i]],
+ * the factor amber_hip_pm_gather multiplies a photon's weight with.  Host arrays, three floats per item; an object index out of range is AMBER_EINVAL. */
+int amber_hip_kat_bsdf(amber_hip_pt*, uint32_t n, const int32_t* object, const float* normal, const float* dir_out, const float* dir_in, float* rgb_out);
 /* the engine's sin/cos/pow on device: mode 0 = sincos(x[i]) -> out[2i], out[2i+1] ; mode 1 = pow(x[2i], x[2i+1]) -> out[i] ;
  * mode 2 / 3 = x[i]^4 / x[i]^5 in binary64 -> out[2i], out[2i+1] = low, high word of the double */
 int amber_hip_kat_math(int device, int mode, uint32_t n, const float* x, float* out);
