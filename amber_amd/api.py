@@ -1,6 +1,7 @@
 """ctypes binding of include/amber_hip.h and include/amber_host.h (no compute in Python)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -697,9 +698,8 @@ class PathTracer:
             _check(lib.amber_hip_pt_cast_rays(self._h, n, packed.ctypes.data, hits.ctypes.data, RAYS_HOST))
             return hits["object"].copy(), hits["t"].copy(), hits["pos"].copy(), hits["normal"].copy()
         out = torch.empty((n, 8), dtype=torch.float32, device=packed.device)
-        same = self._torch_enter(torch, packed.device)
-        _check(lib.amber_hip_pt_cast_rays(self._h, n, packed.data_ptr(), out.data_ptr(), 0))
-        self._torch_leave(same)
+        with self._on_stream(torch, packed.device):
+            _check(lib.amber_hip_pt_cast_rays(self._h, n, packed.data_ptr(), out.data_ptr(), 0))
         return out[:, 1].contiguous().view(torch.int32), out[:, 0].contiguous(), out[:, 2:5].contiguous(), out[:, 5:8].contiguous()
 
     def occluded(self, origins, dirs, t_max=None):
@@ -713,9 +713,8 @@ class PathTracer:
             _check(lib.amber_hip_pt_occluded(self._h, n, packed.ctypes.data, occ.ctypes.data, RAYS_HOST))
             return occ.astype(bool)
         out = torch.empty(n, dtype=torch.uint8, device=packed.device)
-        same = self._torch_enter(torch, packed.device)
-        _check(lib.amber_hip_pt_occluded(self._h, n, packed.data_ptr(), out.data_ptr(), 0))
-        self._torch_leave(same)
+        with self._on_stream(torch, packed.device):
+            _check(lib.amber_hip_pt_occluded(self._h, n, packed.data_ptr(), out.data_ptr(), 0))
         return out.to(torch.bool)
 
     def trace_paths(self, origins, dirs, weights=None, states=None, n_samples: int = 1, max_depth: int = 0):
@@ -750,9 +749,8 @@ class PathTracer:
                 states = torch.from_numpy(np.ascontiguousarray(states, np.uint64).view(np.int64))
             packed.view(torch.int64)[:, 6] = states.to(device=o.device, dtype=torch.int64).reshape(-1)
             out = torch.empty((n, 8), dtype=torch.float32, device=o.device)
-            same = self._torch_enter(torch, o.device)
-            _check(lib.amber_hip_pt_trace_paths(self._h, n, packed.data_ptr(), out.data_ptr(), n_samples, max_depth, 0))
-            self._torch_leave(same)
+            with self._on_stream(torch, o.device):
+                _check(lib.amber_hip_pt_trace_paths(self._h, n, packed.data_ptr(), out.data_ptr(), n_samples, max_depth, 0))
             return out[:, 0:3].contiguous(), out[:, 3].contiguous().view(torch.int32), out.view(torch.int64)[:, 2].contiguous()
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
         n = len(o)
@@ -766,16 +764,24 @@ class PathTracer:
         _check(lib.amber_hip_pt_trace_paths(self._h, n, packed.ctypes.data, res.ctypes.data, n_samples, max_depth, RAYS_HOST))
         return res["rgb"].copy(), res["casts"].copy(), res["rng_state"].copy()
 
-    def _torch_enter(self, torch, device) -> bool:
-        """True when torch's current stream IS the handle's stream (everything is ordered already); otherwise torch's stream is waited for."""
+    @contextlib.contextmanager
+    def _on_stream(self, torch, device):
+        """Around a call that works on torch memory: nothing when torch's current stream IS the handle's stream (everything is ordered already);
+        otherwise torch's stream is waited for before the call and the handle's stream after it, also when the call raises."""
         same = torch.cuda.current_stream(device).cuda_stream == self.stream()
         if not same:
             torch.cuda.current_stream(device).synchronize()
-        return same
+        try:
+            yield
+        finally:
+            if not same:
+                self.sync()
 
-    def _torch_leave(self, same: bool) -> None:
-        if not same:
-            self.sync()
+    @staticmethod
+    def _rows_tensor(t, row_bytes: int, what: str) -> None:
+        """`what` is raised unless t is a contiguous two-dimensional CUDA tensor with rows of row_bytes bytes"""
+        if not PathTracer._is_torch(t) or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.shape[1] * t.element_size() != row_bytes:
+            raise AmberError(what)
 
     def resolve(self, n_samples: int, format: int = RESOLVE_RGB8, mirror: bool = False, out=None):
         """amber_hip_pt_resolve: the band's sums divided by n_samples (RESOLVE_MEAN_F32: float32, 3 channels) or taken through Filmic + Gamma 2.2 to
@@ -861,9 +867,8 @@ class PathTracer:
         dtype = torch.float32 if format == RESOLVE_MEAN_F32 else torch.uint8
         if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or out.numel() != rows * width * channels:
             raise AmberError(f"{what}: out must be a contiguous {dtype} tensor of {rows} x {width} x {channels} elements on the handle's device")
-        same = self._torch_enter(torch, out.device)
-        _check(entry(*head, format, out.data_ptr(), out.numel() * out.element_size(), flags))
-        self._torch_leave(same)
+        with self._on_stream(torch, out.device):
+            _check(entry(*head, format, out.data_ptr(), out.numel() * out.element_size(), flags))
         return out
 
     # ---- batch moments and the variance-guided filter ------------------------------------------
@@ -1004,13 +1009,9 @@ class PathTracer:
             return out[: d["n_written"]], d
         if self._is_torch(out):
             import torch
-            if not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] * out.element_size() != 64:
-                raise AmberError("lt_trace_photons: out must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
-            same = self._torch_enter(torch, out.device)
-            try:
+            self._rows_tensor(out, 64, "lt_trace_photons: out must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
+            with self._on_stream(torch, out.device):
                 d = call(out.data_ptr() if out.shape[0] else None, out.shape[0], 0)
-            finally:
-                self._torch_leave(same)
             return out[: d["n_written"]], d
         ptr, capacity = out
         d = call(ptr, capacity, 0)
@@ -1037,13 +1038,9 @@ class PathTracer:
             return call(rec.ctypes.data if len(rec) else None, len(rec), PHOTONS_HOST)
         if self._is_torch(photons):
             import torch
-            if not photons.is_cuda or not photons.is_contiguous() or photons.dim() != 2 or photons.shape[1] * photons.element_size() != 64:
-                raise AmberError("pm_build: photons must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
-            same = self._torch_enter(torch, photons.device)
-            try:
+            self._rows_tensor(photons, 64, "pm_build: photons must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
+            with self._on_stream(torch, photons.device):
                 return call(photons.data_ptr() if photons.shape[0] else None, photons.shape[0], 0)
-            finally:
-                self._torch_leave(same)
         ptr, n = photons
         return call(ptr, n, 0)
 
@@ -1058,18 +1055,15 @@ class PathTracer:
         flags = PM_RAW_SUM if raw else 0
         if self._is_torch(queries):
             import torch
-            if not queries.is_cuda or not queries.is_contiguous() or queries.dim() != 2 or queries.shape[1] * queries.element_size() != 64:
-                raise AmberError("pm_gather: queries must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
+            self._rows_tensor(queries, 64, "pm_gather: queries must be a contiguous torch tensor on the handle's device with rows of 64 bytes")
             n = queries.shape[0]
             if out is None:
                 out = torch.empty((n, 8), dtype=torch.float32, device=queries.device)
-            elif not self._is_torch(out) or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[0] != n or out.shape[1] * out.element_size() != 32:
-                raise AmberError("pm_gather: out must be a contiguous torch tensor on the handle's device with a row of 32 bytes per query")
-            same = self._torch_enter(torch, queries.device)
-            try:
+            else:
+                self._rows_tensor(out if self._is_torch(out) and out.shape[:1] == (n,) else None, 32,
+                                  "pm_gather: out must be a contiguous torch tensor on the handle's device with a row of 32 bytes per query")
+            with self._on_stream(torch, queries.device):
                 _check(lib.amber_hip_pm_gather(self._h, n, queries.data_ptr() if n else None, out.data_ptr() if n else None, k, flags))
-            finally:
-                self._torch_leave(same)
             return out
         q = np.ascontiguousarray(queries, GATHER_QUERY_DTYPE).reshape(-1)
         if out is None:

@@ -93,6 +93,16 @@ int LaunchLabRecords(amber_hip_pt* h, uint32_t n, uint32_t n_pixels, float* targ
   return FinishPathLaunch(h, 0u, n, n_pixels, target, producer, false);
 }
 
+// The stage hooks (amber_hip_kat_*_stage_ms): the first call switches the stage's clock on; every call reports the sums of the clock's intervals
+// since the call before (a null pointer: not asked for, or not a stage) and zeroes them.
+template <int kN>
+int StageMs(const char* name, amber_hip_pt* h, StageClock<kN>* clock, double* const (&out)[kN - 1]) { return Guarded(name, [&]() -> int {
+  if (!h) return Fail(AMBER_EINVAL, "null handle");
+  clock->on = true;
+  for (int i = 0; i < kN - 1; i++) { if (out[i]) *out[i] = clock->ms[i]; clock->ms[i] = 0; }
+  return AMBER_OK;
+}); }
+
 }  // namespace
 
 extern "C" {
@@ -487,35 +497,15 @@ int amber_hip_kat_scout_flags(amber_hip_pt* h, uint32_t first_sample, uint32_t n
   return AMBER_OK;
 }); }
 
-int amber_hip_kat_lt_stage_ms(amber_hip_pt* h, double* sort_ms, double* sum_ms) { return Guarded("amber_hip_kat_lt_stage_ms", [&]() -> int {
-  if (!h) return Fail(AMBER_EINVAL, "null handle");
-  h->lt.stage_timing = true;
-  if (sort_ms) *sort_ms = h->lt.sort_ms;
-  if (sum_ms) *sum_ms = h->lt.sum_ms;
-  h->lt.sort_ms = h->lt.sum_ms = 0;
-  return AMBER_OK;
-}); }
-
-int amber_hip_kat_photon_stage_ms(amber_hip_pt* h, double* trace_ms, double* sort_ms, double* gather_ms) { return Guarded("amber_hip_kat_photon_stage_ms", [&]() -> int {
-  if (!h) return Fail(AMBER_EINVAL, "null handle");
-  PhotonBufs& s = h->photons;
-  s.stage_timing = true;
-  if (trace_ms) *trace_ms = s.trace_ms;
-  if (sort_ms) *sort_ms = s.sort_ms;
-  if (gather_ms) *gather_ms = s.gather_ms;
-  s.trace_ms = s.sort_ms = s.gather_ms = 0;
-  return AMBER_OK;
-}); }
-
-int amber_hip_kat_pm_stage_ms(amber_hip_pt* h, double* build_ms, double* gather_ms) { return Guarded("amber_hip_kat_pm_stage_ms", [&]() -> int {
-  if (!h) return Fail(AMBER_EINVAL, "null handle");
-  PhotonMapBufs& m = h->pm;
-  m.stage_timing = true;
-  if (build_ms) *build_ms = m.build_ms;
-  if (gather_ms) *gather_ms = m.gather_ms;
-  m.build_ms = m.gather_ms = 0;
-  return AMBER_OK;
-}); }
+int amber_hip_kat_lt_stage_ms(amber_hip_pt* h, double* sort_ms, double* sum_ms) {
+  return StageMs("amber_hip_kat_lt_stage_ms", h, h ? &h->lt.clock : nullptr, {sort_ms, sum_ms});
+}
+int amber_hip_kat_photon_stage_ms(amber_hip_pt* h, double* trace_ms, double* sort_ms, double* gather_ms) {
+  return StageMs("amber_hip_kat_photon_stage_ms", h, h ? &h->photons.clock : nullptr, {trace_ms, nullptr, sort_ms, gather_ms});   // (between trace and sort the host reads the counters)
+}
+int amber_hip_kat_pm_stage_ms(amber_hip_pt* h, double* build_ms, double* gather_ms) {
+  return StageMs("amber_hip_kat_pm_stage_ms", h, h ? &h->pm.clock : nullptr, {build_ms, gather_ms});
+}
 
 int amber_hip_kat_bsdf(amber_hip_pt* h, uint32_t n, const int32_t* object, const float* normal, const float* dir_out, const float* dir_in, float* rgb_out) {
   return Guarded("amber_hip_kat_bsdf", [&]() -> int {

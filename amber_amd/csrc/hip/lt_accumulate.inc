@@ -81,12 +81,6 @@ __global__ void __launch_bounds__(256) lt_sum_kernel(const unsigned long long* _
   if (best > *reinterpret_cast<volatile unsigned int*>(longest)) atomicMax(longest, best);   // (a counter of the info struct, not the framebuffer)
 }
 
-uint32_t BitsFor(uint32_t below) {            // bits that hold every value < below
-  uint32_t bits = 0;
-  while (bits < 32u && (below - 1u) >> bits) bits++;
-  return below > 1u ? bits : 1u;
-}
-
 int EnsureLtSplats(amber_hip_pt* h, uint32_t capacity) {
   LtAccumBufs& s = h->lt;
   if (s.capacity < AMBER_LT_SPLAT_CAPACITY0) s.capacity = AMBER_LT_SPLAT_CAPACITY0;
@@ -101,69 +95,45 @@ int EnsureLtSplats(amber_hip_pt* h, uint32_t capacity) {
 // the handle's stream; the buffers may grow first, which waits for the stream.
 int LtAccumulate(amber_hip_pt* h, uint32_t n, uint32_t path_bits) {
   LtAccumBufs& s = h->lt;
+  IndexSortBufs& sort = h->sort;
   const uint32_t n_pixels = h->scene.sensor.w * h->scene.sensor.h;
   const hipStream_t st = h->stream;
-  for (int k = 0; k < 2; k++) {
-    AMBER_TRY(Grow(h, s.key[k], n, "splat keys"));
-    AMBER_TRY(Grow(h, s.index[k], n, "splat order"));
-  }
-  AMBER_TRY(Grow(h, s.value, n, "sorted splats"));
   // (path, bounce): bounce has no bound (max_depth == 0), all its 32 bits count; (pixel, pass): pass is any 32-bit value, pixel < n_pixels
-  const unsigned int path_end = 32u + path_bits, pixel_end = 32u + BitsFor(n_pixels);
-  size_t bytes_a = 0, bytes_b = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes_a, s.key[0].p, s.key[1].p, s.index[0].p, s.index[1].p, n, 0u, path_end, st));
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes_b, s.key[0].p, s.key[1].p, s.index[1].p, s.index[0].p, n, 0u, pixel_end, st));
-  AMBER_TRY(Grow(h, s.temp, std::max(bytes_a, bytes_b), "sort scratch"));
+  AMBER_TRY(sort.Prepare(h, n, 32u + path_bits, 32u + BitsFor(n_pixels), "splat keys", "splat order"));
+  AMBER_TRY(Grow(h, s.value, n, "sorted splats"));
   const dim3 grid((n + 255u) / 256u), wg(256);
-#ifdef AMBER_LAB
-  if (s.stage_timing) {
-    for (Event& e : s.ev) if (!e.v) HIP_TRY(hipEventCreate(&e.v));
-    HIP_TRY(hipEventRecord(s.ev[0].v, st));
-  }
-#endif
-  hipLaunchKernelGGL(lt_key_path_kernel, grid, wg, 0, st, h->d_splats.p, n, s.key[0].p, s.index[0].p);
+  AMBER_TRY(s.clock.Mark(0, st));
+  hipLaunchKernelGGL(lt_key_path_kernel, grid, wg, 0, st, h->d_splats.p, n, sort.keys(), sort.order());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rocprim::radix_sort_pairs(s.temp.p, bytes_a, s.key[0].p, s.key[1].p, s.index[0].p, s.index[1].p, n, 0u, path_end, st));
-  hipLaunchKernelGGL(lt_key_pixel_kernel, grid, wg, 0, st, h->d_splats.p, s.index[1].p, n, s.key[0].p);
+  AMBER_TRY(sort.Pass(0));
+  hipLaunchKernelGGL(lt_key_pixel_kernel, grid, wg, 0, st, h->d_splats.p, sort.order(), n, sort.keys());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rocprim::radix_sort_pairs(s.temp.p, bytes_b, s.key[0].p, s.key[1].p, s.index[1].p, s.index[0].p, n, 0u, pixel_end, st));   // stable: ties stay in (path, bounce) order
-  hipLaunchKernelGGL(lt_gather_kernel, grid, wg, 0, st, h->d_splats.p, s.index[0].p, n, s.value.p);
+  AMBER_TRY(sort.Pass(1));
+  hipLaunchKernelGGL(lt_gather_kernel, grid, wg, 0, st, h->d_splats.p, sort.order(), n, s.value.p);
   HIP_TRY(hipGetLastError());
-#ifdef AMBER_LAB
-  if (s.stage_timing) HIP_TRY(hipEventRecord(s.ev[1].v, st));
-#endif
-  hipLaunchKernelGGL(lt_sum_kernel, grid, wg, 0, st, s.key[1].p, s.value.p, n, n_pixels, h->d_fb.p, s.longest.p);
+  AMBER_TRY(s.clock.Mark(1, st));
+  hipLaunchKernelGGL(lt_sum_kernel, grid, wg, 0, st, sort.sorted_keys(), s.value.p, n, n_pixels, h->d_fb.p, s.longest.p);
   HIP_TRY(hipGetLastError());
-#ifdef AMBER_LAB
-  if (s.stage_timing) {
-    HIP_TRY(hipEventRecord(s.ev[2].v, st));
-    HIP_TRY(hipEventSynchronize(s.ev[2].v));
-    float a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&a, s.ev[0].v, s.ev[1].v)); HIP_TRY(hipEventElapsedTime(&b, s.ev[1].v, s.ev[2].v));
-    s.sort_ms += a; s.sum_ms += b;
-  }
-#endif
-  return AMBER_OK;
+  AMBER_TRY(s.clock.Mark(2, st));
+  return s.clock.Lap(0, 2);
 }
 
 // A handle whose framebuffer is the whole frame: light paths land anywhere in it
 bool WholeFrame(const amber_hip_pt* h) { return h->row_begin == 0u && h->row_end == h->scene.sensor.h && h->stripe_period == 0u && h->stripe_rows == 0u; }
 
 int LtRenderPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, AmberLtPassInfo* info) {
-  const std::string name = "amber_hip_lt_render_pass";
+  const std::string prefix = "amber_hip_lt_render_pass: ";
   if (info) *info = AmberLtPassInfo{};
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, name + ": sample index overflow");
-  if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, name + ": light tracing runs on the work-queue kernel (engine auto, list, two_phase or bvh)");
-  if (h->lights_stale) return Fail(AMBER_EINVAL, name + ": lights are stale after amber_hip_pt_update_objects: re-create the handle");
-  if (!WholeFrame(h)) return Fail(AMBER_EINVAL, name + ": the handle renders a band or stripes of the frame; light paths land anywhere in it (use amber_hip_lt_trace_range and merge on the host)");
-  if (n_samples == 0 || h->scene.n_lights == 0) return AMBER_OK;
+  if (!h) return Fail(AMBER_EINVAL, prefix + "null handle");
+  const uint32_t n_paths = h->scene.sensor.w * h->scene.sensor.h;
+  AMBER_TRY(LtCheck(h, prefix, "OWS", first_sample, n_samples, 0u, n_paths));
+  if (!WholeFrame(h)) return Fail(AMBER_EINVAL, prefix + "the handle renders a band or stripes of the frame; light paths land anywhere in it (use amber_hip_lt_trace_range and merge on the host)");
+  if (LtNothingToDo(h, n_samples, n_paths)) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
   AMBER_TRY(ResolvePending(h));   // the order of the sums: a path-tracing pass in flight must stand first
   AMBER_TRY(EnsureLtSplats(h, 0u));
   LtAccumBufs& s = h->lt;
   HIP_TRY(hipMemsetAsync(s.longest.p, 0, sizeof(unsigned int), h->stream));
-  const uint32_t n_paths = h->scene.sensor.w * h->scene.sensor.h;
   AmberLtPassInfo total{};
   unsigned long long rays_begin = 0, rays_kept = 0;
   bool have_begin = false, repeated = false;
@@ -171,17 +141,8 @@ int LtRenderPass(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, Amb
                                  [&](uint32_t, uint32_t, unsigned int produced, unsigned long long rays_before, unsigned long long rays_now, bool* again) -> int {
     if (!have_begin) { rays_begin = rays_kept = rays_before; have_begin = true; }
     total.n_launches++;
-    if (produced > s.capacity) {
-      // out of slots: nothing of this launch reaches the framebuffer, the ray counter goes back, the buffer grows to what the launch reported
-      // and the (deterministic) launch runs once more
-      if (repeated) return Fail(AMBER_EHIP, name + ": a repeated launch produced more records than it reported the first time");
-      if (produced > 0x7fffffffu) return Fail(AMBER_ENOMEM, name + ": more than 2^31 records in one launch");
-      HIP_TRY(hipMemcpyAsync(h->d_rays, &rays_kept, sizeof rays_kept, hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      AMBER_TRY(EnsureLtSplats(h, produced));
-      repeated = true; total.n_repeats++; *again = true;
-      return AMBER_OK;
-    }
+    // out of slots: nothing of this launch reaches the framebuffer
+    if (produced > s.capacity) return RepeatOutgrownLaunch(h, prefix, produced, h->d_rays.p, rays_kept, EnsureLtSplats, &repeated, &total.n_repeats, again);
     repeated = false;
     rays_kept = rays_now;
     total.n_splats += produced;

@@ -7,10 +7,10 @@
 // lt_accumulate.inc takes splats to the framebuffer:
 //   1. order      an index permutation sorted by (sample, path, bounce): two stable radix sorts (rocPRIM), first by bounce (as many bits as
 //                 max_depth can set; all 32 when it is 0), then by (sample, path) relative to the launch, packed into the bits that the launch's
-//                 pass count and the call's path range can set.  The scratch is lt_accumulate.inc's (LtAccumBufs: keys, permutations, rocPRIM's).
+//                 pass count and the call's path range can set.  The sort is the handle's (IndexSortBufs: keys, permutations, rocPRIM's scratch).
 //   2. gather     the records into `out` at the running offset, four lanes per record, 16 bytes each: the records move once.
 // Launches run in pass order, so their concatenation is the global order.  The key names a record completely: the output does not depend on the
-// arrival order.  A launch that runs out of staging slots is repeated once with the buffer it asked for (the protocol of LtRenderPass).
+// arrival order.  A launch that runs out of staging slots is repeated once with the buffer it asked for (RepeatOutgrownLaunch, as in LtRenderPass).
 
 namespace {
 
@@ -57,67 +57,42 @@ int EnsurePhotonStaging(amber_hip_pt* h, uint32_t capacity) {
 // order to dst (device, 16-byte aligned).  Enqueued on the handle's stream; the scratch may grow first, which waits for the stream.
 int PhotonOrder(amber_hip_pt* h, uint32_t n, uint32_t first_sample, uint32_t n_launch_samples, uint32_t path_begin, uint32_t n_paths, float4* dst) {
   PhotonBufs& s = h->photons;
-  LtAccumBufs& k = h->lt;
+  IndexSortBufs& sort = h->sort;
   const hipStream_t st = h->stream;
-  for (int b = 0; b < 2; b++) {
-    AMBER_TRY(Grow(h, k.key[b], n, "photon keys"));
-    AMBER_TRY(Grow(h, k.index[b], n, "photon order"));
-  }
   const uint32_t max_depth = h->scene.max_depth;
   const unsigned int bounce_bits = max_depth == 0u || max_depth == 0xffffffffu ? 32u : BitsFor(max_depth + 1u);   // 1 <= bounce <= max_depth
   const uint32_t path_bits = BitsFor(n_paths);
-  const unsigned int path_end = path_bits + BitsFor(n_launch_samples);
-  size_t bytes_a = 0, bytes_b = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes_a, k.key[0].p, k.key[1].p, k.index[0].p, k.index[1].p, n, 0u, bounce_bits, st));
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes_b, k.key[0].p, k.key[1].p, k.index[1].p, k.index[0].p, n, 0u, path_end, st));
-  AMBER_TRY(Grow(h, k.temp, std::max(bytes_a, bytes_b), "sort scratch"));
+  AMBER_TRY(sort.Prepare(h, n, bounce_bits, path_bits + BitsFor(n_launch_samples), "photon keys", "photon order"));
   const dim3 grid((n + 255u) / 256u), wg(256);
-#ifdef AMBER_LAB
-  if (s.stage_timing) HIP_TRY(hipEventRecord(s.ev[2].v, st));           // (ev[0], ev[1]: around the trace kernel, LtTraceLaunches)
-#endif
-  hipLaunchKernelGGL(photon_key_bounce_kernel, grid, wg, 0, st, s.staging.p, n, k.key[0].p, k.index[0].p);
+  AMBER_TRY(s.clock.Mark(2, st));                                       // (events 0, 1: around the trace kernel, LtTraceLaunches)
+  hipLaunchKernelGGL(photon_key_bounce_kernel, grid, wg, 0, st, s.staging.p, n, sort.keys(), sort.order());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rocprim::radix_sort_pairs(k.temp.p, bytes_a, k.key[0].p, k.key[1].p, k.index[0].p, k.index[1].p, n, 0u, bounce_bits, st));
-  hipLaunchKernelGGL(photon_key_path_kernel, grid, wg, 0, st, s.staging.p, k.index[1].p, n, first_sample, path_begin, path_bits, k.key[0].p);
+  AMBER_TRY(sort.Pass(0));
+  hipLaunchKernelGGL(photon_key_path_kernel, grid, wg, 0, st, s.staging.p, sort.order(), n, first_sample, path_begin, path_bits, sort.keys());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rocprim::radix_sort_pairs(k.temp.p, bytes_b, k.key[0].p, k.key[1].p, k.index[1].p, k.index[0].p, n, 0u, path_end, st));   // stable: ties stay in bounce order
-#ifdef AMBER_LAB
-  if (s.stage_timing) HIP_TRY(hipEventRecord(s.ev[3].v, st));
-#endif
-  hipLaunchKernelGGL(photon_gather_kernel, dim3(static_cast<uint32_t>((static_cast<uint64_t>(n) * 4u + 255u) / 256u)), wg, 0, st, s.staging.p, k.index[0].p, n, dst);
+  AMBER_TRY(sort.Pass(1));
+  AMBER_TRY(s.clock.Mark(3, st));
+  hipLaunchKernelGGL(photon_gather_kernel, dim3(static_cast<uint32_t>((static_cast<uint64_t>(n) * 4u + 255u) / 256u)), wg, 0, st, s.staging.p, sort.order(), n, dst);
   HIP_TRY(hipGetLastError());
-#ifdef AMBER_LAB
-  if (s.stage_timing) {
-    HIP_TRY(hipEventRecord(s.ev[4].v, st));
-    HIP_TRY(hipEventSynchronize(s.ev[4].v));
-    float a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&a, s.ev[2].v, s.ev[3].v)); HIP_TRY(hipEventElapsedTime(&b, s.ev[3].v, s.ev[4].v));
-    s.sort_ms += a; s.gather_ms += b;
-  }
-#endif
-  return AMBER_OK;
+  AMBER_TRY(s.clock.Mark(4, st));
+  return s.clock.Lap(2, 4);
 }
 
 int TracePhotons(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end, uint32_t surfaces,
                  AmberPhoton* out, uint64_t capacity, AmberPhotonInfo* info, uint32_t flags) {
-  const std::string name = "amber_hip_lt_trace_photons";
+  const std::string prefix = "amber_hip_lt_trace_photons: ";
   if (info) *info = AmberPhotonInfo{};
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, name + ": sample index overflow");
-  const uint32_t all_paths = h->scene.sensor.w * h->scene.sensor.h;          // image.Size() light paths per pass
-  if (path_begin > path_end || path_end > all_paths) return Fail(AMBER_EINVAL, name + ": bad light-path range");
-  if (surfaces == 0u || (surfaces & ~static_cast<uint32_t>(AMBER_PHOTON_ALL))) return Fail(AMBER_EINVAL, name + ": surfaces must be a non-empty set of AMBER_PHOTON_* bits");
-  if (flags & ~static_cast<uint32_t>(AMBER_PHOTONS_HOST)) return Fail(AMBER_EINVAL, name + ": unknown flag bits");
-  if (!out && capacity) return Fail(AMBER_EINVAL, name + ": null output pointer with a capacity");
+  if (!h) return Fail(AMBER_EINVAL, prefix + "null handle");
+  AMBER_TRY(LtCheck(h, prefix, "OP", first_sample, n_samples, path_begin, path_end));
+  if (surfaces == 0u || (surfaces & ~static_cast<uint32_t>(AMBER_PHOTON_ALL))) return Fail(AMBER_EINVAL, prefix + "surfaces must be a non-empty set of AMBER_PHOTON_* bits");
+  if (flags & ~static_cast<uint32_t>(AMBER_PHOTONS_HOST)) return Fail(AMBER_EINVAL, prefix + "unknown flag bits");
+  if (!out && capacity) return Fail(AMBER_EINVAL, prefix + "null output pointer with a capacity");
   const bool host = (flags & AMBER_PHOTONS_HOST) != 0u;
-  if (!host && (reinterpret_cast<uintptr_t>(out) & 15u)) return Fail(AMBER_EINVAL, name + ": the device pointer must be 16-byte aligned");
-  if (h->lights_stale) return Fail(AMBER_EINVAL, name + ": lights are stale after amber_hip_pt_update_objects: re-create the handle");
-  if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, name + ": light tracing runs on the work-queue kernel (engine auto, list, two_phase or bvh)");
-#if AMBER_BVH_WIDE
-  return Fail(AMBER_EINVAL, name + ": not part of an AMBER_BVH_WIDE measurement build");
-#endif
+  if (!host && (reinterpret_cast<uintptr_t>(out) & 15u)) return Fail(AMBER_EINVAL, prefix + "the device pointer must be 16-byte aligned");
+  AMBER_TRY(LtCheck(h, prefix, "SW", first_sample, n_samples, path_begin, path_end));
+  AMBER_TRY(RefuseWideBuild(prefix));
   const uint32_t n_paths = path_end - path_begin;
-  if (n_samples == 0 || n_paths == 0 || h->scene.n_lights == 0) return AMBER_OK;
+  if (LtNothingToDo(h, n_samples, n_paths)) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
   AMBER_TRY(ResolvePending(h));   // (the work-queue head is shared with the render launches: a pass in flight that may have to be repeated stands first)
   AMBER_TRY(EnsurePhotonStaging(h, 0u));
@@ -129,30 +104,15 @@ int TracePhotons(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uin
   bool fits = true, repeated = false;
   unsigned long long rays_kept = 0;
   LtSink<float4> sink{s.staging, s.count.p, s.rays.p, surfaces};
-#ifdef AMBER_LAB
-  if (s.stage_timing) {
-    for (Event& e : s.ev) if (!e.v) HIP_TRY(hipEventCreate(&e.v));
-    sink.ev_begin = s.ev[0].v; sink.ev_end = s.ev[1].v;
-  }
-#endif
+  AMBER_TRY(s.clock.Get(0, &sink.ev_begin));
+  AMBER_TRY(s.clock.Get(1, &sink.ev_end));
   const int rc = LtTraceLaunches(h, first_sample, n_samples, path_begin, n_paths, false, s.capacity, sink,
                                  [&](uint32_t first, uint32_t n, unsigned int produced, unsigned long long, unsigned long long rays_now, bool* again) -> int {
     total.n_launches++;
-#ifdef AMBER_LAB
-    if (s.stage_timing) { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, s.ev[0].v, s.ev[1].v)); s.trace_ms += ms; }   // (the launch has been waited for)
-#endif
+    AMBER_TRY(s.clock.Lap(0, 1));                          // (the launch has been waited for)
     const bool wanted = !counting && fits && total.n_photons + produced <= capacity;     // the records of this launch have a place in `out`
-    if (wanted && produced > s.capacity) {
-      // out of staging slots: nothing of this launch reaches `out`, the call's ray counter goes back, the buffer grows to what the launch reported
-      // and the (deterministic) launch runs once more
-      if (repeated) return Fail(AMBER_EHIP, name + ": a repeated launch produced more records than it reported the first time");
-      if (produced > 0x7fffffffu) return Fail(AMBER_ENOMEM, name + ": more than 2^31 records in one launch");
-      HIP_TRY(hipMemcpyAsync(s.rays.p, &rays_kept, sizeof rays_kept, hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      AMBER_TRY(EnsurePhotonStaging(h, produced));
-      repeated = true; total.n_repeats++; *again = true;
-      return AMBER_OK;
-    }
+    // out of staging slots: nothing of this launch reaches `out` (the ray counter is the call's own)
+    if (wanted && produced > s.capacity) return RepeatOutgrownLaunch(h, prefix, produced, s.rays.p, rays_kept, EnsurePhotonStaging, &repeated, &total.n_repeats, again);
     repeated = false;
     rays_kept = rays_now;
     if (!wanted) {
@@ -160,9 +120,11 @@ int TracePhotons(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uin
     } else if (produced) {
       if (!host) AMBER_TRY(PhotonOrder(h, produced, first, n, path_begin, n_paths, reinterpret_cast<float4*>(out + written)));
       else {
-        AMBER_TRY(Grow(h, s.sorted, static_cast<size_t>(produced) * 4u, "sorted photons"));
-        AMBER_TRY(PhotonOrder(h, produced, first, n, path_begin, n_paths, s.sorted.p));
-        HIP_TRY(hipMemcpyAsync(out + written, s.sorted.p, static_cast<size_t>(produced) * sizeof(AmberPhoton), hipMemcpyDeviceToHost, h->stream));
+        // through the handle's staging (HostStaging: the copy of the launch before has been waited for; Grow waits before it frees)
+        DevBuf<uint8_t>& sorted = h->staging.out;
+        AMBER_TRY(Grow(h, sorted, static_cast<size_t>(produced) * sizeof(AmberPhoton), "sorted photons"));
+        AMBER_TRY(PhotonOrder(h, produced, first, n, path_begin, n_paths, reinterpret_cast<float4*>(sorted.p)));
+        HIP_TRY(hipMemcpyAsync(out + written, sorted.p, static_cast<size_t>(produced) * sizeof(AmberPhoton), hipMemcpyDeviceToHost, h->stream));
       }
       written += produced;
     }
@@ -174,7 +136,7 @@ int TracePhotons(amber_hip_pt* h, uint32_t first_sample, uint32_t n_samples, uin
   total.n_rays = rays_kept;
   total.n_written = !counting && fits ? written : 0u;
   if (info) *info = total;
-  if (!counting && !fits) return Fail(AMBER_ENOMEM, name + ": photon buffer too small: " + std::to_string(total.n_photons) + " records needed");
+  if (!counting && !fits) return Fail(AMBER_ENOMEM, prefix + "photon buffer too small: " + std::to_string(total.n_photons) + " records needed");
   return AMBER_OK;
 }
 

@@ -141,30 +141,17 @@ int LaunchPathQuery(amber_hip_pt* h, uint64_t n, const float4* d_rays, float4* d
 }
 
 int TracePaths(amber_hip_pt* h, uint64_t n, const AmberPathRay* rays, AmberPathResult* out, uint32_t n_samples, uint32_t max_depth, uint32_t flags) {
-  const char* name = "amber_hip_pt_trace_paths";
-  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
-  if (flags & ~static_cast<uint32_t>(AMBER_RAYS_HOST)) return Fail(AMBER_EINVAL, std::string(name) + ": unknown flag bits");
-  if (n > kQueryMaxRays) return Fail(AMBER_EINVAL, std::string(name) + ": more than 2^31 rays in one call");
-  if (n_samples > kPathMaxSamples) return Fail(AMBER_EINVAL, std::string(name) + ": more than 65536 samples in one call");
+  const std::string prefix = "amber_hip_pt_trace_paths: ";
+  AMBER_TRY(CheckQueryCall(h, prefix, flags, AMBER_RAYS_HOST, n, "rays"));
+  if (n_samples > kPathMaxSamples) return Fail(AMBER_EINVAL, prefix + "more than 65536 samples in one call");
   if (n == 0 || n_samples == 0) return AMBER_OK;
-  if (!rays || !out) return Fail(AMBER_EINVAL, std::string(name) + ": null rays or output pointer");
-#if AMBER_BVH_WIDE
-  return Fail(AMBER_EINVAL, std::string(name) + ": not part of an AMBER_BVH_WIDE measurement build");
-#endif
+  AMBER_TRY(CheckQueryPointers(prefix, rays, out, "rays"));
+  AMBER_TRY(RefuseWideBuild(prefix));
   HIP_TRY(hipSetDevice(h->device));
   if (!(flags & AMBER_RAYS_HOST)) return LaunchPathQuery(h, n, reinterpret_cast<const float4*>(rays), reinterpret_cast<float4*>(out), n_samples, max_depth);
-  // host pointers: through the handle's staging buffers, kPathStageRays at a time, and back before the call returns
-  const uint64_t chunk = n < kPathStageRays ? n : kPathStageRays;
-  AMBER_TRY(Grow(h, h->query.rays, chunk * 4u, "path ray staging"));
-  AMBER_TRY(Grow(h, h->query.out, chunk * sizeof(AmberPathResult), "path ray staging"));
-  for (uint64_t done = 0; done < n; done += chunk) {
-    const uint64_t m = n - done < chunk ? n - done : chunk;
-    HIP_TRY(hipMemcpyAsync(h->query.rays, rays + done, m * sizeof(AmberPathRay), hipMemcpyHostToDevice, h->stream));
-    AMBER_TRY(LaunchPathQuery(h, m, h->query.rays, reinterpret_cast<float4*>(h->query.out.p), n_samples, max_depth));
-    HIP_TRY(hipMemcpyAsync(out + done, h->query.out, m * sizeof(AmberPathResult), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return AMBER_OK;
+  return StagedTrips(h, n, kPathStageRays, sizeof(AmberPathRay), sizeof(AmberPathResult), rays, out, "path ray staging", [&](uint64_t part, uint8_t* d_in, uint8_t* d_out) {
+    return LaunchPathQuery(h, part, reinterpret_cast<const float4*>(d_in), reinterpret_cast<float4*>(d_out), n_samples, max_depth);
+  });
 }
 
 uint64_t HostXorShiftSeed(uint64_t hashed_global_seed, uint32_t pixel, uint32_t sample) {     // dev_math.h's XorShiftSeed on the host

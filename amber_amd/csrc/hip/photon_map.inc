@@ -18,7 +18,7 @@
 //           values that occur and the search ends as soon as a probe counts exactly k; then one sweep sums d2 < T and the first ties in visit order.
 //           No per-lane heap: k = 1024 entries of (d2, index) per lane would be 512 KiB of scratch a wave, sifted through scattered memory, where the
 //           sweeps re-read 16-byte records that the first sweep left in the caches (DESIGN.md, "Photon map").
-// The sort's scratch is lt_accumulate.inc's (LtAccumBufs: keys, permutations, rocPRIM's).
+// The sort is the handle's (IndexSortBufs: keys, permutations, rocPRIM's scratch), as for lt_accumulate.inc and lt_photons.inc.
 
 namespace {
 
@@ -247,14 +247,13 @@ int PmBuild(amber_hip_pt* h, const AmberPhoton* photons, uint64_t n, float cell_
   if (n == 0) { HIP_TRY(hipStreamSynchronize(st)); return finish(); }
   const float4* rec = reinterpret_cast<const float4*>(photons);
   if (host) {
-    AMBER_TRY(Grow(h, m.staged, static_cast<size_t>(n) * 4u, "photon map input"));
-    HIP_TRY(hipMemcpyAsync(m.staged.p, photons, static_cast<size_t>(n) * sizeof(AmberPhoton), hipMemcpyHostToDevice, st));
-    rec = m.staged.p;
+    DevBuf<uint8_t>& staged = h->staging.in;                             // (HostStaging: the build reads it until the wait that ends this call)
+    AMBER_TRY(Grow(h, staged, static_cast<size_t>(n) * sizeof(AmberPhoton), "photon map input"));
+    HIP_TRY(hipMemcpyAsync(staged.p, photons, static_cast<size_t>(n) * sizeof(AmberPhoton), hipMemcpyHostToDevice, st));
+    rec = reinterpret_cast<const float4*>(staged.p);
   }
   if (!m.ctl) HIP_TRY(m.ctl.alloc(PM_CTL_WORDS));
-#ifdef AMBER_LAB
-  if (m.stage_timing) { for (Event& e : m.ev) if (!e.v) HIP_TRY(hipEventCreate(&e.v)); HIP_TRY(hipEventRecord(m.ev[0].v, st)); }
-#endif
+  AMBER_TRY(m.clock.Mark(0, st));
   // ---- 1. bounds, read back
   const uint32_t n32 = static_cast<uint32_t>(n);                        // (n <= 2^31)
   const dim3 wg(256), per_photon(static_cast<uint32_t>((n + 255u) / 256u));
@@ -294,36 +293,25 @@ int PmBuild(amber_hip_pt* h, const AmberPhoton* photons, uint64_t n, float cell_
   info.cell_size = c;
   const uint32_t n_cells = info.dims[0] * info.dims[1] * info.dims[2];
   // ---- 2, 3. keys and the sort
-  LtAccumBufs& k = h->lt;
-  for (int b = 0; b < 2; b++) {
-    AMBER_TRY(Grow(h, k.key[b], n32, "photon map keys"));
-    AMBER_TRY(Grow(h, k.index[b], n32, "photon map order"));
-  }
-  const unsigned int key_bits = BitsFor(n_cells + 1u);                  // the dropped photons' key is n_cells
-  size_t sort_bytes = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, k.key[0].p, k.key[1].p, k.index[0].p, k.index[1].p, n32, 0u, key_bits, st));
-  AMBER_TRY(Grow(h, k.temp, sort_bytes, "sort scratch"));
+  IndexSortBufs& sort = h->sort;
+  AMBER_TRY(sort.Prepare(h, n32, BitsFor(n_cells + 1u), 0u, "photon map keys", "photon map order"));   // the dropped photons' key is n_cells
   m.built = false;                                                      // from here on the previous map is being replaced
   AMBER_TRY(Grow(h, m.start, static_cast<size_t>(n_cells) + 1u, "photon map cells"));
   AMBER_TRY(Grow(h, m.posidx, n_kept, "photon map positions"));
   AMBER_TRY(Grow(h, m.payload, static_cast<size_t>(n_kept) * 2u, "photon map payload"));
   const PmGrid g = PmGridOf(m, info);
-  hipLaunchKernelGGL(pm_key_kernel, per_photon, wg, 0, st, rec, n32, g, k.key[0].p, k.index[0].p);
+  hipLaunchKernelGGL(pm_key_kernel, per_photon, wg, 0, st, rec, n32, g, sort.keys(), sort.order());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rocprim::radix_sort_pairs(k.temp.p, sort_bytes, k.key[0].p, k.key[1].p, k.index[0].p, k.index[1].p, n32, 0u, key_bits, st));
+  AMBER_TRY(sort.Pass(0));
   // ---- 4, 5. cell starts, the packed arrays
-  hipLaunchKernelGGL(pm_start_kernel, dim3((n_cells + 255u) / 256u), wg, 0, st, k.key[1].p, n_kept, n_cells, m.start.p, m.ctl.p);
+  hipLaunchKernelGGL(pm_start_kernel, dim3((n_cells + 255u) / 256u), wg, 0, st, sort.sorted_keys(), n_kept, n_cells, m.start.p, m.ctl.p);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(pm_pack_kernel, dim3((n_kept + 255u) / 256u), wg, 0, st, rec, k.index[1].p, n_kept, m.posidx.p, m.payload.p);
+  hipLaunchKernelGGL(pm_pack_kernel, dim3((n_kept + 255u) / 256u), wg, 0, st, rec, sort.order(), n_kept, m.posidx.p, m.payload.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ctl, m.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, st));
-#ifdef AMBER_LAB
-  if (m.stage_timing) HIP_TRY(hipEventRecord(m.ev[1].v, st));
-#endif
+  AMBER_TRY(m.clock.Mark(1, st));
   HIP_TRY(hipStreamSynchronize(st));                                    // the caller's buffer is free, the cell statistics are here
-#ifdef AMBER_LAB
-  if (m.stage_timing) { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, m.ev[0].v, m.ev[1].v)); m.build_ms += ms; }
-#endif
+  AMBER_TRY(m.clock.Lap(0, 1));
   info.max_cell_count = ctl[PM_CTL_MAX_COUNT];
   return finish();
 }
@@ -342,45 +330,25 @@ int LaunchPmGather(amber_hip_pt* h, uint64_t n, const float4* d_queries, float4*
 }
 
 int PmGather(amber_hip_pt* h, uint64_t n, const AmberGatherQuery* q, AmberGatherResult* out, uint32_t k, uint32_t flags) {
-  const std::string name = "amber_hip_pm_gather";
-  if (!h) return Fail(AMBER_EINVAL, name + ": null handle");
-  if (flags & ~static_cast<uint32_t>(AMBER_RAYS_HOST | AMBER_PM_RAW_SUM)) return Fail(AMBER_EINVAL, name + ": unknown flag bits");
-  if (n > kPmMaxItems) return Fail(AMBER_EINVAL, name + ": more than 2^31 queries in one call");
-  if (k > kPmMaxItems) return Fail(AMBER_EINVAL, name + ": k above 2^31");
-  if (!h->pm.built) return Fail(AMBER_EINVAL, name + ": the handle has no photon map (amber_hip_pm_build comes first; amber_hip_pm_release ends it)");
+  const std::string prefix = "amber_hip_pm_gather: ";
+  AMBER_TRY(CheckQueryCall(h, prefix, flags, AMBER_RAYS_HOST | AMBER_PM_RAW_SUM, n, "queries"));
+  if (k > kPmMaxItems) return Fail(AMBER_EINVAL, prefix + "k above 2^31");
+  if (!h->pm.built) return Fail(AMBER_EINVAL, prefix + "the handle has no photon map (amber_hip_pm_build comes first; amber_hip_pm_release ends it)");
   if (n == 0) return AMBER_OK;
-  if (!q || !out) return Fail(AMBER_EINVAL, name + ": null queries or output pointer");
+  AMBER_TRY(CheckQueryPointers(prefix, q, out, "queries"));
   const bool host = (flags & AMBER_RAYS_HOST) != 0u, raw = (flags & AMBER_PM_RAW_SUM) != 0u;
-  if (!host && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(out)) & 15u)) return Fail(AMBER_EINVAL, name + ": device pointers must be 16-byte aligned");
+  if (!host && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(out)) & 15u)) return Fail(AMBER_EINVAL, prefix + "device pointers must be 16-byte aligned");
   HIP_TRY(hipSetDevice(h->device));
-  PhotonMapBufs& m = h->pm;
-#ifdef AMBER_LAB
-  if (m.stage_timing) { for (Event& e : m.ev) if (!e.v) HIP_TRY(hipEventCreate(&e.v)); }
-  auto timed = [&](auto&& launch) -> int {
-    if (!m.stage_timing) return launch();
-    HIP_TRY(hipEventRecord(m.ev[0].v, h->stream));
-    AMBER_TRY(launch());
-    HIP_TRY(hipEventRecord(m.ev[1].v, h->stream));
-    HIP_TRY(hipEventSynchronize(m.ev[1].v));
-    float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, m.ev[0].v, m.ev[1].v)); m.gather_ms += ms;
-    return AMBER_OK;
+  // one launch; the lab's clock brackets the launch alone (events 1, 2), not the copies of a trip
+  auto launch = [&](uint64_t part, const void* d_q, void* d_out) -> int {
+    StageClock<3>& clock = h->pm.clock;
+    AMBER_TRY(clock.Mark(1, h->stream));
+    AMBER_TRY(LaunchPmGather(h, part, static_cast<const float4*>(d_q), static_cast<float4*>(d_out), k, raw));
+    AMBER_TRY(clock.Mark(2, h->stream));
+    return clock.Lap(1, 2);
   };
-#else
-  auto timed = [&](auto&& launch) -> int { return launch(); };
-#endif
-  if (!host) return timed([&] { return LaunchPmGather(h, n, reinterpret_cast<const float4*>(q), reinterpret_cast<float4*>(out), k, raw); });
-  // host pointers: through the handle's staging buffers, kQueryStageRays at a time, and back before the call returns
-  const uint64_t chunk = n < kQueryStageRays ? n : kQueryStageRays;
-  AMBER_TRY(Grow(h, m.queries, chunk * 4u, "gather staging"));
-  AMBER_TRY(Grow(h, m.results, chunk * 2u, "gather staging"));
-  for (uint64_t done = 0; done < n; done += chunk) {
-    const uint64_t part = n - done < chunk ? n - done : chunk;
-    HIP_TRY(hipMemcpyAsync(m.queries.p, q + done, part * sizeof(AmberGatherQuery), hipMemcpyHostToDevice, h->stream));
-    AMBER_TRY(timed([&] { return LaunchPmGather(h, part, m.queries.p, m.results.p, k, raw); }));
-    HIP_TRY(hipMemcpyAsync(out + done, m.results.p, part * sizeof(AmberGatherResult), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return AMBER_OK;
+  if (!host) return launch(n, q, out);
+  return StagedTrips(h, n, kQueryStageRays, sizeof(AmberGatherQuery), sizeof(AmberGatherResult), q, out, "gather staging", launch);
 }
 
 // Gathers enqueued earlier may still read the map: the stream is waited for, then everything the map and its build own is released
@@ -390,7 +358,8 @@ int PmRelease(amber_hip_pt* h) {
   HIP_TRY(hipStreamSynchronize(h->stream));
   PhotonMapBufs& m = h->pm;
   m.built = false; m.info = AmberPhotonMapInfo{};
-  m.posidx.reset(); m.payload.reset(); m.start.reset(); m.ctl.reset(); m.staged.reset(); m.queries.reset(); m.results.reset();
+  m.posidx.reset(); m.payload.reset(); m.start.reset(); m.ctl.reset();
+  h->staging.in.reset(); h->staging.out.reset();                        // (the stream has been waited for: nobody holds them)
   return AMBER_OK;
 }
 

@@ -13,14 +13,18 @@
 //                          sums, reduce_partials_kernel.
 //   launch_plan.h, pt_launch.inc   the host side of a render launch: the samples and record slots of the next launch as pure functions (launch_plan.h); grids,
 //                          the timed-launch bracket, the loop that splits a pass into launches, the path-granular launch with its repeat (ResolvePending,
-//                          SettlePending), the item launch, light tracing's launches; where a pass adds its sums is an argument (RenderSamples)
+//                          SettlePending), the item launch; where a pass adds its sums is an argument (RenderSamples).  Grow, and behind it the growth of
+//                          the handle's index sort (IndexSortBufs, below).  Light tracing's launches (LtTraceLaunches) with what its three entry points
+//                          share: their argument checks (LtCheck) and the one repeat of a launch that outgrew its record buffer (RepeatOutgrownLaunch).
 //   bvh_device_build.inc   AMBER_PT_FLAG_DEVICE_BUILD: engine BVH's tree built by kernels at create (Morton order, radix-tree hierarchy, the host builder's
 //                          bounds / padding / outward binary16 planes) instead of bvh_build.h's binned-SAH build on the host.
 //   bvh_update.inc         amber_hip_pt_update_objects: new object geometry into a live handle -- records converted and checked by a kernel, then the
 //                          tree made valid again on the device: refitted (any tree, topology kept) or rebuilt (the Morton tree, in place).
 //   ray_query.inc          amber_hip_pt_cast_rays / amber_hip_pt_occluded: the caller's rays through the handle's engine -- engine BVH in a persistent refill
 //                          kernel (closest hit, and the any-hit walk BvhAnyHit), the other engines one thread per ray through ClosestHit<kEngine>;
-//                          LaunchPerItem, the launch of every kernel with a thread per item (its engine front end: dev_closest_hit.h).
+//                          LaunchPerItem, the launch of every kernel with a thread per item (its engine front end: dev_closest_hit.h).  StagedTrips, the
+//                          trips of every call with host pointers through the handle's one pair of staging buffers (HostStaging, below), and the
+//                          argument checks of the three calls that answer the caller's buffers (CheckQueryCall, CheckQueryPointers).
 //   path_query.inc         amber_hip_pt_trace_paths: radiance along the caller's rays -- the bounce loop of the render kernels from (origin, dir, weight, sampler
 //                          state) records, a lane per ray with its samples in sequence, idle lanes refilled per ray from one counter; every engine.
 //   image_stage.inc        what the five files below share, the stage that runs on the band after accumulation: BandPixels, the zero-on-first-use band
@@ -37,7 +41,8 @@
 //   temporal.inc           amber_hip_pt_temporal and its three companions: a per-pixel history of the mean image -- one kernel reprojects the previous history
 //                          through the previous lens, validates it against the previous guide records, blends and writes; then denoise.inc's levels.
 //   lt_accumulate.inc      amber_hip_lt_render_pass: the splat records of a light-tracing launch into the framebuffer in the reference's order -- an index
-//                          permutation sorted by (pixel, pass, path, bounce) with two stable radix sorts, then one thread per pixel run.
+//                          permutation sorted by (pixel, pass, path, bounce) with two stable radix sorts (the handle's IndexSortBufs, which the
+//                          two files below use as well), then one thread per pixel run.
 //   lt_photons.inc         amber_hip_lt_trace_photons: the vertex records of a light-tracing launch (PathShade's second sink) into the caller's buffer in
 //                          (sample, path, bounce) order -- two stable radix sorts of an index permutation, one gather of the 64-byte records.
 //   photon_map.inc         amber_hip_pm_build / amber_hip_pm_gather / amber_hip_pm_release: the handle's photon map -- a uniform grid over the caller's photons (bounds
@@ -50,7 +55,8 @@
 //                          pixel_mask_kernel (candidates of a pixel block's eye rays).
 // LAB BUILD (-DAMBER_LAB -> libamber_hip_lab.so; include/amber_hip_lab.h): the schedulers that were measured and lost but stay provably equal
 // (bvh_pool.inc, wavefront.inc, bvh_stream.inc), the known-answer kernels and entry points the tests use (lab_kernels.inc, lab_api.inc) and the
-// signature instantiations of the product kernels.  libamber_hip.so is built WITHOUT it and exports only the documented ABI.
+// signature instantiations of the product kernels.  libamber_hip.so is built WITHOUT it and exports only the documented ABI.  The lab's stage
+// timing of the three files above is StageClock (below), which the product build compiles to nothing.
 //
 // Replaces: PathTracing<RGB>::Thread::operator() / Render
 //           (/root/reference/src/amber/rendering/algorithm_pt.cc:112-160).
@@ -140,6 +146,39 @@ struct Owned {
 };
 using Event = Owned<hipEvent_t, hipEventDestroy>;
 
+// Lab build: the device time between kN events of a stage, summed per interval (ms[i]: from event i to event i + 1) until the stage's
+// amber_hip_kat_*_stage_ms hook (lab_api.inc: StageMs) reports and zeroes the sums; the hook's first call switches the clock on.  A timed stage waits
+// for its last event.  The product build has no clock: every member is an empty inline function, and Get leaves the event null.
+template <int kN>
+struct StageClock {
+#ifdef AMBER_LAB
+  bool on = false;
+  double ms[kN - 1] = {};
+  Event ev[kN];
+  int Get(int i, hipEvent_t* e) {               // the event itself, for a launch code that records it (LtSink)
+    if (on && !ev[i].v) HIP_TRY(hipEventCreate(&ev[i].v));
+    if (on) *e = ev[i].v;
+    return AMBER_OK;
+  }
+  int Mark(int i, hipStream_t st) {
+    hipEvent_t e = nullptr;
+    AMBER_TRY(Get(i, &e));
+    if (e) HIP_TRY(hipEventRecord(e, st));
+    return AMBER_OK;
+  }
+  int Lap(int first, int last) {                // the intervals between the recorded events first .. last into the sums
+    if (!on) return AMBER_OK;
+    HIP_TRY(hipEventSynchronize(ev[last].v));
+    for (int i = first; i < last; i++) { float t = 0; HIP_TRY(hipEventElapsedTime(&t, ev[i].v, ev[i + 1].v)); ms[i] += t; }
+    return AMBER_OK;
+  }
+#else
+  int Get(int, hipEvent_t*) { return AMBER_OK; }
+  int Mark(int, hipStream_t) { return AMBER_OK; }
+  int Lap(int, int) { return AMBER_OK; }
+#endif
+};
+
 }  // namespace
 
 #include "scene_prep.h"
@@ -161,35 +200,59 @@ struct BvhBuildScratch {
   DevBuf<double> area;                      // update: {sum of the child boxes' areas, the root's area} of the tree before and after
   DevBuf<uint8_t> retired_nodes;            // a node array a rebuild has outgrown: passes enqueued earlier may still read it, released once the stream has been waited for
 };
-// amber_hip_lt_render_pass (lt_accumulate.inc): the scratch of the two sorts and of the ordered sum, grown on first use, kept, released with the handle
-struct LtAccumBufs {
+// Where host pointers pass through device memory: the input and the output of the trips of amber_hip_pt_cast_rays / _occluded / _trace_paths and
+// amber_hip_pm_gather (AMBER_RAYS_HOST; ray_query.inc: StagedTrips), the photons amber_hip_pm_build reads (`in`) and the sorted records of a launch
+// of amber_hip_lt_trace_photons on their way out (`out`) (AMBER_PHOTONS_HOST).  Grown on first use, kept, released by amber_hip_pm_release and with
+// the handle.  ONE pair serves them all because no two users can hold it at once: every user works on the handle's stream and waits for that stream
+// before its call returns, none calls another, and within amber_hip_lt_trace_photons the asynchronous copy out of launch i has been waited for (every
+// launch is, LtTraceLaunches) before launch i + 1's records are sorted into `out` -- and Grow waits for the stream before it frees what it replaces.
+struct HostStaging { DevBuf<uint8_t> in, out; };
+// The stable sort of an index permutation by 64-bit keys, in one or two passes of rocPRIM's radix sort (two: the second key is the major one) --
+// the order of lt_accumulate.inc, lt_photons.inc and photon_map.inc, one at a time on the handle's stream.  Grown on first use, kept.
+//   Prepare    grows everything (which may wait for the stream): before the stage's first kernel and its first timing event
+//   keys()     where the caller's key kernel writes the keys of the next pass -- for the first pass with the identity in order(), for the second
+//              one read through order(), the first pass's result
+//   Pass(i)    sorts; afterwards order() is the permutation and sorted_keys() holds its keys
+struct IndexSortBufs {
   DevBuf<unsigned long long> key[2];        // sort keys, in and out
-  DevBuf<uint32_t> index[2];                // the permutation, in and out
-  DevBuf<float4> value;                     // {rgb, pad} of the records in sorted order
+  DevBuf<uint32_t> index[2];                // the permutation, used ping-pong
   DevBuf<uint8_t> temp;                     // rocPRIM's temporary storage
+  hipStream_t stream = nullptr;             // of the sort in flight (Prepare): the handle's
+  uint32_t n = 0;                           // ... its items
+  unsigned int end_bit[2] = {0, 0};         // ... the bits of its passes' keys
+  size_t temp_bytes[2] = {0, 0};
+  int cur = 0;                              // ... and the slot of `index` that holds the current permutation
+  int Prepare(amber_hip_pt* h, uint32_t n_items, unsigned int end_bit0, unsigned int end_bit1, const char* keys_label, const char* order_label);   // end_bit1 == 0: one pass; defined behind Grow (pt_launch.inc)
+  unsigned long long* keys() const { return key[0].p; }
+  const unsigned long long* sorted_keys() const { return key[1].p; }
+  uint32_t* order() const { return index[cur].p; }
+  int Pass(int i) {
+    HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_bytes[i], key[0].p, key[1].p, index[cur].p, index[cur ^ 1].p, n, 0u, end_bit[i], stream));   // stable: ties stay in the order of the pass before
+    cur ^= 1;
+    return AMBER_OK;
+  }
+};
+uint32_t BitsFor(uint32_t below) {            // bits that hold every value < below
+  uint32_t bits = 0;
+  while (bits < 32u && (below - 1u) >> bits) bits++;
+  return below > 1u ? bits : 1u;
+}
+// amber_hip_lt_render_pass (lt_accumulate.inc): the scratch of the ordered sum, grown on first use, kept, released with the handle
+struct LtAccumBufs {
+  DevBuf<float4> value;                     // {rgb, pad} of the records in sorted order
   DevBuf<unsigned int> longest;             // AmberLtPassInfo.longest_run of the call in flight
   uint32_t capacity = 0;                    // records d_splats holds for that call: AMBER_LT_SPLAT_CAPACITY0, or what a launch made it grow to
-#ifdef AMBER_LAB
-  bool stage_timing = false;                // amber_hip_kat_lt_stage_ms: sort and sum timed with events (waits for the stream after every accumulation)
-  double sort_ms = 0, sum_ms = 0;
-  Event ev[3];
-#endif
+  StageClock<3> clock;                      // amber_hip_kat_lt_stage_ms: sort | sum (a timed accumulation waits for the stream)
 };
-// amber_hip_lt_trace_photons (lt_photons.inc): nothing of it exists before the first call; the sorts borrow LtAccumBufs' keys, permutations and scratch
+// amber_hip_lt_trace_photons (lt_photons.inc): nothing of it exists before the first call
 struct PhotonBufs {
   DevBuf<float4> staging;                   // the records of the launch in flight in arrival order, four float4 each
   uint32_t capacity = 0;                    // records it holds: AMBER_PHOTON_CAPACITY0, or what a launch made it grow to
   DevBuf<unsigned int> count;               // slots claimed by the launch in flight
   DevBuf<unsigned long long> rays;          // casts of the call in flight: a counter of its own, the handle's is not touched
-  DevBuf<float4> sorted;                    // AMBER_PHOTONS_HOST: a launch's records in key order, on their way to the host
-#ifdef AMBER_LAB
-  bool stage_timing = false;                // amber_hip_kat_photon_stage_ms: trace, sort and gather timed with events (waits for the stream after every launch's gather)
-  double trace_ms = 0, sort_ms = 0, gather_ms = 0;
-  Event ev[5];
-#endif
+  StageClock<5> clock;                      // amber_hip_kat_photon_stage_ms: trace | (the host reads the counters) | sort | gather (waits for the stream after every launch's gather)
 };
-// amber_hip_pm_build / amber_hip_pm_gather (photon_map.inc): the handle's one photon map and the scratch of its build, nothing of it before the first
-// build; the sort borrows LtAccumBufs' keys, permutations and scratch
+// amber_hip_pm_build / amber_hip_pm_gather (photon_map.inc): the handle's one photon map and the scratch of its build, nothing of it before the first build
 struct PhotonMapBufs {
   bool built = false;                       // a build has succeeded and amber_hip_pm_release has not been called since
   AmberPhotonMapInfo info{};                // of that build (n_photons - n_dropped photons are in the map)
@@ -197,13 +260,7 @@ struct PhotonMapBufs {
   DevBuf<float4> payload;                   // {dir_out, 0} {weight, 0} in the same order: read for the photons that pass it
   DevBuf<uint32_t> start;                   // cells + 1: the first photon of every cell
   DevBuf<uint32_t> ctl;                     // build: ordered bit patterns of the bounds (3 minima, 3 maxima), the dropped count
-  DevBuf<float4> staged;                    // AMBER_PHOTONS_HOST: the caller's records on their way in
-  DevBuf<float4> queries, results;          // AMBER_RAYS_HOST: staging of a gather, at most kQueryStageRays queries
-#ifdef AMBER_LAB
-  bool stage_timing = false;                // amber_hip_kat_pm_stage_ms: build and gather timed with events (every gather then waits for the stream)
-  double build_ms = 0, gather_ms = 0;
-  Event ev[2];
-#endif
+  StageClock<3> clock;                      // amber_hip_kat_pm_stage_ms: build | gather (events 0, 1 around a build, 1, 2 around a gather's launch, which then waits for the stream)
 };
 // The image stage -- everything that runs on the band after accumulation (image_stage.inc and the five files behind it): its buffers, per band pixel
 struct ImageStageBufs {
@@ -225,8 +282,6 @@ struct RayQueryBufs {
   DevBuf<int32_t> stack;                    // engine BVH: the global levels of the hybrid traversal stack, [level][thread of the largest query grid]
   uint64_t stack_threads = 0;               // ... and the threads it was allocated for
   DevBuf<unsigned int> next;                // engine BVH: the work counter
-  DevBuf<float4> rays;                      // AMBER_RAYS_HOST: staging of the rays and of the results, at most kQueryStageRays rays
-  DevBuf<uint8_t> out;
 };
 // Path-granular launches (pt_launch.inc: LaunchPaths, ResolvePending): bitmap, records in arrival order, measurements in path order, ranks -- and
 // the launch whose record counter the host has not looked at yet
@@ -302,6 +357,8 @@ struct amber_hip_pt : amber_prep::SceneState {   // engine, scene, lens, ...: wh
   DevBuf<uint2> d_ref_stack;                // engine REFERENCE_BVH: the traversal stack of the reference's tree, [level][thread of the largest grid]
   uint64_t ref_stack_threads = 0;           // ... and the threads it was allocated for: no launch that walks that tree may have more (CheckRefStack)
   RayQueryBufs query;                       // amber_hip_pt_cast_rays / amber_hip_pt_occluded
+  HostStaging staging;                      // every call that takes host pointers through device memory
+  IndexSortBufs sort;                       // the sorts of light tracing's accumulation, of the photons and of the photon map
   ImageStageBufs img;                       // resolve, AOVs, the filters, batches
   DevBuf<float> d_fb;
   DevBuf<unsigned long long> d_rays;
@@ -622,13 +679,9 @@ int amber_hip_lt_trace_range(amber_hip_pt* h, uint32_t first_sample, uint32_t n_
   if (!h || !n_out || (capacity && !out)) return Fail(AMBER_EINVAL, "null argument");
   *n_out = 0;
   if (ray_count) *ray_count = 0;
-  if (h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, "light tracing runs on the work-queue kernel (engine auto, list, two_phase or bvh)");
-  if (h->lights_stale) return Fail(AMBER_EINVAL, "lights are stale after amber_hip_pt_update_objects: re-create the handle");
-  if (static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, "sample index overflow");
-  const uint32_t all_paths = h->scene.sensor.w * h->scene.sensor.h;          // image.Size() light paths per pass
-  if (path_begin > path_end || path_end > all_paths) return Fail(AMBER_EINVAL, "bad light-path range");
+  AMBER_TRY(LtCheck(h, "", "WSOP", first_sample, n_samples, path_begin, path_end));
   const uint32_t n_paths = path_end - path_begin;
-  if (n_samples == 0 || n_paths == 0 || h->scene.n_lights == 0) return AMBER_OK;
+  if (LtNothingToDo(h, n_samples, n_paths)) return AMBER_OK;
   HIP_TRY(hipSetDevice(h->device));
   AMBER_TRY(ResolvePending(h));
   const uint32_t dev_capacity = capacity ? capacity : 1u;

@@ -108,6 +108,19 @@ int Grow(amber_hip_pt* h, DevBuf<T>& b, size_t n, const char* what) {
   return AMBER_OK;
 }
 
+// (the labels name the caller's keys and permutation in an out-of-memory message)
+int IndexSortBufs::Prepare(amber_hip_pt* h, uint32_t n_items, unsigned int end_bit0, unsigned int end_bit1, const char* keys_label, const char* order_label) {
+  for (int k = 0; k < 2; k++) {
+    AMBER_TRY(Grow(h, key[k], n_items, keys_label));
+    AMBER_TRY(Grow(h, index[k], n_items, order_label));
+  }
+  stream = h->stream; n = n_items; end_bit[0] = end_bit0; end_bit[1] = end_bit1; cur = 0;
+  temp_bytes[0] = temp_bytes[1] = 0;
+  for (int i = 0; i < (end_bit1 ? 2 : 1); i++)               // (a null pointer: rocPRIM states the temporary storage pass i needs)
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes[i], key[0].p, key[1].p, index[i].p, index[i ^ 1].p, n, 0u, end_bit[i], stream));
+  return Grow(h, temp, std::max(temp_bytes[0], temp_bytes[1]), "sort scratch");
+}
+
 // What every launch of a render kernel states first: the scene, the seed, the handle's band, the samples and their chunks (with the dividers).
 RenderArgs MakeRenderArgs(const amber_hip_pt* h, uint64_t hashed_seed, uint32_t n_pixels, uint32_t first_sample, uint32_t n_samples) {
   RenderArgs a{};
@@ -428,6 +441,33 @@ struct LtSink {
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;          // measurements: recorded around the kernel of every launch
 };
 LtSink<DevSplat> SplatLtSink(const amber_hip_pt* h) { return LtSink<DevSplat>{h->d_splats, h->d_splat_count.p, h->d_rays.p, 0u}; }
+
+// The argument checks the entry points of light tracing share, in the order `order` names them -- 'O' sample overflow, 'P' the light-path range,
+// 'W' engine WAVEFRONT, 'S' stale lights: which message an input gets that fails several of them is part of each entry point's behaviour.
+int LtCheck(const amber_hip_pt* h, const std::string& prefix, const char* order, uint32_t first_sample, uint32_t n_samples, uint32_t path_begin, uint32_t path_end) {
+  for (const char* c = order; *c; c++) {
+    if (*c == 'O' && static_cast<uint64_t>(first_sample) + n_samples > 0xffffffffull) return Fail(AMBER_EINVAL, prefix + "sample index overflow");
+    if (*c == 'P' && (path_begin > path_end || path_end > h->scene.sensor.w * h->scene.sensor.h)) return Fail(AMBER_EINVAL, prefix + "bad light-path range");   // image.Size() light paths per pass
+    if (*c == 'W' && h->engine == AMBER_ENGINE_WAVEFRONT) return Fail(AMBER_EINVAL, prefix + "light tracing runs on the work-queue kernel (engine auto, list, two_phase or bvh)");
+    if (*c == 'S' && h->lights_stale) return Fail(AMBER_EINVAL, prefix + "lights are stale after amber_hip_pt_update_objects: re-create the handle");
+  }
+  return AMBER_OK;
+}
+bool LtNothingToDo(const amber_hip_pt* h, uint32_t n_samples, uint32_t n_paths) { return n_samples == 0 || n_paths == 0 || h->scene.n_lights == 0; }
+
+// A launch of LtTraceLaunches produced more records than its buffer holds.  Nothing of it counts: the sink's ray counter goes back to what the launches
+// before left (rays_kept), the buffer grows to what the launch reported (ensure) and the (deterministic) launch runs once more -- once: `repeated`
+// is the caller's, cleared by every launch that fits.
+int RepeatOutgrownLaunch(amber_hip_pt* h, const std::string& prefix, unsigned int produced, unsigned long long* d_rays, unsigned long long rays_kept,
+                         int (*ensure)(amber_hip_pt*, uint32_t), bool* repeated, uint32_t* n_repeats, bool* again) {
+  if (*repeated) return Fail(AMBER_EHIP, prefix + "a repeated launch produced more records than it reported the first time");
+  if (produced > 0x7fffffffu) return Fail(AMBER_ENOMEM, prefix + "more than 2^31 records in one launch");
+  HIP_TRY(hipMemcpyAsync(d_rays, &rays_kept, sizeof rays_kept, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  AMBER_TRY(ensure(h, produced));
+  *repeated = true; (*n_repeats)++; *again = true;
+  return AMBER_OK;
+}
 
 // The launches of light tracing over the passes [first_sample, first_sample + n_samples) of the light paths [path_begin, path_begin + n_paths): what
 // amber_hip_lt_trace_range, amber_hip_lt_render_pass and amber_hip_lt_trace_photons share.  Each launch leaves its records at sink.records in arrival

@@ -149,6 +149,44 @@ int LaunchPerItem(amber_hip_pt* h, uint64_t n_items, F&& launch) {
   return AMBER_OK;
 }
 
+// AMBER_RAYS_HOST: n items through the handle's staging buffers (HostStaging), at most per_trip of them at a time, and back before the call returns.
+// Per trip launch(part, d_in, d_out) answers `part` records of in_size bytes at d_in with records of out_size bytes at d_out, on the handle's stream.
+// `what` names the staging in an out-of-memory message.
+template <typename F>
+int StagedTrips(amber_hip_pt* h, uint64_t n, uint64_t per_trip, size_t in_size, size_t out_size, const void* in, void* out, const char* what, F&& launch) {
+  HostStaging& s = h->staging;
+  const uint64_t chunk = n < per_trip ? n : per_trip;
+  AMBER_TRY(Grow(h, s.in, chunk * in_size, what));
+  AMBER_TRY(Grow(h, s.out, chunk * out_size, what));
+  for (uint64_t done = 0; done < n; done += chunk) {
+    const uint64_t part = n - done < chunk ? n - done : chunk;
+    HIP_TRY(hipMemcpyAsync(s.in.p, static_cast<const uint8_t*>(in) + done * in_size, part * in_size, hipMemcpyHostToDevice, h->stream));
+    AMBER_TRY(launch(part, s.in.p, s.out.p));
+    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(out) + done * out_size, s.out.p, part * out_size, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  return AMBER_OK;
+}
+
+// The front matter of the calls that answer the caller's buffers (rays, path rays, gather queries): the handle, the flag bits, the count ...
+int CheckQueryCall(const amber_hip_pt* h, const std::string& prefix, uint32_t flags, uint32_t known_flags, uint64_t n, const char* items) {
+  if (!h) return Fail(AMBER_EINVAL, prefix + "null handle");
+  if (flags & ~known_flags) return Fail(AMBER_EINVAL, prefix + "unknown flag bits");
+  if (n > kQueryMaxRays) return Fail(AMBER_EINVAL, prefix + "more than 2^31 " + items + " in one call");
+  return AMBER_OK;
+}
+// ... and, once there is something to do, the two pointers
+int CheckQueryPointers(const std::string& prefix, const void* in, const void* out, const char* items) {
+  if (!in || !out) return Fail(AMBER_EINVAL, prefix + "null " + items + " or output pointer");
+  return AMBER_OK;
+}
+int RefuseWideBuild(const std::string& prefix) {
+#if AMBER_BVH_WIDE
+  return Fail(AMBER_EINVAL, prefix + "not part of an AMBER_BVH_WIDE measurement build");
+#endif
+  return AMBER_OK;
+}
+
 // One launch over n rays in device memory.  Engine BVH's scratch (the global levels of the hybrid stack for the largest grid, the work counter)
 // is allocated by the first query and kept.
 int LaunchRayQuery(amber_hip_pt* h, uint64_t n, const float4* d_rays, void* d_out, bool any_hit) {
@@ -182,29 +220,16 @@ int LaunchRayQuery(amber_hip_pt* h, uint64_t n, const float4* d_rays, void* d_ou
 }
 
 int RayQuery(amber_hip_pt* h, uint64_t n, const AmberRay* rays, void* out, uint32_t flags, bool any_hit, const char* name) {
-  if (!h) return Fail(AMBER_EINVAL, std::string(name) + ": null handle");
-  if (flags & ~static_cast<uint32_t>(AMBER_RAYS_HOST)) return Fail(AMBER_EINVAL, std::string(name) + ": unknown flag bits");
-  if (n > kQueryMaxRays) return Fail(AMBER_EINVAL, std::string(name) + ": more than 2^31 rays in one call");
+  const std::string prefix = std::string(name) + ": ";
+  AMBER_TRY(CheckQueryCall(h, prefix, flags, AMBER_RAYS_HOST, n, "rays"));
   if (n == 0) return AMBER_OK;
-  if (!rays || !out) return Fail(AMBER_EINVAL, std::string(name) + ": null rays or output pointer");
-#if AMBER_BVH_WIDE
-  return Fail(AMBER_EINVAL, std::string(name) + ": not part of an AMBER_BVH_WIDE measurement build");
-#endif
+  AMBER_TRY(CheckQueryPointers(prefix, rays, out, "rays"));
+  AMBER_TRY(RefuseWideBuild(prefix));
   HIP_TRY(hipSetDevice(h->device));
   if (!(flags & AMBER_RAYS_HOST)) return LaunchRayQuery(h, n, reinterpret_cast<const float4*>(rays), out, any_hit);
-  // host pointers: through the handle's staging buffers, kQueryStageRays at a time, and back before the call returns
-  const size_t out_size = any_hit ? 1u : sizeof(AmberRayHit);
-  const uint64_t chunk = n < kQueryStageRays ? n : kQueryStageRays;
-  AMBER_TRY(Grow(h, h->query.rays, chunk * 2u, "ray staging"));
-  AMBER_TRY(Grow(h, h->query.out, chunk * out_size, "ray staging"));
-  for (uint64_t done = 0; done < n; done += chunk) {
-    const uint64_t m = n - done < chunk ? n - done : chunk;
-    HIP_TRY(hipMemcpyAsync(h->query.rays, rays + done, m * sizeof(AmberRay), hipMemcpyHostToDevice, h->stream));
-    AMBER_TRY(LaunchRayQuery(h, m, h->query.rays, h->query.out, any_hit));
-    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(out) + done * out_size, h->query.out, m * out_size, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return AMBER_OK;
+  return StagedTrips(h, n, kQueryStageRays, sizeof(AmberRay), any_hit ? 1u : sizeof(AmberRayHit), rays, out, "ray staging", [&](uint64_t part, uint8_t* d_in, uint8_t* d_out) {
+    return LaunchRayQuery(h, part, reinterpret_cast<const float4*>(d_in), d_out, any_hit);
+  });
 }
 
 }  // namespace

@@ -304,7 +304,8 @@ int  amber_hip_pt_update_lens(amber_hip_pt*, const AmberFlatThinLens* lens, cons
  * new one; read the output after amber_hip_pt_sync, or from work enqueued on amber_hip_pt_stream.  With AMBER_RAYS_HOST both are HOST pointers: the
  * call stages through buffers the handle owns (a million rays at a time) and returns after the copy back.
  * Neither function touches the framebuffer, the ray counter or amber_hip_pt_kernel_time.  Scratch (engine BVH's traversal stacks and work counter,
- * the staging buffers) is allocated by the first query, sized by the launch and not by n, reused by every later query and released by destroy.
+ * the staging buffers) is allocated by the first query, sized by the launch and not by n, reused by every later query and released by destroy (the
+ * staging buffers, which every call that takes host pointers shares, also by amber_hip_pm_release; the next such call allocates them again).
  * n == 0: AMBER_OK.  AMBER_EINVAL: n > 2^31, a NULL pointer with n > 0, unknown flag bits, an AMBER_BVH_WIDE measurement build.  A handle of the lab
  * engine WAVEFRONT answers as engine AUTO does (its closest hit is AUTO's). */
 typedef struct { float origin[3]; float t_max; float dir[3]; uint32_t pad; } AmberRay;      /* 32 bytes: two float4 loads */
