@@ -180,7 +180,8 @@ struct DevScene {
   uint32_t always_mask;        // program slots that are always candidates (disks, cylinders, degenerate triangles)
   uint32_t blade_mask;         // program slots of the aperture blades (primary rays: decided per ray, not per pixel)
   uint32_t n_prog_tris;        // program slots [0, n_prog_tris) are filtered triangles, then spheres, then the rest
-  const DevObject* __restrict__ prog_objects;   // objects in program order, kind |= scene index << 8 (| 0x80: a filtered triangle) (staged to LDS)
+  const DevObject* __restrict__ prog_objects;   // objects in program order, kind |= scene index << 8 (| 0x80: a filtered triangle) (staged to LDS); the 32-object engine's
+                                                // axis-flat program triangles carry AMBER_FLAT_SELF_MARK in their `radius` dword (filter_build.h, "Flat self")
   const DevFilterGroup* __restrict__ groups;    // engine TWO_PHASE_N: n_groups records (null otherwise)
   uint32_t n_groups;                            // 1 for the 32-object engine
   uint32_t n_lds_objects;                       // records of prog_objects (n_objects, or 32 * n_groups)

@@ -418,7 +418,15 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
   if (sc.max_depth && casts >= sc.max_depth) return false;                   // build-side extension (BASELINE config 5)
   o = pos; d = dir_in;                                                       // :155 Ray(pos, UnitVector3) -- no renormalisation
   if (kEngine == ENGINE_TWO_PHASE_N) origin_slot = (lds_objects[h.slot].kind & 0x80u) ? h.slot : -1;      // a filtered triangle of its group (bit 7 of the LDS record)
+#if AMBER_FLAT_SELF
+  // The 32-object engine: o is ResolveHit's pos of the triangle in slot h.slot, formed from that record -- the one fact the flat-self mark stands for
+  // (filter_build.h), so it is set here and nowhere else: the record's mark word (AMBER_FLAT_SELF_MARK or 0) joins the slot, and the pool carries it in
+  // the chunk it stores anyway.  (The primary rounds' 1u << origin_slot, pt_megakernel.inc, sees GenerateEyeRay's slots only: aperture blades, never marked.)
+  else if (kEngine == ENGINE_TWO_PHASE) origin_slot = static_cast<uint32_t>(h.slot) < sc.n_prog_tris ? static_cast<int>(static_cast<uint32_t>(h.slot) | __float_as_uint(lds_objects[h.slot].radius)) : -1;
+  else origin_slot = -1;
+#else
   else origin_slot = (kEngine == ENGINE_TWO_PHASE && static_cast<uint32_t>(h.slot) < sc.n_prog_tris) ? h.slot : -1;
+#endif
   if (kScout) {                                                              // :156 without the quotients and the products: what they can have grown to
     *scout_bound = amber_scout::BounceBound(*scout_bound, __float_as_uint(sw.x), __float_as_uint(sw.y), __float_as_uint(sw.z), __float_as_uint(p_rr));
     return true;

@@ -25,6 +25,14 @@ namespace amber_dev {
 #ifndef AMBER_AXIS_FIRST
 #define AMBER_AXIS_FIRST 1
 #endif
+// 1: the 32-object engine drops the self candidate of a ray that starts on a marked triangle without the self trip's arithmetic (filter_build.h,
+// "Flat self": the proof and the host's classification).  The mark travels in origin_slot itself: PathShade (dev_shading.h), the one place where a ray's
+// origin is ResolveHit's pos of the triangle, ORs the word the host left in the triangle's `radius` dword of the LDS image -- AMBER_FLAT_SELF_MARK, the
+// bit above the 32 slot numbers, or 0 -- into the slot.  0: no record is marked and nothing decodes a mark (the A/B partner: the code before the shortcut).
+#ifndef AMBER_FLAT_SELF
+#define AMBER_FLAT_SELF 1
+#endif
+#define AMBER_FLAT_SELF_MARK 0x20u
 // The Phase-A program one call works through: the whole scene's (the 32-object engine: DevScene's own fields, compile-time `first`) or one group's.
 struct FilterView {
   ConstWords planes, tris, spheres;
@@ -235,8 +243,16 @@ __device__ __forceinline__ void ClosestHitTwoPhaseView(const DevScene& sc, const
   // that carry such a self candidate evaluate just t -- the same operations the full test performs -- in one
   // common trip; "t <= kEPS" means the full test would reject whatever u and v are, so the bit is cleared.
   // Otherwise (t above kEPS, or NaN) the bit stays and the full exact test decides below.
+  // A marked origin (AMBER_FLAT_SELF, the 32-object engine: 32 + slot) has that t known beforehand, +-0 or NaN (filter_build.h): its bit is cleared
+  // here and the lane is no has_self, so a wave none of whose lanes starts on an unmarked triangle skips the trip.  Eye and light rays and
+  // callers' rays carry plain slots and take it as before.
   {
+#if AMBER_FLAT_SELF
+    if (!kMulti) cand &= ~(origin_slot >= 32 ? 1u << (origin_slot & 31) : 0u);
+    const bool has_self = (kMulti ? origin_slot >= 0 : static_cast<uint32_t>(origin_slot) < 32u) && ((cand >> (origin_slot & 31)) & 1u) != 0u;
+#else
     const bool has_self = origin_slot >= 0 && ((cand >> (origin_slot & 31)) & 1u) != 0u;
+#endif
     if (has_self) {
       const DevObject& ob = lds_objects[origin_slot];
       const V3 A = ld3(ob.a), E1 = ld3(ob.e1), E2 = ld3(ob.e2);

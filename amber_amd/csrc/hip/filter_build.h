@@ -56,6 +56,61 @@ inline int AxisSlabClass(const DevPlane& p, const DevTriFilter& f) {
   return -1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Flat self (AMBER_FLAT_SELF, dev_two_phase.h): the self candidate of a bounce ray that leaves an AXIS-FLAT triangle is dropped without arithmetic.
+//
+// CLAIM.  Let a triangle's stored binary32 record (A, E1, E2) have, for some axis c, E1_c and E2_c both +-0, and every component of A, E1 and E2
+// finite with magnitude below 2^40.  Let (u, v) be what IntersectTriangle stored with a hit on it, let pos be what ResolveHit forms from them and this
+// record, and let a ray of ANY direction d start at o = pos.  Then the t of this triangle in that cast -- the self trip's and the full test's are the
+// same expression, Dot(Cross(o - A, E1), E2) / det, det = Dot(Cross(d, E2), E1) -- is +-0 or NaN.  The self trip clears the bit on t <= kEPS (+-0) and
+// leaves a NaN to the full test, whose `!(t <= kEPS) && Closer(t)` refuses +-0 by its first half and NaN by IsFinite: the triangle can never become
+// the hit, and clearing its bit beforehand leaves HitRec as it is.  Every operation below is one binary32 operation rounded to nearest (the
+// translation unit is built with -ffp-contract=off; a fused form of the same products would give the same zeros).  a, b: the two other axes.
+//
+//  1. (u, v).  The hit passed !(u > 1 || u < 0) and the same for v: each is in [0, 1] (-0 and subnormals included) or NaN.
+//  2. NaN u or v.  pos_k = (A_k + u E1_k) + v E2_k, k = x, y, z: a NaN factor makes all three components NaN, so o - A is NaN in every component of
+//     every object's test, every distance of the next cast is NaN and nothing is hit at all -- with or without the bit.  From here on u, v are in [0, 1].
+//  3. The zero products.  u E1_c and v E2_c are a finite number times +-0: +-0.
+//  4. pos_c.  A_c + (+-0) is A_c for A_c != 0, and a zero (+0 unless both are -0) for A_c = +-0; adding the second +-0 repeats that.  pos_c has the
+//     VALUE of A_c; only the sign of a zero can differ -- A_c = -0 gives pos_c = +0 unless both products are -0.
+//  5. T = o - A.  T_c = pos_c - A_c is x - x = +0 for x != 0, and (+-0) - (+-0) = +-0 for the zeros.  T_a and T_b are finite:
+//     |pos_k| <= |A_k| + |E1_k| + |E2_k| < 3 * 2^40 before two roundings, so |T_k| < 2^43.
+//  6. Q = Cross(T, E1).  Q_a = T_b E1_c - T_c E1_b and Q_b = T_c E1_a - T_a E1_c: each product has a +-0 factor and a FINITE one, so it is +-0, and
+//     a difference of zeros is +-0.  Q_c = T_a E1_b - T_b E1_a is finite: |Q_c| < 2 * 2^43 * 2^40 = 2^84.
+//  7. The numerator Dot(Q, E2) = Q_x E2_x + Q_y E2_y + Q_z E2_z.  Q_a E2_a and Q_b E2_b are +-0 times finite, Q_c E2_c is finite times E2_c = +-0:
+//     three zeros, whose sums are +-0.  The numerator is an exact zero of either sign.
+//  8. The sign of zero never matters: +0 and -0 alike satisfy t <= kEPS, and neither is ever stored.
+//  9. det.  +-0 / det is +-0 for det finite and non-zero and for det = +-inf; it is NaN for det = +-0 and for det NaN.  Both outcomes are refused (above).
+// 10. The magnitude bound is what keeps every second factor in 6 and 7 finite: inf * 0 would be NaN, not zero.  With all stored components below 2^40
+//     the largest intermediate is below 2^84 < 2^128, whatever u, v in [0, 1] and whatever d.  (A NaN would be refused as well; the bound lets the
+//     claim, and the host test of it, say "zero".)
+//
+// The premise "o is ResolveHit's pos of this record" holds where PathShade (dev_shading.h) sets origin_slot after o = pos, and only there: eye rays,
+// light rays and callers' rays form their origins otherwise and keep plain slots.  The mark is per record of the LDS image (prog_objects); engine
+// LIST's records, the reference of the tests, are not touched.  tests/cpp/flat_self_check.hip draws the claim at random.
+inline bool FlatSelfTriangle(const DevObject& o) {
+  if ((o.kind & 0xffu) != AMBER_PRIM_TRIANGLE) return false;
+  uint32_t a[3], e1[3], e2[3];
+  std::memcpy(a, o.a, sizeof a); std::memcpy(e1, o.e1, sizeof e1); std::memcpy(e2, o.e2, sizeof e2);
+  bool flat = false;
+  for (int c = 0; c < 3; c++) {
+    flat = flat || ((e1[c] & 0x7fffffffu) == 0u && (e2[c] & 0x7fffffffu) == 0u);                       // +-0 by the bit pattern, sign masked off
+    const uint32_t below = 0x53800000u;                                                                  // 2^40: magnitudes order like their bit patterns; inf and NaN are above
+    if ((a[c] & 0x7fffffffu) >= below || (e1[c] & 0x7fffffffu) >= below || (e2[c] & 0x7fffffffu) >= below) return false;
+  }
+  return flat;
+}
+// The marks of the 32-object engine's LDS image: program slots [0, n_prog_tris) are the filtered triangles; `radius` is a dword no triangle uses.
+inline void MarkFlatSelf(std::vector<DevObject>& prog, uint32_t n_prog_tris) {
+#if AMBER_FLAT_SELF
+  const uint32_t mark = AMBER_FLAT_SELF_MARK;
+  for (size_t k = 0; k < prog.size() && k < n_prog_tris && k < 32; k++)
+    if (FlatSelfTriangle(prog[k])) std::memcpy(&prog[k].radius, &mark, sizeof mark);
+#else
+  (void)prog; (void)n_prog_tris;
+#endif
+}
+
 // `center`: the filter works in coordinates relative to this point (the device subtracts it from the ray origin), so its
 // affine maps see magnitudes of the order of the scene size however far the scene lies from the world origin; in
 // absolute coordinates u = A.P + a0 cancels two large terms and loses the precision the tolerances assume

@@ -247,6 +247,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
               if (kTwoPhase && pixel_mask) {
                 // the candidates of this pixel's beam, plus the ray's own aperture blade (the self trip decides it exactly), plus
                 // every blade when the aperture sample lies on a blade's boundary (only then can a neighbour's exact test see it)
+                // (origin_slot is GenerateEyeRay's here, a plain slot below 32: only PathShade sets the flat-self mark, AMBER_FLAT_SELF)
                 premask = pixel_mask[plocal] | (origin_slot >= 0 ? 1u << origin_slot : 0u) | (near_edge ? AMBER_ARG(cold, scene.blade_mask) : 0u);
               }
             }

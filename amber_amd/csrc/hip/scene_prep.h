@@ -451,6 +451,7 @@ inline PreparedScene PrepareScene(const AmberFlatScene* s, const AmberSensor* se
     for (size_t k = 0; k < fp.order.size(); k++) { prog[base + k] = objs[fp.order[k]]; prog[base + k].kind |= fp.order[k] << 8 | (!more_progs.empty() && k < fp.n_prog_tris ? 0x80u : 0u); }   // (the flag only in the grouped engine's image)
   };
   place(fprog, 0);
+  if (more_progs.empty()) amber_filter::MarkFlatSelf(prog, fprog.n_prog_tris);   // the 32-object engine only: its axis-flat program triangles (filter_build.h, "Flat self")
   if (!more_progs.empty()) {
     auto record = [&](const amber_filter::FilterProgram& fp, size_t plane_first, size_t tri_first, size_t sphere_first) {
       DevFilterGroup g{};
