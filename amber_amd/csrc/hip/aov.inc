@@ -37,15 +37,13 @@ __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? AMBER_QUERY_WAVES
   for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * 256u; base < a.n_pixels; base += static_cast<uint64_t>(gridDim.x) * 256u) {   // uniform over the workgroup
     const uint64_t i = base + threadIdx.x;
     const bool mine = i < a.n_pixels;
-    const uint32_t plocal = static_cast<uint32_t>(ClampToLastItem<uint64_t>(i, a.n_pixels));
-    const uint32_t lrow = Quotient(a.div_width, plocal), px = plocal - lrow * sc.sensor.w;
-    const uint32_t py = FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow);
+    const PathPlace at = PlacePixel(a, static_cast<uint32_t>(ClampToLastItem<uint64_t>(i, a.n_pixels)));
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
     if (mine) { s0 = a.aov[2u * i]; s1 = a.aov[2u * i + 1u]; }
     for (uint32_t k = 0; k < a.n_samples; ++k) {
-      uint64_t rng = XorShiftSeed(a.hashed_seed, px + py * sc.sensor.w, a.first_sample + k);   // Image index x + y*W, as the render kernels seed it
+      uint64_t rng = PathSeed(a, at, k);                // as the render kernels seed it
       V3 o, d; float ew; int origin_slot;
-      GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot);
+      GenerateEyeRay(sc, at.px, at.py, rng, o, d, ew, origin_slot);
       HitRec h;
       if constexpr (kEngine == ENGINE_BVH) {
         ClosestHitBvh<true>(sc, lds.stack, o, d, h);

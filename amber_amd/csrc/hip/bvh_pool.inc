@@ -81,15 +81,13 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
   // wave-uniform (SGPRs)
   uint32_t rhead = 0, rcount = 0, dhead = 0, dcount = 0;            // READY / DONE rings
   uint32_t n_unfilled = kWait;                                      // entries that have not received their first ray yet
-  uint32_t claim_next = 0, claim_end = 0;
-  bool exhausted = false;
+  WaveClaim claim;                                                  // paths claimed from the queue, not yet handed to a lane
   uint32_t rec_next = 0, rec_end = 0, rays_wave = 0;
   // per lane: the ray in flight (or held)
   uint32_t st = LS_FRESH, r = lane;
   V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
-  BvhTrav tr; tr.A = v3(0.f, 0.f, 0.f); tr.b_in = v3(0.f, 0.f, 0.f); tr.b_out = v3(0.f, 0.f, 0.f); tr.neg_slack = 0.f; tr.rot[0] = tr.rot[1] = tr.rot[2] = 0u;
-  tr.cur = AMBER_BVH_DONE; tr.pend = 0; tr.sp = 0; tr.overflow = false;
-  HitRec hit; hit.t = 0.f; hit.u = 0.f; hit.v = 0.f; hit.idx = -1; hit.slot = -1;
+  BvhTrav tr; HitRec hit;
+  BvhIdle(tr, hit);
 #ifdef AMBER_STAMPS
   StampCtx stamp_store{}, stamp_shade{}; StampCtx* stamp_ctx = &stamp_store;      // counters here; PathShade's clocks go to a dummy
 #define AMBER_POOL_SHADE_STAMP_ARG , &stamp_shade
@@ -98,7 +96,6 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
 #define AMBER_POOL_SHADE_STAMP_ARG
 #endif
 #define AMBER_WRAP(x_) ((x_) >= kWait ? (x_) - kWait : (x_))     /* ring index; x_ < 2 kWait */
-#define AMBER_RANK(m_) __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>((m_) >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m_), 0u))
 #define AMBER_F2U(x_) __float_as_uint(x_)
 #define AMBER_U2F(x_) __uint_as_float(x_)
 
@@ -109,7 +106,7 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
       const bool want = fin || st == LS_IDLE;
       const unsigned long long m = __ballot(want);
       if (static_cast<uint32_t>(__popcll(m)) >= AMBER_BVH_POOL_SWAP_MIN && rcount != 0u) {   // wave-uniform
-        const uint32_t rank = AMBER_RANK(m), n_want = static_cast<uint32_t>(__popcll(m));
+        const uint32_t rank = WaveRank(m), n_want = static_cast<uint32_t>(__popcll(m));
         const uint32_t take = n_want < rcount ? n_want : rcount;
         const bool got = want && rank < take;
         uint32_t e = 0;
@@ -137,7 +134,7 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
         const bool swapped = got && fin;
         const unsigned long long ms = __ballot(swapped);
         if (ms != 0ull) {
-          const uint32_t rk = AMBER_RANK(ms);
+          const uint32_t rk = WaveRank(ms);
           if (swapped) done_q[AMBER_WRAP(AMBER_WRAP(dhead + dcount) + rk)] = e;
           dcount += static_cast<uint32_t>(__popcll(ms));
         }
@@ -151,16 +148,16 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
     const unsigned long long m_hold = __ballot(st == LS_HOLD), m_fresh = __ballot(st == LS_FRESH), m_trav = __ballot(st == LS_TRAV);
     if (m_trav == 0ull && m_hold == 0ull && m_fresh == 0ull && dcount == 0u && rcount == 0u) break;
     const uint32_t n_hold = static_cast<uint32_t>(__popcll(m_hold));
-    const bool fill = n_unfilled != 0u && !exhausted && (m_hold | m_fresh) != ~0ull;
+    const bool fill = n_unfilled != 0u && !claim.exhausted && (m_hold | m_fresh) != ~0ull;
     if (m_fresh != 0ull || n_hold + dcount >= AMBER_BVH_POOL_SHADE || (m_trav == 0ull && n_hold + dcount != 0u) || fill) {
       AMBER_CLK(0);
       const bool hold = st == LS_HOLD, fresh = st == LS_FRESH;
       const bool free_lane = !hold && !fresh;
       const unsigned long long mf = __ballot(free_lane);
-      const uint32_t rank_free = AMBER_RANK(mf), n_free = static_cast<uint32_t>(__popcll(mf));
+      const uint32_t rank_free = WaveRank(mf), n_free = static_cast<uint32_t>(__popcll(mf));
       const uint32_t n_take = dcount < n_free ? dcount : n_free;
       uint32_t n_fill = 0;
-      if (!exhausted) { n_fill = n_free - n_take; if (n_fill > n_unfilled) n_fill = n_unfilled; }
+      if (!claim.exhausted) { n_fill = n_free - n_take; if (n_fill > n_unfilled) n_fill = n_unfilled; }
       const bool lds_shade = free_lane && rank_free < n_take;
       const bool filler = free_lane && !lds_shade && rank_free < n_take + n_fill;
       uint32_t e = 0, sr = r;
@@ -183,25 +180,27 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
       rays_wave += static_cast<uint32_t>(__popcll(__ballot(shading)));
       V3 sw = v3(0.f, 0.f, 0.f), meas = v3(0.f, 0.f, 0.f);
       uint64_t srng = 1;
-      uint32_t sq = 0, scasts = 0, sflags = 0, sg_obj = 2166136261u, sg_t = 2166136261u;
+      uint32_t sq = 0, scasts = 0, sflags = 0;
+      PathSig sg; sg.Reset();
       bool have = false, emit = false;
       if (shading) {
         AMBER_COUNT_ROUNDS(3);
         const uint4 p0 = path[sr * kPathQ], p1 = path[sr * kPathQ + 1u];
         sw = v3(AMBER_U2F(p0.x), AMBER_U2F(p0.y), AMBER_U2F(p0.z)); scasts = p0.w;
         srng = static_cast<uint64_t>(p1.x) | (static_cast<uint64_t>(p1.y) << 32); sq = p1.z; sflags = p1.w;
-        if (kSig) { const uint4 p2 = path[sr * kPathQ + (kPathQ - 1u)]; sg_obj = p2.x; sg_t = p2.y; }
+        if (kSig) { const uint4 p2 = path[sr * kPathQ + (kPathQ - 1u)]; sg.obj = p2.x; sg.t = p2.y; }
         if (sflags & 1u) meas = ld3(carried + sr * 3u);               // degenerate paths only (see the file comment)
-        int origin_slot = -1;
+        PathRay ray{so, sd, sw, meas, srng, scasts, -1};
         if (kSig) {
           Bounce b;
-          have = PathShade<true, ENGINE_BVH, false>(sc, nullptr, sh, so, sd, sw, meas, srng, scasts, origin_slot, &b AMBER_POOL_SHADE_STAMP_ARG, nullptr);
-          sg_obj = Fnv32(sg_obj, static_cast<uint32_t>(b.object));
-          if (b.object >= 0) sg_t = Fnv32(sg_t, AMBER_F2U(b.t));
-          if (!have) a.sig[sq] = static_cast<unsigned long long>(sg_obj) | (static_cast<unsigned long long>(sg_t) << 32);
+          BounceExtras extras; extras.trace = &b;
+          have = PathShade<TracedBounceCfg<ENGINE_BVH>>(sc, nullptr, sh, ray, extras AMBER_POOL_SHADE_STAMP_ARG);
+          sg.Add(b);
+          if (!have) a.sig[sq] = sg.Packed();
         } else {
-          have = PathShade<false, ENGINE_BVH, false>(sc, nullptr, sh, so, sd, sw, meas, srng, scasts, origin_slot, nullptr AMBER_POOL_SHADE_STAMP_ARG, nullptr);
+          have = PathShade<BounceCfg<ENGINE_BVH>>(sc, nullptr, sh, ray, BounceExtras{} AMBER_POOL_SHADE_STAMP_ARG);
         }
+        so = ray.o; sd = ray.d; sw = ray.w; meas = ray.meas; srng = ray.rng; scasts = ray.casts;
         const bool nz = (AMBER_F2U(meas.x) | AMBER_F2U(meas.y) | AMBER_F2U(meas.z)) != 0u;   // anything but +0 (RGB)
         emit = !have && nz;
         if (have && nz) { carried[sr * 3u] = meas.x; carried[sr * 3u + 1u] = meas.y; carried[sr * 3u + 2u] = meas.z; sflags |= 1u; }
@@ -209,37 +208,14 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
       EmitRecords(a, emit, sq, meas, rec_next, rec_end);
 
       // the next paths of the queue for the lanes whose path ended, the lanes that start, and the entries to fill
-      bool want_path = (shading && !have) || fresh || filler;
-      bool got_path = false;
-      unsigned long long mw = __ballot(want_path);
-      while (mw != 0ull) {
-        const uint32_t avail = claim_end - claim_next;
-        if (avail == 0u) {
-          if (exhausted) break;
-          uint32_t base = 0;
-          if (lane == 0u) base = atomicAdd(a.next_item, AMBER_BVH_CLAIM_PATHS);
-          base = __builtin_amdgcn_readfirstlane(base);
-          if (base >= a.n_items) { exhausted = true; break; }
-          claim_next = base;
-          claim_end = a.n_items - base < AMBER_BVH_CLAIM_PATHS ? a.n_items : base + AMBER_BVH_CLAIM_PATHS;
-          continue;
-        }
-        const uint32_t rank = AMBER_RANK(mw);
-        if (want_path && rank < avail) { sq = claim_next + rank; want_path = false; got_path = true; }
-        const uint32_t wanted = static_cast<uint32_t>(__popcll(mw));
-        claim_next += wanted < avail ? wanted : avail;
-        mw = __ballot(want_path);
-      }
-      if (got_path) {                                                 // algorithm_pt.cc:125-136: the path's sampler and eye ray
-        const uint32_t plocal = Quotient(a.div_samples, sq), k = sq - plocal * a.n_samples;   // exact dividers formed by the host (exact_div.h)
-        const uint32_t lrow = Quotient(a.div_width, plocal);
-        const uint32_t px = plocal - lrow * sc.sensor.w;
-        const uint32_t py = FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow);
-        srng = XorShiftSeed(a.hashed_seed, px + py * sc.sensor.w, a.first_sample + k);     // Image index x + y*W (image.h:116-124)
+      const bool want_path = (shading && !have) || fresh || filler;
+      if (ServeLanes<AMBER_BVH_CLAIM_PATHS>(claim, a.next_item, a.n_items, lane, want_path, sq)) {                                                 // algorithm_pt.cc:125-136: the path's sampler and eye ray
+        const PathPlace at = PlacePath(a, sq);
+        srng = PathSeed(a, at, at.k);
         float ew; int os;
-        GenerateEyeRay(sc, px, py, srng, so, sd, ew, os);
+        GenerateEyeRay(sc, at.px, at.py, srng, so, sd, ew, os);
         sw = v3(ew, ew, ew);                                          // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
-        scasts = 0; sflags = 0; sg_obj = 2166136261u; sg_t = 2166136261u;
+        scasts = 0; sflags = 0; sg.Reset();
         have = true;
       }
       if (have) {                                                     // slab operands of the ray that will be traversed next
@@ -247,7 +223,7 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
         BvhBegin(sc, so, sd, nt, nh);
         path[sr * kPathQ] = make_uint4(AMBER_F2U(sw.x), AMBER_F2U(sw.y), AMBER_F2U(sw.z), scasts);
         path[sr * kPathQ + 1u] = make_uint4(static_cast<uint32_t>(srng), static_cast<uint32_t>(srng >> 32), sq, sflags);
-        if (kSig) path[sr * kPathQ + (kPathQ - 1u)] = make_uint4(sg_obj, sg_t, 0u, 0u);
+        if (kSig) path[sr * kPathQ + (kPathQ - 1u)] = make_uint4(sg.obj, sg.t, 0u, 0u);
         if (free_lane) {                                              // it waits in the entry; this lane's own traversal goes on
           const uint32_t fl = (nt.rot[0] ? 1u : 0u) | (nt.rot[1] ? 2u : 0u) | (nt.rot[2] ? 4u : 0u) | (nt.cur == AMBER_BVH_DONE ? 8u : 0u);
           entry[e * 5u] = make_uint4(AMBER_F2U(so.x), AMBER_F2U(so.y), AMBER_F2U(so.z), AMBER_F2U(sd.x));
@@ -264,7 +240,7 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
       const bool pushes = have && free_lane;
       const unsigned long long mp = __ballot(pushes);
       if (mp != 0ull) {
-        const uint32_t rk = AMBER_RANK(mp);
+        const uint32_t rk = WaveRank(mp);
         if (pushes) ready_q[AMBER_WRAP(AMBER_WRAP(rhead + rcount) + rk)] = e;
         rcount += static_cast<uint32_t>(__popcll(mp));
       }
@@ -289,7 +265,6 @@ __global__ void __launch_bounds__(256, kSig ? 2 : AMBER_BVH_POOL_WGS) pt_bvh_poo
 
   CloseRecords(a, rec_next, rec_end);
 #undef AMBER_POOL_SHADE_STAMP_ARG
-#undef AMBER_RANK
 #undef AMBER_WRAP
 #undef AMBER_F2U
 #undef AMBER_U2F

@@ -14,37 +14,17 @@ __global__ void __launch_bounds__(256, kWaves) bvh_trace_rate_kernel(const DevSc
   __shared__ int32_t lds_stack[kLdsLevels * 256];
   const BvhStackHybrid stack{(LdsInts)(lds_stack + wave * (kLdsLevels * 64)), (GlobalInts)(gstack + (blockIdx.x * 256u + wave * 64u)), gridDim.x * 256u,
                              kLdsLevels, AMBER_BVH_STACK};
-  uint32_t blk_next = 0, blk_end = 0;
-  bool exhausted = false, has = false;
+  WaveClaim claim;
+  bool has = false;
   uint32_t ray_id = 0, rounds = 0;
   V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
-  BvhTrav tr; tr.A = v3(0.f, 0.f, 0.f); tr.b_in = v3(0.f, 0.f, 0.f); tr.b_out = v3(0.f, 0.f, 0.f); tr.neg_slack = 0.f; tr.rot[0] = tr.rot[1] = tr.rot[2] = 0u;
-  tr.cur = AMBER_BVH_DONE; tr.pend = 0; tr.sp = 0; tr.overflow = false;
-  HitRec hit; hit.t = 0.f; hit.u = 0.f; hit.v = 0.f; hit.idx = -1; hit.slot = -1;
+  BvhTrav tr; HitRec hit;
+  BvhIdle(tr, hit);
   for (;;) {
     const unsigned long long m_has = __ballot(has);
     const uint32_t n_idle = 64u - static_cast<uint32_t>(__popcll(m_has));
     if (n_idle >= refill_min || m_has == 0ull) {                          // wave-uniform: serve the idle lanes
-      bool want = !has, got = false;
-      unsigned long long mw = __ballot(want);
-      while (mw != 0ull) {
-        const uint32_t avail = blk_end - blk_next;
-        if (avail == 0u) {
-          if (exhausted) break;
-          uint32_t base = 0;
-          if (lane == 0u) base = atomicAdd(next, 256u);
-          base = __builtin_amdgcn_readfirstlane(base);
-          if (base >= n) { exhausted = true; break; }
-          blk_next = base; blk_end = n - base < 256u ? n : base + 256u;
-          continue;
-        }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mw >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mw), 0u));
-        if (want && rank < avail) { ray_id = blk_next + rank; want = false; got = true; }
-        const uint32_t wanted = static_cast<uint32_t>(__popcll(mw));
-        blk_next += wanted < avail ? wanted : avail;
-        mw = __ballot(want);
-      }
-      if (got) {
+      if (ServeLanes<256u>(claim, next, n, lane, !has, ray_id)) {
         const uint32_t src = ray_id % n_unique;                             // the ray array is walked `repeats` times: longer launches from the same rays
         const float4 ro = rays[2u * src], rd = rays[2u * src + 1u];
         o = v3(ro.x, ro.y, ro.z); d = v3(rd.x, rd.y, rd.z);

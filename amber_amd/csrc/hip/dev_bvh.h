@@ -54,6 +54,13 @@ struct BvhTrav {
 #define AMBER_BVH_DONE 0x7fffffff
 #define AMBER_BVH_REL_SLACK 9.5367431640625e-07f   /* 2^-20 */
 
+// The state of a lane that holds no ray: nothing to traverse, no hit.  What the persistent kernels start from, and what a lane is left with between rays.
+__device__ __forceinline__ void BvhIdle(BvhTrav& tr, HitRec& hit) {
+  tr.A = v3(0.f, 0.f, 0.f); tr.b_in = v3(0.f, 0.f, 0.f); tr.b_out = v3(0.f, 0.f, 0.f); tr.neg_slack = 0.f; tr.rot[0] = tr.rot[1] = tr.rot[2] = 0u;
+  tr.cur = AMBER_BVH_DONE; tr.pend = 0; tr.sp = 0; tr.overflow = false;
+  hit.t = 0.f; hit.u = 0.f; hit.v = 0.f; hit.idx = -1; hit.slot = -1;
+}
+
 // Slab-test operands of a ray.
 __device__ __forceinline__ void BvhOperands(const DevScene& sc, V3 o, V3 d, BvhTrav& tr) {
   V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);

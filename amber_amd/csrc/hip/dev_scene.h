@@ -24,7 +24,7 @@ __device__ __forceinline__ void CountAt(StampCtx* c, int k) {
   if (!c) return;
   const unsigned long long m = __ballot(true);
   c->acc[2 * k] += 1ull;
-  if (__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u)) == 0u) c->acc[2 * k + 1] += 1ull;
+  if (WaveRank(m) == 0u) c->acc[2 * k + 1] += 1ull;
 }
 #ifdef AMBER_BVH_CLOCKS   /* the same sites as clocks: where a wave's time goes (tools/bvh_counters.py --clocks) */
 #define AMBER_COUNT(k)

@@ -332,24 +332,70 @@ struct PhotonSink : SplatSink { float4* photons; uint32_t surfaces; };
 #define AMBER_PHOTON_CLAIM_PER_LANE 0
 #endif
 
-template <bool kTrace, int kEngine, bool kLight, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u, int kSink = SINK_SPLATS>
-__device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
-                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink, uint32_t* scout_bound = nullptr);
+// A path in flight: the ray of its next cast, its weight (throughput) and measurement, the sampler state, the casts so far, and the filter-program slot
+// of the triangle the ray starts on (-1: none).
+struct PathRay { V3 o, d, w, meas; uint64_t rng; uint32_t casts; int origin_slot; };
 
-template <bool kTrace, int kEngine, bool kLight = false, bool kDivBasis = false, bool kDivHit = false, uint32_t kSqrtMask = 0u, int kSink = SINK_SPLATS>
-__device__ __forceinline__ bool PathStep(const DevScene& sc, const DevObject* lds_objects, int32_t* lds_stack, V3& o, V3& d, V3& weight, V3& measurement,
-                                         uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* sink = nullptr,
-                                         const bool use_premask = false, const uint32_t premask = 0u, const int bvh_stack_cap = AMBER_BVH_STACK, uint32_t* scout_bound = nullptr) {
+// What a bounce is compiled for.  A kernel names its configuration by deriving from BounceCfg<its engine> and restating the members it sets; an option
+// added here with its default is seen only by the kernels that set it.
+//   kTrace     extras.trace receives the hit (object, t, position, weight on arrival)
+//   kLight     a light path (see above);  kSink: what it leaves behind, or SINK_SCOUT
+//   kDivBasis, kDivHit   Normalize's three quotients through one reciprocal (shared_div.h) in the lobe basis / in ResolveHit
+//   kSqrtMask  the switch bits of AMBER_EXACT_SQRT (dev_math.h) that the kernel asks for
+template <int kEngine_> struct BounceCfg {
+  static constexpr int kEngine = kEngine_;
+  static constexpr bool kTrace = false, kLight = false, kDivBasis = false, kDivHit = false;
+  static constexpr uint32_t kSqrtMask = 0u;
+  static constexpr int kSink = SINK_SPLATS;
+  static constexpr bool kPremask = false;              // the kernel may know a cast's candidates (extras.use_premask, extras.premask; the two-phase engines)
+  static constexpr int kBvhStackCap = AMBER_BVH_STACK; // engine BVH's one-shot traversal: levels of the stack in lds.stack
+};
+template <int kEngine_> struct TracedBounceCfg : BounceCfg<kEngine_> { static constexpr bool kTrace = true; };
+template <int kEngine_, bool kPhotons> struct LightBounceCfg : BounceCfg<kEngine_> {       // a light path and what it leaves behind
+  static constexpr bool kLight = true;
+  static constexpr int kSink = kPhotons ? SINK_PHOTONS : SINK_SPLATS;
+};
+// What a bounce is handed at run time beyond the path: all optional.
+struct BounceExtras {
+  Bounce* trace = nullptr;                 // kTrace
+  const SplatSink* sink = nullptr;         // kLight: a SplatSink, or (SINK_PHOTONS) a PhotonSink
+  bool use_premask = false;                // kPremask: the candidates of this cast are known ...
+  uint32_t premask = 0u;                   // ... and are these (pt_megakernel's primary rounds)
+  uint32_t* scout_bound = nullptr;         // SINK_SCOUT
+};
+
+// PathStep / PathShade: one bounce of `ray`.  The ...On forms take the seven values of a PathRay one by one, for a kernel that keeps them as separate locals
+// (pt_megakernel and its replay, whose instruction streams are pinned: EXPERIMENTS.md, device fold); everything else hands over its PathRay.
+template <typename Cfg>
+__device__ __forceinline__ bool PathShadeOn(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
+                                            uint64_t& rng, uint32_t& casts, int& origin_slot, const BounceExtras& extras AMBER_STAMP_PARAM);
+template <typename Cfg>
+__device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, PathRay& ray, const BounceExtras& extras AMBER_STAMP_PARAM) {
+  return PathShadeOn<Cfg>(sc, lds_objects, h, ray.o, ray.d, ray.w, ray.meas, ray.rng, ray.casts, ray.origin_slot, extras AMBER_STAMP_ARG);
+}
+template <typename Cfg>
+__device__ __forceinline__ bool PathStepOn(const DevScene& sc, const EngineLds& lds, V3& o, V3& d, V3& weight, V3& measurement, uint64_t& rng, uint32_t& casts, int& origin_slot,
+                                           const BounceExtras& extras AMBER_STAMP_PARAM) {
   HitRec h;
-  ClosestHit<kEngine, (kSqrtMask & 8u) ? SQRT_EXACT : SQRT_PLAIN>(sc, lds_objects, lds_stack, o, d, origin_slot, h AMBER_STAMP_ARG, use_premask, premask, bvh_stack_cap);
-  return PathShade<kTrace, kEngine, kLight, kDivBasis, kDivHit, kSqrtMask, kSink>(sc, lds_objects, h, o, d, weight, measurement, rng, casts, origin_slot, trace AMBER_STAMP_ARG, sink, scout_bound);
+  ClosestHit<Cfg::kEngine, (Cfg::kSqrtMask & 8u) ? SQRT_EXACT : SQRT_PLAIN>(sc, lds.objects, lds.stack, o, d, origin_slot, h AMBER_STAMP_ARG, Cfg::kPremask && extras.use_premask, Cfg::kPremask ? extras.premask : 0u, Cfg::kBvhStackCap);
+  return PathShadeOn<Cfg>(sc, lds.objects, h, o, d, weight, measurement, rng, casts, origin_slot, extras AMBER_STAMP_ARG);
+}
+template <typename Cfg>
+__device__ __forceinline__ bool PathStep(const DevScene& sc, const EngineLds& lds, PathRay& ray, const BounceExtras& extras AMBER_STAMP_PARAM) {
+  return PathStepOn<Cfg>(sc, lds, ray.o, ray.d, ray.w, ray.meas, ray.rng, ray.casts, ray.origin_slot, extras AMBER_STAMP_ARG);
 }
 
 // Everything of a bounce after the closest-hit query (algorithm_pt.cc:140-157): h is the result of Scene::Cast.
-template <bool kTrace, int kEngine, bool kLight, bool kDivBasis, bool kDivHit, uint32_t kSqrtMask, int kSink>
-__device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
-                                          uint64_t& rng, uint32_t& casts, int& origin_slot, Bounce* trace AMBER_STAMP_PARAM, const SplatSink* splat_sink, uint32_t* scout_bound) {
+template <typename Cfg>
+__device__ __forceinline__ bool PathShadeOn(const DevScene& sc, const DevObject* lds_objects, const HitRec& h, V3& o, V3& d, V3& weight, V3& measurement,
+                                            uint64_t& rng, uint32_t& casts, int& origin_slot, const BounceExtras& extras AMBER_STAMP_PARAM) {
+  constexpr int kEngine = Cfg::kEngine, kSink = Cfg::kSink;
+  constexpr bool kTrace = Cfg::kTrace, kLight = Cfg::kLight, kDivBasis = Cfg::kDivBasis, kDivHit = Cfg::kDivHit;
+  constexpr uint32_t kSqrtMask = Cfg::kSqrtMask;
   constexpr bool kScout = !kLight && kSink == SINK_SCOUT;
+  Bounce* const trace = extras.trace;
+  const SplatSink* const splat_sink = extras.sink;
+  uint32_t* const scout_bound = extras.scout_bound;
   casts++;
   if (h.idx < 0) {
     if (kTrace) { trace->object = -1; trace->t = __builtin_nanf(""); trace->pos = v3(0, 0, 0); trace->weight_before = v3(0, 0, 0); }
@@ -376,7 +422,7 @@ __device__ __forceinline__ bool PathShade(const DevScene& sc, const DevObject* l
 #if AMBER_PHOTON_CLAIM_PER_LANE
         const unsigned int k = atomicAdd(sink->count, 1u);
 #else
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(voters >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(voters), 0u));
+        const uint32_t rank = WaveRank(voters);
         unsigned int base = 0u;
         if (rank == 0u) base = atomicAdd(sink->count, static_cast<unsigned int>(__popcll(voters)));
         const unsigned int k = static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(base), __builtin_ctzll(voters))) + rank;

@@ -120,11 +120,11 @@ __global__ void kat_trace_kernel(const DevScene sc, uint64_t hashed_seed, uint32
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t k = ClampToLastItem(i, n);
   const EngineLds lds = StageEngineLds<kEngine, AMBER_BVH_STACK>(sc);
-  uint64_t rng = XorShiftSeed(hashed_seed, pixel[k], sample[k]);
-  V3 o, d; float ew; int origin_slot;
-  GenerateEyeRay(sc, pixel[k] % sc.sensor.w, pixel[k] / sc.sensor.w, rng, o, d, ew, origin_slot);
-  V3 w = v3(ew, ew, ew), meas = v3(0.f, 0.f, 0.f);
-  uint32_t casts = 0;
+  PathRay ray;
+  ray.rng = XorShiftSeed(hashed_seed, pixel[k], sample[k]);
+  float ew;
+  GenerateEyeRay(sc, pixel[k] % sc.sensor.w, pixel[k] / sc.sensor.w, ray.rng, ray.o, ray.d, ew, ray.origin_slot);
+  ray.w = v3(ew, ew, ew); ray.meas = v3(0.f, 0.f, 0.f); ray.casts = 0;
   bool alive = true;
   // all lanes iterate together so that the scene loop stays wave-uniform; finished lanes idle
   while (__any(alive)) {
@@ -133,18 +133,19 @@ __global__ void kat_trace_kernel(const DevScene sc, uint64_t hashed_seed, uint32
 #ifdef AMBER_STAMPS
       StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-      alive = PathStep<true, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG);
-      if (i < n && casts <= max_bounces) {
-        uint32_t* r = out_records + (static_cast<size_t>(i) * max_bounces + (casts - 1)) * 11u;
+      BounceExtras extras; extras.trace = &b;
+      alive = PathStep<TracedBounceCfg<kEngine>>(sc, lds, ray, extras AMBER_STAMP_ARG);
+      if (i < n && ray.casts <= max_bounces) {
+        uint32_t* r = out_records + (static_cast<size_t>(i) * max_bounces + (ray.casts - 1)) * 11u;
         r[0] = static_cast<uint32_t>(b.object);
         r[1] = __float_as_uint(b.t);
         r[2] = __float_as_uint(b.pos.x); r[3] = __float_as_uint(b.pos.y); r[4] = __float_as_uint(b.pos.z);
         r[5] = __float_as_uint(b.weight_before.x); r[6] = __float_as_uint(b.weight_before.y); r[7] = __float_as_uint(b.weight_before.z);
-        r[8] = __float_as_uint(meas.x); r[9] = __float_as_uint(meas.y); r[10] = __float_as_uint(meas.z);
+        r[8] = __float_as_uint(ray.meas.x); r[9] = __float_as_uint(ray.meas.y); r[10] = __float_as_uint(ray.meas.z);
       }
     }
   }
-  if (i < n) out_casts[i] = casts;
+  if (i < n) out_casts[i] = ray.casts;
 }
 
 // Path signatures of the handle's band (amber_hip_kat_signatures): thread i traces the path of (band pixel i / n_samples,
@@ -159,11 +160,12 @@ __global__ void kat_signature_kernel(const DevScene sc, uint64_t hashed_seed, ui
   const uint32_t plocal = static_cast<uint32_t>(k / n_samples), smp = first_sample + static_cast<uint32_t>(k % n_samples);
   const uint32_t lrow = plocal / sc.sensor.w, px = plocal - lrow * sc.sensor.w;
   const uint32_t py = FrameRow(row_begin, stripe_rows, stripe_period, div_stripe_rows, lrow);
-  uint64_t rng = XorShiftSeed(hashed_seed, px + py * sc.sensor.w, smp);
-  V3 o, d; float ew; int origin_slot;
-  GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot);
-  V3 w = v3(ew, ew, ew), meas = v3(0.f, 0.f, 0.f);
-  uint32_t casts = 0, sig_obj = 2166136261u, sig_t = 2166136261u;
+  PathRay ray;
+  ray.rng = XorShiftSeed(hashed_seed, px + py * sc.sensor.w, smp);
+  float ew;
+  GenerateEyeRay(sc, px, py, ray.rng, ray.o, ray.d, ew, ray.origin_slot);
+  ray.w = v3(ew, ew, ew); ray.meas = v3(0.f, 0.f, 0.f); ray.casts = 0;
+  PathSig sig; sig.Reset();
   bool alive = true;
   while (__any(alive)) {
     if (alive) {
@@ -171,12 +173,12 @@ __global__ void kat_signature_kernel(const DevScene sc, uint64_t hashed_seed, ui
 #ifdef AMBER_STAMPS
       StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-      alive = PathStep<true, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG);
-      sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
-      if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
+      BounceExtras extras; extras.trace = &b;
+      alive = PathStep<TracedBounceCfg<kEngine>>(sc, lds, ray, extras AMBER_STAMP_ARG);
+      sig.Add(b);
     }
   }
-  if (i < n) out[i] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
+  if (i < n) out[i] = sig.Packed();
 }
 
 // The caller's records through the product's own emitters (amber_hip_kat_accumulate).  Wave w of n_waves takes the trips w, w + n_waves, ... of 64

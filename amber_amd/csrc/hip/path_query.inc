@@ -10,7 +10,7 @@
 //                                is one bounce of every lane that holds a ray.  The two-phase image is staged once per workgroup, before anything diverges.
 //                                Engine BVH: ClosestHitBvh<true> (the one-shot per-lane traversal with the whole AMBER_BVH_STACK levels in LDS; an origin
 //                                outside the scene's bounding sphere and a stack overflow take the leaf-list scan) + PathShade, on the query grid at
-//                                AMBER_QUERY_WAVES; the other engines PathStep<false, kEngine> on the render kernels' grid (REFERENCE_BVH: one global stack
+//                                AMBER_QUERY_WAVES; the other engines PathStep<BounceCfg<kEngine>> on the render kernels' grid (REFERENCE_BVH: one global stack
 //                                column per thread of THAT grid).  The IsNanRay guard applies to the first cast of a path only: every later ray is the path's own.
 //                                A ray is four 16-byte loads (the first three again at the start of each further sample: nothing of the start is kept in
 //                                registers across a path), a result two 16-byte stores.
@@ -33,24 +33,23 @@ struct PathQueryArgs {
 
 // What a lane holds of its ray: the path in flight, the sums of the finished samples, the sampler stream.
 struct PathLane {
-  V3 o, d, w, meas, sum;
-  uint64_t rng;
-  uint32_t ray, sample, path_casts, casts;
-  int origin_slot;
+  PathRay path;                                   // (path.casts: the casts of the path in flight)
+  V3 sum;
+  uint32_t ray, sample, casts;
   bool first;                                     // the next cast is the first of its path: the caller's own ray
 };
 
 // A path of the lane's ray starts: (origin, dir, weight) as the caller gave them, measurement +0, no origin object
 __device__ __forceinline__ void PathQueryStart(const float4* __restrict__ rays, PathLane& p) {
   const float4 ro = rays[4u * static_cast<size_t>(p.ray)], rd = rays[4u * static_cast<size_t>(p.ray) + 1u], rw = rays[4u * static_cast<size_t>(p.ray) + 2u];
-  p.o = v3(ro.x, ro.y, ro.z); p.d = v3(rd.x, rd.y, rd.z); p.w = v3(rw.x, rw.y, rw.z);
-  p.meas = v3(0.f, 0.f, 0.f); p.path_casts = 0u; p.origin_slot = -1; p.first = true;
+  p.path.o = v3(ro.x, ro.y, ro.z); p.path.d = v3(rd.x, rd.y, rd.z); p.path.w = v3(rw.x, rw.y, rw.z);
+  p.path.meas = v3(0.f, 0.f, 0.f); p.path.casts = 0u; p.path.origin_slot = -1; p.first = true;
 }
 __device__ __forceinline__ void PathQueryBegin(const float4* __restrict__ rays, uint32_t ray, PathLane& p) {
   p.ray = ray; p.sample = 0u; p.casts = 0u; p.sum = v3(0.f, 0.f, 0.f);
   const float4 rs = rays[4u * static_cast<size_t>(ray) + 3u];
-  p.rng = static_cast<uint64_t>(__float_as_uint(rs.x)) | (static_cast<uint64_t>(__float_as_uint(rs.y)) << 32);
-  if (p.rng == 0ull) p.rng = 0x9E3779B97F4A7C15ull;            // a zero xorshift state draws 0 forever
+  p.path.rng = static_cast<uint64_t>(__float_as_uint(rs.x)) | (static_cast<uint64_t>(__float_as_uint(rs.y)) << 32);
+  if (p.path.rng == 0ull) p.path.rng = 0x9E3779B97F4A7C15ull;            // a zero xorshift state draws 0 forever
   PathQueryStart(rays, p);
 }
 
@@ -59,27 +58,27 @@ template <int kEngine>
 __device__ __forceinline__ bool PathQueryBounce(const PathQueryArgs& a, const EngineLds& lds, PathLane& p) {
   const DevScene& sc = a.scene;
   bool alive;
-  if (p.first && IsNanRay(p.o, p.d)) {                        // misses, as in cast_rays: the cast is counted, nothing is drawn
-    p.path_casts++; alive = false;
+  if (p.first && IsNanRay(p.path.o, p.path.d)) {              // misses, as in cast_rays: the cast is counted, nothing is drawn
+    p.path.casts++; alive = false;
   } else if constexpr (kEngine == ENGINE_BVH) {
     HitRec h;
-    ClosestHitBvh<true>(sc, lds.stack, p.o, p.d, h);
+    ClosestHitBvh<true>(sc, lds.stack, p.path.o, p.path.d, h);
 #ifdef AMBER_STAMPS
     StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-    alive = PathShade<false, ENGINE_BVH, false>(sc, lds.objects, h, p.o, p.d, p.w, p.meas, p.rng, p.path_casts, p.origin_slot, nullptr AMBER_STAMP_ARG, nullptr);
+    alive = PathShade<BounceCfg<ENGINE_BVH>>(sc, lds.objects, h, p.path, BounceExtras{} AMBER_STAMP_ARG);
   } else {
 #ifdef AMBER_STAMPS
     StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-    alive = PathStep<false, kEngine>(sc, lds.objects, lds.stack, p.o, p.d, p.w, p.meas, p.rng, p.path_casts, p.origin_slot, nullptr AMBER_STAMP_ARG);
+    alive = PathStep<BounceCfg<kEngine>>(sc, lds, p.path, BounceExtras{} AMBER_STAMP_ARG);
   }
   p.first = false;
   if (alive) return true;
-  p.sum = p.sum + p.meas; p.casts += p.path_casts;
+  p.sum = p.sum + p.path.meas; p.casts += p.path.casts;
   if (++p.sample < a.n_samples) { PathQueryStart(a.rays, p); return true; }
   a.out[2u * static_cast<size_t>(p.ray)] = make_float4(p.sum.x, p.sum.y, p.sum.z, __uint_as_float(p.casts));
-  a.out[2u * static_cast<size_t>(p.ray) + 1u] = make_float4(__uint_as_float(static_cast<uint32_t>(p.rng)), __uint_as_float(static_cast<uint32_t>(p.rng >> 32)), 0.f, 0.f);
+  a.out[2u * static_cast<size_t>(p.ray) + 1u] = make_float4(__uint_as_float(static_cast<uint32_t>(p.path.rng)), __uint_as_float(static_cast<uint32_t>(p.path.rng >> 32)), 0.f, 0.f);
   return false;
 }
 
@@ -87,37 +86,17 @@ template <int kEngine>
 __global__ void __launch_bounds__(256, kEngine == ENGINE_BVH ? AMBER_QUERY_WAVES : 1) path_query_kernel(const PathQueryArgs a) {
   const EngineLds lds = StageEngineLds<kEngine, AMBER_BVH_STACK>(a.scene);   // (ends with a barrier where it stages: before anything diverges)
   PathLane p;
-  p.o = v3(0.f, 0.f, 0.f); p.d = v3(0.f, 0.f, 1.f); p.w = p.o; p.meas = p.o; p.sum = p.o;
-  p.rng = 1ull; p.ray = 0u; p.sample = 0u; p.path_casts = 0u; p.casts = 0u; p.origin_slot = -1; p.first = false;
+  p.path.o = v3(0.f, 0.f, 0.f); p.path.d = v3(0.f, 0.f, 1.f); p.path.w = p.path.o; p.path.meas = p.path.o; p.sum = p.path.o;
+  p.path.rng = 1ull; p.ray = 0u; p.sample = 0u; p.path.casts = 0u; p.casts = 0u; p.path.origin_slot = -1; p.first = false;
   bool has = false;
   const uint32_t lane = threadIdx.x & 63u;
-  uint32_t blk_next = 0, blk_end = 0;
-  bool exhausted = false;
+  WaveClaim claim;
   for (;;) {
     const unsigned long long m_has = __ballot(has);
     const uint32_t n_idle = 64u - static_cast<uint32_t>(__popcll(m_has));
     if (n_idle >= AMBER_QUERY_REFILL || m_has == 0ull) {                  // wave-uniform: serve the idle lanes
-      bool want = !has, got = false;
       uint32_t ray = 0;
-      unsigned long long mw = __ballot(want);
-      while (mw != 0ull) {
-        const uint32_t avail = blk_end - blk_next;
-        if (avail == 0u) {
-          if (exhausted) break;
-          uint32_t base = 0;
-          if (lane == 0u) base = atomicAdd(a.next, AMBER_PATH_CLAIM);        // (n <= 2^31 and every wave adds once more at most: no wrap)
-          base = __builtin_amdgcn_readfirstlane(base);
-          if (base >= a.n) { exhausted = true; break; }
-          blk_next = base; blk_end = a.n - base < AMBER_PATH_CLAIM ? a.n : base + AMBER_PATH_CLAIM;
-          continue;
-        }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mw >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mw), 0u));
-        if (want && rank < avail) { ray = blk_next + rank; want = false; got = true; }
-        const uint32_t wanted = static_cast<uint32_t>(__popcll(mw));
-        blk_next += wanted < avail ? wanted : avail;
-        mw = __ballot(want);
-      }
-      if (got) { PathQueryBegin(a.rays, ray, p); has = true; }
+      if (ServeLanes<AMBER_PATH_CLAIM>(claim, a.next, a.n, lane, !has, ray)) { PathQueryBegin(a.rays, ray, p); has = true; }
       if (__ballot(has) == 0ull) break;
     }
     if (has) has = PathQueryBounce<kEngine>(a, lds, p);

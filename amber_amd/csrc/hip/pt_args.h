@@ -58,11 +58,32 @@ __device__ __forceinline__ typename std::conditional<kPhotons, PhotonSink, Splat
 }
 
 // Local row of a band -> row of the frame: contiguous rows from row_begin (stripe_rows == 0: the divider is not used), or stripes of stripe_rows rows
-// every stripe_period rows.  The kernels that read these fields as plain arguments share it; pt_megakernel reads them cold, one by one (pt_megakernel.inc).
+// every stripe_period rows.  The kernels that read these fields as plain arguments share it through PlacePath / PlacePixel below.  Four sites keep their
+// own form: pt_megakernel reads the fields cold, one by one (pt_megakernel.inc); pt_bvh_megakernel divides plainly on purpose (its comment cites the
+// measurement); replay_records_kernel's instruction stream is pinned, and through PlacePath its schedule moves (EXPERIMENTS.md, device fold);
+// kat_signature_kernel's frozen argument list has no divider for the width.
 __device__ __forceinline__ uint32_t FrameRow(uint32_t row_begin, uint32_t stripe_rows, uint32_t stripe_period, ExactDiv div_stripe_rows, uint32_t lrow) {
   if (stripe_rows == 0u) return row_begin + lrow;
   const uint32_t band = Quotient(div_stripe_rows, lrow);
   return row_begin + band * stripe_period + (lrow - band * stripe_rows);
+}
+// Where a path lies: band pixel, sample offset within the launch, pixel of the frame.  Args: RenderArgs, or any record with its band fields (SetBand).
+struct PathPlace { uint32_t plocal, k, px, py; };
+template <typename Args>
+__device__ __forceinline__ PathPlace PlacePixel(const Args& a, uint32_t plocal, uint32_t k = 0u) {
+  const uint32_t lrow = Quotient(a.div_width, plocal);
+  return PathPlace{plocal, k, plocal - lrow * a.scene.sensor.w, FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow)};
+}
+// Path q = plocal * n_samples + k of a launch (pt_megakernel.inc)
+__device__ __forceinline__ PathPlace PlacePath(const RenderArgs& a, uint32_t q) {
+  const uint32_t plocal = Quotient(a.div_samples, q);
+  return PlacePixel(a, plocal, q - plocal * a.n_samples);
+}
+// The sampler state the k-th sample of the launch at that pixel starts from: Image index x + y*W (image.h:116-124), sample first_sample + k.  k is an
+// argument, not place.k: a kernel that owns a pixel (aov_kernel, wf_generate_kernel) places it once with PlacePixel and seeds every sample from it.
+template <typename Args>
+__device__ __forceinline__ uint64_t PathSeed(const Args& a, const PathPlace& p, uint32_t k) {
+  return XorShiftSeed(a.hashed_seed, p.px + p.py * a.scene.sensor.w, a.first_sample + k);
 }
 
 // COLD kernel arguments of pt_megakernel.  A field of RenderArgs that the kernel reads as `a.field` is loaded once at the kernel's entry and then
@@ -95,6 +116,16 @@ __device__ __forceinline__ uint32_t Fnv32(uint32_t h, uint32_t v) {
   for (int k = 0; k < 4; k++) { h ^= (v >> (8 * k)) & 0xffu; h *= 16777619u; }
   return h;
 }
+// A path's signature: FNV-1a-32 over the object index of every cast (0xffffffff = miss) and over the bits of every hit distance, packed {obj, t << 32}
+struct PathSig {
+  uint32_t obj, t;
+  __device__ __forceinline__ void Reset() { obj = 2166136261u; t = 2166136261u; }          // the FNV offset basis
+  __device__ __forceinline__ void Add(const Bounce& b) {
+    obj = Fnv32(obj, static_cast<uint32_t>(b.object));
+    if (b.object >= 0) t = Fnv32(t, __float_as_uint(b.t));
+  }
+  __device__ __forceinline__ unsigned long long Packed() const { return static_cast<unsigned long long>(obj) | (static_cast<unsigned long long>(t) << 32); }
+};
 
 // Accumulation without owners, device side.  A path that ends with a measurement other than +0 appends {q, rgb} to the
 // record buffer and sets bit q.  Slots are reserved per WAVE, AMBER_REC_BLOCK at a time (one atomicAdd on the shared
@@ -112,7 +143,7 @@ __device__ __forceinline__ void EmitRecords(SinkOf sink_of, bool emit, uint32_t 
   if (me == 0ull) return;                                     // wave-uniform
   const RecordSink a = sink_of();
   const uint32_t n = static_cast<uint32_t>(__popcll(me));
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(me >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(me), 0u));
+  const uint32_t rank = WaveRank(me);
   const uint32_t room = rec_end - rec_next;
   uint32_t fresh = 0;
   if (n > room) {                                             // n <= 64 = AMBER_REC_BLOCK: one new block always suffices

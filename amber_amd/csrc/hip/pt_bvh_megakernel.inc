@@ -31,19 +31,16 @@ __global__ void __launch_bounds__(256, kStack <= 24 && !kSig ? AMBER_BVH_WGS : 4
                                                            // throughput -- what the compiler spills next -- make 32 KB per workgroup: five no longer fit a CU, 113 ms instead of 101 at 128 spp)
   float* const my_sum = lds_sum + threadIdx.x;
 
-  uint32_t pool_next = 0, pool_end = 0;
-  bool exhausted = false;
+  WaveClaim claim;
   bool lane_done = false, have_item = false, alive = false, traversing = false;
   uint32_t s = 0, s_end = 0, pixel = 0, slot = 0;          // the pixel's x, y are recomputed where a path starts: two registers less
-  V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f), w = v3(0.f, 0.f, 0.f);
-  uint64_t rng = 1;
-  uint32_t casts = 0;
+  PathRay ray;                                              // (ray.meas lives in LDS between bounces: rows 3-5 of lds_sum)
+  ray.o = v3(0.f, 0.f, 0.f); ray.d = v3(0.f, 0.f, 1.f); ray.w = v3(0.f, 0.f, 0.f);
+  ray.rng = 1; ray.casts = 0; ray.origin_slot = -1;
   uint32_t rays_wave = 0;                                   // wave-uniform (SGPR): rays shaded by this wave
-  int origin_slot = -1;
-  uint32_t sig_obj = 2166136261u, sig_t = 2166136261u;      // kSig only
-  BvhTrav tr; tr.A = v3(0.f, 0.f, 0.f); tr.b_in = v3(0.f, 0.f, 0.f); tr.b_out = v3(0.f, 0.f, 0.f); tr.neg_slack = 0.f; tr.rot[0] = tr.rot[1] = tr.rot[2] = 0u;
-  tr.cur = AMBER_BVH_DONE; tr.pend = 0; tr.sp = 0; tr.overflow = false;
-  HitRec hit; hit.t = 0.f; hit.u = 0.f; hit.v = 0.f; hit.idx = -1; hit.slot = -1;
+  PathSig sig; sig.Reset();                                 // kSig only
+  BvhTrav tr; HitRec hit;
+  BvhIdle(tr, hit);
 #ifdef AMBER_STAMPS
   StampCtx stamp_store{}, stamp_shade{}; StampCtx* stamp_ctx = &stamp_store;     // counters here; PathShade's clocks go to a dummy
 #define AMBER_SHADE_STAMP_ARG , &stamp_shade
@@ -61,40 +58,21 @@ __global__ void __launch_bounds__(256, kStack <= 24 && !kSig ? AMBER_BVH_WGS : 4
       }
       have_item = false;
     }
-    unsigned long long mask = __ballot(need);
-    while (mask) {                                          // hand out work items (see pt_megakernel)
-      const uint32_t avail = pool_end - pool_next;
-      if (avail == 0) {
-        if (exhausted) break;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(a.next_item, 64u);
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (base >= a.n_items) { exhausted = true; break; }
-        pool_next = base;
-        pool_end = base + 64u < a.n_items ? base + 64u : a.n_items;
-        continue;
-      }
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32),
-                                                     __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-      if (need && rank < avail) {
-        const uint32_t item = pool_next + rank;
-        const uint32_t plocal = item / a.n_chunks, chunk = item - plocal * a.n_chunks;
-        // (plain divisions, once per item: the exact dividers of exact_div.h were measured here and the kernel was no faster, EXPERIMENTS.md)
-        const uint32_t lrow = plocal / sc.sensor.w;
-        const uint32_t px = plocal - lrow * sc.sensor.w;
-        const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);
-        pixel = kLight ? a.path_offset + plocal : px + py * sc.sensor.w;      // light tracing: the light path's index
-        slot = chunk * a.n_pixels + plocal;
-        s = a.first_sample + chunk * AMBER_ACCUM_CHUNK;
-        const uint32_t left = a.first_sample + a.n_samples - s;
-        s_end = s + (left < AMBER_ACCUM_CHUNK ? left : AMBER_ACCUM_CHUNK);
-        my_sum[0] = 0.f; my_sum[256] = 0.f; my_sum[512] = 0.f;
-        have_item = true;
-        need = false;
-      }
-      const uint32_t wanted = static_cast<uint32_t>(__popcll(mask));
-      pool_next += wanted < avail ? wanted : avail;
-      mask = __ballot(need);
+    uint32_t item = 0;
+    if (ServeLanes<64u>(claim, a.next_item, a.n_items, lane, need, item)) {     // hand out work items, 64 to a claim
+      const uint32_t plocal = item / a.n_chunks, chunk = item - plocal * a.n_chunks;
+      // (plain divisions, once per item: the exact dividers of exact_div.h were measured here and the kernel was no faster, EXPERIMENTS.md)
+      const uint32_t lrow = plocal / sc.sensor.w;
+      const uint32_t px = plocal - lrow * sc.sensor.w;
+      const uint32_t py = a.row_begin + (a.stripe_rows ? (lrow / a.stripe_rows) * a.stripe_period + lrow % a.stripe_rows : lrow);
+      pixel = kLight ? a.path_offset + plocal : px + py * sc.sensor.w;      // light tracing: the light path's index
+      slot = chunk * a.n_pixels + plocal;
+      s = a.first_sample + chunk * AMBER_ACCUM_CHUNK;
+      const uint32_t left = a.first_sample + a.n_samples - s;
+      s_end = s + (left < AMBER_ACCUM_CHUNK ? left : AMBER_ACCUM_CHUNK);
+      my_sum[0] = 0.f; my_sum[256] = 0.f; my_sum[512] = 0.f;
+      have_item = true;
+      need = false;
     }
     if (need) lane_done = true;
     if (__ballot(!lane_done) == 0ull) break;
@@ -102,21 +80,21 @@ __global__ void __launch_bounds__(256, kStack <= 24 && !kSig ? AMBER_BVH_WGS : 4
     AMBER_CLK(0);
     if (!alive && !lane_done) {                             // regenerate: next sample of the item, start its traversal
       AMBER_COUNT_ROUNDS(3);
-      rng = XorShiftSeed(a.hashed_seed, pixel, s);
+      ray.rng = XorShiftSeed(a.hashed_seed, pixel, s);
       if (kLight) {
-        GenerateLightRay(sc, rng, o, d, w, origin_slot);
+        GenerateLightRay(sc, ray.rng, ray.o, ray.d, ray.w, ray.origin_slot);
       } else {
         float ew;
         const uint32_t py = pixel / sc.sensor.w;
-        GenerateEyeRay(sc, pixel - py * sc.sensor.w, py, rng, o, d, ew, origin_slot);
-        w = v3(ew, ew, ew);
+        GenerateEyeRay(sc, pixel - py * sc.sensor.w, py, ray.rng, ray.o, ray.d, ew, ray.origin_slot);
+        ray.w = v3(ew, ew, ew);
       }
       my_sum[768] = 0.f; my_sum[1024] = 0.f; my_sum[1280] = 0.f;
-      casts = 0;
+      ray.casts = 0;
       alive = true;
       ++s;
-      if (kSig) { sig_obj = 2166136261u; sig_t = 2166136261u; }
-      BvhBegin(sc, o, d, tr, hit);
+      if (kSig) sig.Reset();
+      BvhBegin(sc, ray.o, ray.d, tr, hit);
       traversing = true;
     }
 
@@ -127,34 +105,36 @@ __global__ void __launch_bounds__(256, kStack <= 24 && !kSig ? AMBER_BVH_WGS : 4
       if (static_cast<uint32_t>(__popcll(__ballot(alive && !traversing))) >= a.shade_batch) break;
       if (traversing) {
         AMBER_COUNT_ROUNDS(2);
-        traversing = BvhRound(sc, lds_stack, o, d, tr, hit, kStack AMBER_STAMP_ARG);
-        if (!traversing && tr.overflow) ClosestHitLeafList(sc, o, d, hit);
+        traversing = BvhRound(sc, lds_stack, ray.o, ray.d, tr, hit, kStack AMBER_STAMP_ARG);
+        if (!traversing && tr.overflow) ClosestHitLeafList(sc, ray.o, ray.d, hit);
       }
     }
 
     AMBER_CLK(6);
     rays_wave += static_cast<uint32_t>(__popcll(__ballot(alive && !traversing)));
     if (alive && !traversing) {                             // shade the lanes whose closest hit is known
-      V3 meas = v3(my_sum[768], my_sum[1024], my_sum[1280]);  // the measurement is read and written once per bounce: LDS, not registers held across the traversal
+      V3& meas = ray.meas;
+      meas = v3(my_sum[768], my_sum[1024], my_sum[1280]);     // the measurement is read and written once per bounce: LDS, not registers held across the traversal
       if (kLight) {
         if (kPhotons) BvhResolveIndex(sc, hit);               // a vertex names its object
         const typename std::conditional<kPhotons, PhotonSink, SplatSink>::type sink = MakeLightSink<kPhotons>(a, pixel, s - 1u);
-        alive = PathShade<false, ENGINE_BVH, true, false, false, 0u, kPhotons ? SINK_PHOTONS : SINK_SPLATS>(sc, nullptr, hit, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_SHADE_STAMP_ARG, &sink);
+        BounceExtras extras; extras.sink = &sink;
+        alive = PathShade<LightBounceCfg<ENGINE_BVH, kPhotons>>(sc, nullptr, hit, ray, extras AMBER_SHADE_STAMP_ARG);
       } else if (kSig) {
         BvhResolveIndex(sc, hit);                             // only the signature variant reports object indices
         Bounce b;
-        alive = PathShade<true, ENGINE_BVH, false>(sc, nullptr, hit, o, d, w, meas, rng, casts, origin_slot, &b AMBER_SHADE_STAMP_ARG, nullptr);
-        sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
-        if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
+        BounceExtras extras; extras.trace = &b;
+        alive = PathShade<TracedBounceCfg<ENGINE_BVH>>(sc, nullptr, hit, ray, extras AMBER_SHADE_STAMP_ARG);
+        sig.Add(b);
         if (!alive) {                                         // path (band pixel, sample s - 1) of this launch
           const uint32_t plocal = slot % a.n_pixels;
-          a.sig[static_cast<size_t>(plocal) * a.n_samples + (s - 1u - a.first_sample)] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
+          a.sig[static_cast<size_t>(plocal) * a.n_samples + (s - 1u - a.first_sample)] = sig.Packed();
         }
       } else {
-        alive = PathShade<false, ENGINE_BVH, false>(sc, nullptr, hit, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_SHADE_STAMP_ARG, nullptr);
+        alive = PathShade<BounceCfg<ENGINE_BVH>>(sc, nullptr, hit, ray, BounceExtras{} AMBER_SHADE_STAMP_ARG);
       }
       if (alive) { my_sum[768] = meas.x; my_sum[1024] = meas.y; my_sum[1280] = meas.z; }
-      if (alive) { BvhBegin(sc, o, d, tr, hit); traversing = true; }
+      if (alive) { BvhBegin(sc, ray.o, ray.d, tr, hit); traversing = true; }
       else { my_sum[0] = my_sum[0] + meas.x; my_sum[256] = my_sum[256] + meas.y; my_sum[512] = my_sum[512] + meas.z; }   // sequential sum over the item's samples
     }
     AMBER_CLK(5);

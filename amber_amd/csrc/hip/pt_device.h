@@ -16,7 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// The device functions live in nine parts, included here in the order they build on each other (one translation unit: pt_host.hip):
+// The device functions live in ten parts, included here in the order they build on each other (one translation unit: pt_host.hip):
+//   dev_wave.h         a lane's rank in a ballot; indices handed out from a block the wave claimed (WaveRank, ServeLanes)
 //   dev_scene.h        diagnostic macros of the stamped builds; the scene layout in HBM (DevObject ... DevScene)
 //   shared_div.h       three quotients by one denominator at one reciprocal (host and device)
 //   exact_sqrt.h       the correctly rounded square root from one v_rsq_f32 seed; Normalize from that seed (host and device)
@@ -26,6 +27,7 @@
 //   dev_bvh.h          engine BVH: quantised 2-wide tree, two-stage leaves, resumable rounds
 //   dev_closest_hit.h  engine REFERENCE_BVH; ClosestHit<kEngine>; ResolveHit
 //   dev_shading.h      materials, eye ray, light-path start, PathStep / PathShade
+#include "dev_wave.h"
 #include "dev_scene.h"
 #include "shared_div.h"
 #include "exact_sqrt.h"

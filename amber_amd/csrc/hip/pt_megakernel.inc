@@ -42,7 +42,22 @@
 #endif
 // Pool slot: the whole state of a path between two bounces in four 16-byte chunks {o.xyz d.x} {d.yz w.xy} {w.z rng q}
 // {casts | carried-flag, origin slot, signature hashes}.  kScout: three chunks {o.xyz d.x} {d.yz rng} {q casts origin-slot bound} -- no weight, nothing carried.
-template <bool kLight, bool kScout = false> struct PoolLayout { static constexpr int kChunks = kScout ? 3 : 4; };
+// (A carried measurement itself travels through global memory, next to the slot: the kernel copies it.)  Park below writes a slot; the pop in the kernel
+// is the layout's other implementation, written out there: through a helper pt_megakernel<2,0,0> loses its pinned instruction stream (EXPERIMENTS.md).
+template <bool kLight, bool kScout = false> struct PoolLayout {
+  static constexpr int kChunks = kScout ? 3 : 4;
+  static __device__ __forceinline__ void Park(uint4* slot, V3 o, V3 d, V3 w, uint64_t rng, uint32_t q, uint32_t casts, bool carries, int origin_slot, const PathSig& sig, uint32_t scout_bound) {
+    slot[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
+    if constexpr (kScout) {
+      slot[1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), static_cast<uint32_t>(rng), static_cast<uint32_t>(rng >> 32));
+      slot[2] = make_uint4(q, casts, static_cast<uint32_t>(origin_slot), scout_bound);
+    } else {
+      slot[1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(w.x), __float_as_uint(w.y));
+      slot[2] = make_uint4(__float_as_uint(w.z), static_cast<uint32_t>(rng), static_cast<uint32_t>(rng >> 32), q);
+      slot[3] = make_uint4(casts | (carries ? 0x80000000u : 0u), static_cast<uint32_t>(origin_slot), sig.obj, sig.t);
+    }
+  }
+};
 
 // Traversal-stack entries of pt_megakernel<ENGINE_BVH> (a deeper tree renders with pt_bvh_megakernel): 12 KB of LDS next to the 16-KB
 // pool, five workgroups per CU (16 entries: four).  Where the two schedulers cross over (tools/mesh_workloads.py, 1024^2 @ 256 spp, a room
@@ -66,6 +81,17 @@ template <bool kLight, bool kScout = false> struct PoolLayout { static constexpr
 #ifndef AMBER_SCOUT
 #define AMBER_SCOUT 1
 #endif
+// What the eye-path instantiations compile a bounce for: kCold (below) selects the arithmetic family -- Normalize's three quotients through one reciprocal
+// (shared_div.h) and the square roots from one v_rsq_f32 seed (exact_sqrt.h; the switch bits: dev_math.h).  replay_records_kernel takes the same, cold.
+template <int kEngine_, bool kCold> struct PathBounceCfg : BounceCfg<kEngine_> {
+  static constexpr bool kDivBasis = kCold && (AMBER_SHARED_DIV_NORMALIZE & 1), kDivHit = kCold && (AMBER_SHARED_DIV_NORMALIZE & 2);
+  static constexpr uint32_t kSqrtMask = kCold ? static_cast<uint32_t>(AMBER_EXACT_SQRT) : 0u;
+  static constexpr bool kPremask = true;
+  static constexpr int kBvhStackCap = AMBER_PATH_BVH_STACK;
+};
+template <int kEngine_, bool kCold> struct PathSigCfg : PathBounceCfg<kEngine_, kCold> { static constexpr bool kTrace = true; };
+template <int kEngine_, bool kCold> struct PathScoutCfg : PathBounceCfg<kEngine_, kCold> { static constexpr int kSink = SINK_SCOUT; };
+template <int kEngine_, bool kPhotons> struct PathLightCfg : LightBounceCfg<kEngine_, kPhotons> { static constexpr int kBvhStackCap = AMBER_PATH_BVH_STACK; };
 template <int kEngineSink, bool kLight = false, bool kSig = false>
 __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | AMBER_KERNEL_SCOUT)) == ENGINE_BVH ? 5 : AMBER_MEGAKERNEL_WAVES_PER_SIMD) pt_megakernel(const RenderArgs a) {
   constexpr int kEngine = kEngineSink & ~(AMBER_KERNEL_PHOTONS | AMBER_KERNEL_SCOUT);
@@ -75,17 +101,21 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
   static_assert(!kScout || (kEngine == ENGINE_TWO_PHASE && !kLight && !kSig), "the scout is the headline kernel's loop");
   const DevScene& sc = a.scene;
   const uint32_t lane = threadIdx.x & 63u;
+  // What a bounce of this kernel is handed besides the path.  Declared HERE, ahead of the loop, for the pinned instruction stream only: declared next to
+  // the call, pt_megakernel<2,0,0> differs from its parent by one commuted s_and_b64.  So `trace` and `sink` hold addresses of block-local objects that
+  // end with their block: every field a configuration reads is set again in front of each call, and nothing may read `extras` anywhere else.
+  BounceExtras extras;
   constexpr bool kTwoPhase = EngineTraits<kEngine>::kTwoPhase;
-  constexpr int kChunks = PoolLayout<kLight, kScout>::kChunks;
+  using Pool = PoolLayout<kLight, kScout>;
+  constexpr int kChunks = Pool::kChunks;
   constexpr bool kCold = !kLight && kEngine != ENGINE_BVH;    // cold kernel arguments are read next to their use (AMBER_ARG below)
   // a cold argument, read next to its use (pt_args.h).  Two families keep the plain form: the light tracer (its bounces read n_samples and
   // first_sample themselves, and with these reads the kernel reserved scratch) and engine BVH's one-shot traversal (measured: Cornell through
   // ENGINE_BVH 118.6 -> 120.0 ms, the room mesh 52.7 -> 53.6 ms with cold reads, EXPERIMENTS.md).
-  // Normalize's three quotients through one reciprocal (shared_div.h): the same family, for the same kind of reason (the light tracers and
-  // <ENGINE_BVH> were not measured with it and keep the plain divisions)
-  constexpr bool kDivBasis = kCold && (AMBER_SHARED_DIV_NORMALIZE & 1), kDivHit = kCold && (AMBER_SHARED_DIV_NORMALIZE & 2), kDivEye = kCold && (AMBER_SHARED_DIV_NORMALIZE & 4);
-  // the square roots of the bounce and the eye ray from one v_rsq_f32 seed (exact_sqrt.h; the switch bits: dev_math.h): the same family again
-  constexpr uint32_t kSqrtMask = kCold ? static_cast<uint32_t>(AMBER_EXACT_SQRT) : 0u;
+  // The arithmetic of PathBounceCfg, for the bounce and the eye ray: the same family, for the same kind of reason (the light tracers and <ENGINE_BVH> were
+  // not measured with it and keep the plain divisions and roots)
+  constexpr bool kDivEye = kCold && (AMBER_SHARED_DIV_NORMALIZE & 4);
+  constexpr uint32_t kSqrtMask = PathBounceCfg<kEngine, kCold>::kSqrtMask;
 #define AMBER_ARG(cold, field) (kCold ? AMBER_COLD(cold, field) : a.field)
 #define AMBER_COLD_OPEN() (kCold ? ColdArgs::Open() : ColdArgs{nullptr})
   __shared__ uint4 lds_pool[4][64 * kChunks];                 // [wave][slot * kChunks + chunk]
@@ -128,7 +158,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
   uint32_t scout_bound = 0;                  // kScout: scout_bound.h's bound of log2 |weight|, sixteenths of a bit; above kLimit: `suspect`
   uint32_t rays_wave = 0;                    // wave-uniform (SGPR): rays cast by this wave
   int origin_slot = -1;                      // filter-program slot of the triangle the current ray starts on
-  uint32_t sig_obj = 2166136261u, sig_t = 2166136261u;   // kSig only
+  PathSig sig; sig.Reset();                  // kSig only
 #ifdef AMBER_STAMPS
   StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
   stamp_ctx->last = __builtin_amdgcn_s_memtime();
@@ -144,7 +174,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
     uint32_t premask = 0u;
     if (mask) {                                               // wave-uniform
       const uint32_t n_need = static_cast<uint32_t>(__popcll(mask));
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+      const uint32_t rank = WaveRank(mask);
       // (1) the parked rays first
       const uint32_t take = pool_count < n_need ? pool_count : n_need;
       if (kScout) {
@@ -168,7 +198,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
         casts = c3.x & 0x7fffffffu; carries = (c3.x >> 31) != 0u;
         if (!kLight && carries) { const float* from = carried_parked(sl); float* to = AMBER_CARRIED(); to[0] = from[0]; to[1] = from[1]; to[2] = from[2]; }
         origin_slot = static_cast<int>(c3.y);
-        if (kSig) { sig_obj = c3.z; sig_t = c3.w; }
+        if (kSig) { sig.obj = c3.z; sig.t = c3.w; }
         alive = true;
       }
       __builtin_amdgcn_wave_barrier();                        // (compiler fence: the park below overwrites the slots just read)
@@ -196,20 +226,10 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
           const uint32_t gbase = claim_next;
           claim_next += n_new;
           const unsigned long long m_alive = __ballot(alive);
-          if (kScout) {
-            if (alive) {                                      // park (pool_count is 0 here)
-              const uint32_t sl = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m_alive >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m_alive), 0u));
-              pool[sl * kChunks + 0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
-              pool[sl * kChunks + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), static_cast<uint32_t>(rng), static_cast<uint32_t>(rng >> 32));
-              pool[sl * kChunks + 2] = make_uint4(q, casts, static_cast<uint32_t>(origin_slot), scout_bound);
-            }
-          } else if (alive) {                                 // park (pool_count is 0 here)
-            const uint32_t sl = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m_alive >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m_alive), 0u));
-            pool[sl * kChunks + 0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
-            pool[sl * kChunks + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(w.x), __float_as_uint(w.y));
-            pool[sl * kChunks + 2] = make_uint4(__float_as_uint(w.z), static_cast<uint32_t>(rng), static_cast<uint32_t>(rng >> 32), q);
-            pool[sl * kChunks + 3] = make_uint4(casts | (carries ? 0x80000000u : 0u), static_cast<uint32_t>(origin_slot), sig_obj, sig_t);
-            if (!kLight && carries) { const float* from = AMBER_CARRIED(); float* to = carried_parked(sl); to[0] = from[0]; to[1] = from[1]; to[2] = from[2]; }
+          if (alive) {                                        // park (pool_count is 0 here)
+            const uint32_t sl = WaveRank(m_alive);
+            Pool::Park(pool + sl * kChunks, o, d, w, rng, q, casts, carries, origin_slot, sig, scout_bound);
+            if (!kLight && !kScout && carries) { const float* from = AMBER_CARRIED(); float* to = carried_parked(sl); to[0] = from[0]; to[1] = from[1]; to[2] = from[2]; }
           }
           pool_count = static_cast<uint32_t>(__popcll(m_alive));
           __builtin_amdgcn_wave_barrier();
@@ -240,7 +260,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
               GenerateEyeRay<kDivEye, SqrtModeOf(kSqrtMask, 4u), kScout>(eye, px, py, rng, o, d, ew, origin_slot, &near_edge);
               if (kScout) {                                   // ew: the guard quantity, not a weight; NaN fails the guard
                 scout_bound = (Abs(ew) >= amber_scout::kMinZ && Abs(ew) < __builtin_inff()) ? AMBER_ARG(cold, scout_bound0) : amber_scout::kSuspect;
-              } else w = v3(ew, ew, ew);                      // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
+              } else w = v3(ew, ew, ew);                  // Leading<RGB>(.., Radiant(weight)) lens_basic.h:139-144
               // (the pointer is read here and once more below, not held across the bookkeeping above: the two scalar registers it would occupy
               //  there are what the dividers need, and the loop has none to spare -- tests/test_headline_kernel_spills.py)
               const uint32_t* const pixel_mask = kTwoPhase ? AMBER_ARG(cold, pixel_mask) : nullptr;
@@ -253,7 +273,7 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
             }
             carries = false;
             casts = 0;
-            if (kSig) { sig_obj = 2166136261u; sig_t = 2166136261u; }
+            if (kSig) sig.Reset();
           }
           primary = kTwoPhase && !kLight && AMBER_ARG(AMBER_COLD_OPEN(), pixel_mask) != nullptr;
           AMBER_STAMP(1);
@@ -268,23 +288,28 @@ __global__ void __launch_bounds__(256, (kEngineSink & ~(AMBER_KERNEL_PHOTONS | A
     V3 meas = v3(0.f, 0.f, 0.f);
     if (alive) {
       if (!kLight && !kScout && carries) meas = ld3(AMBER_CARRIED());
+      // (The lane's path stays in separate locals, handed over one by one: held as one PathRay across the loop, the same instructions come out in
+      //  other registers -- EXPERIMENTS.md, device fold -- and the headline instantiations' instruction streams are pinned)
+      extras.use_premask = primary; extras.premask = premask;
       if (kLight) {
         const uint32_t plocal = Quotient(a.div_samples, q);
         const typename std::conditional<kPhotons, PhotonSink, SplatSink>::type sink = MakeLightSink<kPhotons>(a, a.path_offset + plocal, a.first_sample + (q - plocal * a.n_samples));
-        alive = PathStep<false, kEngine, true, false, false, 0u, kPhotons ? SINK_PHOTONS : SINK_SPLATS>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, &sink, false, 0u, AMBER_PATH_BVH_STACK);
+        extras.sink = &sink;
+        alive = PathStepOn<PathLightCfg<kEngine, kPhotons>>(sc, lds, o, d, w, meas, rng, casts, origin_slot, extras AMBER_STAMP_ARG);
       } else if (kSig) {
         Bounce b;
-        alive = PathStep<true, kEngine, false, kDivBasis, kDivHit, kSqrtMask>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, &b AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
-        sig_obj = Fnv32(sig_obj, static_cast<uint32_t>(b.object));
-        if (b.object >= 0) sig_t = Fnv32(sig_t, __float_as_uint(b.t));
-        if (!alive) AMBER_ARG(AMBER_COLD_OPEN(), sig)[q] = static_cast<unsigned long long>(sig_obj) | (static_cast<unsigned long long>(sig_t) << 32);
+        extras.trace = &b;
+        alive = PathStepOn<PathSigCfg<kEngine, kCold>>(sc, lds, o, d, w, meas, rng, casts, origin_slot, extras AMBER_STAMP_ARG);
+        sig.Add(b);
+        if (!alive) AMBER_ARG(AMBER_COLD_OPEN(), sig)[q] = sig.Packed();
       } else if (kScout) {
-        alive = PathStep<false, kEngine, false, kDivBasis, kDivHit, kSqrtMask, SINK_SCOUT>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK, &scout_bound);
+        extras.scout_bound = &scout_bound;
+        alive = PathStepOn<PathScoutCfg<kEngine, kCold>>(sc, lds, o, d, w, meas, rng, casts, origin_slot, extras AMBER_STAMP_ARG);
         // meas: the last hit's own Radiance.  The placeholder is what the record holds until the replay has traced the path with its weight
         emit = !alive && (((__float_as_uint(meas.x) | __float_as_uint(meas.y) | __float_as_uint(meas.z)) != 0u) || scout_bound > amber_scout::kLimit);
         meas = v3(0.f, 0.f, 0.f);
       } else {
-        alive = PathStep<false, kEngine, false, kDivBasis, kDivHit, kSqrtMask>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG, nullptr, primary, premask, AMBER_PATH_BVH_STACK);
+        alive = PathStepOn<PathBounceCfg<kEngine, kCold>>(sc, lds, o, d, w, meas, rng, casts, origin_slot, extras AMBER_STAMP_ARG);
       }
       if (!kLight && !kScout) {
         const bool nz = (__float_as_uint(meas.x) | __float_as_uint(meas.y) | __float_as_uint(meas.z)) != 0u;   // anything but +0 (RGB)

@@ -14,13 +14,16 @@
 //
 // The loop bound is read once; a launch that ran out of slots is repeated by the host as ever (what is replayed of it is discarded with it).  No atomics, no
 // rays counted: the scout has counted every cast of every path.
+// pt_megakernel's bounce for this engine, cold family; the stack cap is not that kernel's (no AMBER_PATH_BVH_STACK levels are staged here) but the default
+template <int kEngine> struct ReplayBounceCfg : PathBounceCfg<kEngine, true> { static constexpr int kBvhStackCap = AMBER_BVH_STACK; };
 template <int kEngine>
 __global__ void __launch_bounds__(256) replay_records_kernel(const RenderArgs a) {
   const DevScene& sc = a.scene;
   const EngineLds lds = StageEngineLds<kEngine, 1>(sc);                      // (ends with a barrier: before anything diverges)
   // pt_megakernel's arithmetic family for this engine (its kCold block): the same bits by each switch's own contract, and the same instructions besides
-  constexpr bool kDivBasis = (AMBER_SHARED_DIV_NORMALIZE & 1) != 0, kDivHit = (AMBER_SHARED_DIV_NORMALIZE & 2) != 0, kDivEye = (AMBER_SHARED_DIV_NORMALIZE & 4) != 0;
-  constexpr uint32_t kSqrtMask = static_cast<uint32_t>(AMBER_EXACT_SQRT);
+  constexpr bool kDivEye = (AMBER_SHARED_DIV_NORMALIZE & 4) != 0;
+  constexpr uint32_t kSqrtMask = ReplayBounceCfg<kEngine>::kSqrtMask;
+  const BounceExtras no_extras;
   const uint32_t claimed = *a.rec_count;
   const uint32_t n = claimed < a.rec_capacity ? claimed : a.rec_capacity;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
@@ -39,7 +42,7 @@ __global__ void __launch_bounds__(256) replay_records_kernel(const RenderArgs a)
 #ifdef AMBER_STAMPS
     StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-    while (PathStep<false, kEngine, false, kDivBasis, kDivHit, kSqrtMask>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG)) {}
+    while (PathStepOn<ReplayBounceCfg<kEngine>>(sc, lds, o, d, w, meas, rng, casts, origin_slot, no_extras AMBER_STAMP_ARG)) {}
     a.records[i] = make_uint4(q, __float_as_uint(meas.x), __float_as_uint(meas.y), __float_as_uint(meas.z));
   }
 }

@@ -52,12 +52,10 @@ __global__ void __launch_bounds__(256) wf_generate_kernel(const WfArgs a) {
     float* m = a.meas + static_cast<size_t>(pid) * 3u;
     m[0] = 0.f; m[1] = 0.f; m[2] = 0.f;
     const bool live = s_rel < a.n_samples;             // the last chunk may be short
-    const uint32_t lrow = Quotient(a.div_width, plocal);
-    const uint32_t px = plocal - lrow * sc.sensor.w;
-    const uint32_t py = FrameRow(a.row_begin, a.stripe_rows, a.stripe_period, a.div_stripe_rows, lrow);
-    uint64_t rng = XorShiftSeed(a.hashed_seed, px + py * sc.sensor.w, a.first_sample + s_rel);
+    const PathPlace at = PlacePixel(a, plocal);
+    uint64_t rng = PathSeed(a, at, s_rel);
     V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f); float ew = 0.f; int origin_slot = -1;
-    if (live) GenerateEyeRay(sc, px, py, rng, o, d, ew, origin_slot);
+    if (live) GenerateEyeRay(sc, at.px, at.py, rng, o, d, ew, origin_slot);
     // compact the live paths into queue 0 (all paths are live except in a short last chunk)
     const unsigned long long mask = __ballot(live);
     const uint32_t n_live = static_cast<uint32_t>(__popcll(mask));
@@ -66,7 +64,7 @@ __global__ void __launch_bounds__(256) wf_generate_kernel(const WfArgs a) {
     if ((threadIdx.x & 63u) == 0u && n_live) base = atomicAdd(a.counts + shard, n_live);
     base = __builtin_amdgcn_readfirstlane(base) + shard * a.shard_capacity;
     if (live) {
-      const uint32_t k = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+      const uint32_t k = base + WaveRank(mask);
       a.out.f[0][k] = o.x; a.out.f[1][k] = o.y; a.out.f[2][k] = o.z;
       a.out.f[3][k] = d.x; a.out.f[4][k] = d.y; a.out.f[5][k] = d.z;
       a.out.f[6][k] = ew; a.out.f[7][k] = ew; a.out.f[8][k] = ew;
@@ -93,19 +91,21 @@ __global__ void __launch_bounds__(256) wf_bounce_kernel(const WfArgs a) {
     const uint32_t k = base_k + lane;
     bool alive = k < n_in;
     const uint32_t kk = shard_base + (alive ? k : n_in - 1u);
-    V3 o = v3(a.in.f[0][kk], a.in.f[1][kk], a.in.f[2][kk]);
-    V3 d = v3(a.in.f[3][kk], a.in.f[4][kk], a.in.f[5][kk]);
-    V3 w = v3(a.in.f[6][kk], a.in.f[7][kk], a.in.f[8][kk]);
-    uint64_t rng = static_cast<uint64_t>(a.in.u[0][kk]) | (static_cast<uint64_t>(a.in.u[1][kk]) << 32);
+    PathRay ray;
+    ray.o = v3(a.in.f[0][kk], a.in.f[1][kk], a.in.f[2][kk]);
+    ray.d = v3(a.in.f[3][kk], a.in.f[4][kk], a.in.f[5][kk]);
+    ray.w = v3(a.in.f[6][kk], a.in.f[7][kk], a.in.f[8][kk]);
+    ray.rng = static_cast<uint64_t>(a.in.u[0][kk]) | (static_cast<uint64_t>(a.in.u[1][kk]) << 32);
     const uint32_t pid = a.in.u[2][kk];
-    uint32_t casts = a.in.u[3][kk] & 0x00ffffffu;
-    int origin_slot = static_cast<int>(a.in.u[3][kk] >> 24) - 1;
+    ray.casts = a.in.u[3][kk] & 0x00ffffffu;
+    ray.origin_slot = static_cast<int>(a.in.u[3][kk] >> 24) - 1;
     if (alive) {
-      V3 meas = v3(0.f, 0.f, 0.f);
+      V3& meas = ray.meas;
+      meas = v3(0.f, 0.f, 0.f);
 #ifdef AMBER_STAMPS
       StampCtx stamp_store{}; StampCtx* stamp_ctx = &stamp_store;
 #endif
-      alive = PathStep<false, kEngine>(sc, lds.objects, lds.stack, o, d, w, meas, rng, casts, origin_slot, nullptr AMBER_STAMP_ARG);
+      alive = PathStep<BounceCfg<kEngine>>(sc, lds, ray, BounceExtras{} AMBER_STAMP_ARG);
       ++rays;
       // measurement += weight * Le : non-zero only when a light was hit; x + (+-0) == x, so skipping zeros is exact
       if (__float_as_uint(meas.x) << 1 || __float_as_uint(meas.y) << 1 || __float_as_uint(meas.z) << 1) {
@@ -119,12 +119,12 @@ __global__ void __launch_bounds__(256) wf_bounce_kernel(const WfArgs a) {
     if (lane == 0u && n_live) base = atomicAdd(out_count, n_live);
     base = __builtin_amdgcn_readfirstlane(base) + shard_base;
     if (alive) {
-      const uint32_t q = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-      a.out.f[0][q] = o.x; a.out.f[1][q] = o.y; a.out.f[2][q] = o.z;
-      a.out.f[3][q] = d.x; a.out.f[4][q] = d.y; a.out.f[5][q] = d.z;
-      a.out.f[6][q] = w.x; a.out.f[7][q] = w.y; a.out.f[8][q] = w.z;
-      a.out.u[0][q] = static_cast<uint32_t>(rng); a.out.u[1][q] = static_cast<uint32_t>(rng >> 32);
-      a.out.u[2][q] = pid; a.out.u[3][q] = casts | (static_cast<uint32_t>(origin_slot + 1) << 24);
+      const uint32_t q = base + WaveRank(mask);
+      a.out.f[0][q] = ray.o.x; a.out.f[1][q] = ray.o.y; a.out.f[2][q] = ray.o.z;
+      a.out.f[3][q] = ray.d.x; a.out.f[4][q] = ray.d.y; a.out.f[5][q] = ray.d.z;
+      a.out.f[6][q] = ray.w.x; a.out.f[7][q] = ray.w.y; a.out.f[8][q] = ray.w.z;
+      a.out.u[0][q] = static_cast<uint32_t>(ray.rng); a.out.u[1][q] = static_cast<uint32_t>(ray.rng >> 32);
+      a.out.u[2][q] = pid; a.out.u[3][q] = ray.casts | (static_cast<uint32_t>(ray.origin_slot + 1) << 24);
     }
   }
   unsigned long long r = rays;

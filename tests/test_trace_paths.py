@@ -231,7 +231,7 @@ def test_the_scheduler(amber, engine, n_samples):
     rng = np.random.default_rng(11)
     same(rng.permutation(n), "a permutation")
     same(np.argsort(casts, kind="stable")[::-1], "longest first")
-    for m in (1, 63, 64, 65, 255, 256, 257, 1000):
+    for m in (1, 63, 64, 65, 129, 255, 256, 257, 1000):                          # around the wave, the claim of 64 (and two claims and one), the workgroup
         same(np.arange(m), f"prefix {m}")
     # 4097 rays by repetition, with states of their own: every ray equals its own single-ray answer computed in another batch shape
     idx = np.arange(4097) % n
